@@ -8,6 +8,12 @@ RJMCMC steps.  One bench "step" = one complete chain from the naive initialisati
 
 Prints ONE JSON line (rank 0).  `value` = proposals/s over the whole job with the score maps
 already resident in HBM.
+
+A plain run sets up, warms up, times --steps chains and prints the line.  --full adds everything
+else the bench measures: the roofline figures (with the traced chain they need), the convergence
+chain, the scene / mosaic / dataset / batched blocks and the CPU baselines; their --no-* / 0
+options still switch them off one by one.  --dump-outputs DIR writes the final configuration of
+every tile after the last timed chain (DIR/tileNNN_xy.npy, DIR/tileNNN_marks.npy, float64).
 """
 from __future__ import annotations
 
@@ -84,7 +90,15 @@ def main():
     ap.add_argument("--mosaic", type=int, default=4,
                     help="extra measurement, never part of `value` (0 = skip): BASELINE config 4 -- a MOSAIC x MOSAIC mosaic of the 512-px "
                          "tile generator (2048 x 2048 at 4), score maps given, mpp_log, through MPPModel.infer_image, tiles dealt to the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: roofline (traced chain), convergence, scene, mosaic, "
+                         "dataset, batched and the CPU baselines (each still subject to its own option above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write every tile's final configuration of the last step as DIR/tileNNN_xy.npy "
+                         "(x, y) and DIR/tileNNN_marks.npy (size, ratio, angle), float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from mpp_cnn_rs_object_detection_amd import distributed as mdist
@@ -136,13 +150,17 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # acceptance rate and mean population for the algorithmic-bytes figure: one traced chain (untimed)
+    # one untimed chain before anything is timed, also when the driver asks for --warmup 0: it loads the chain kernels'
+    # code objects.  With --full it is traced: acceptance rate and mean population for the algorithmic-bytes figure.
     for i, (xy, mk) in enumerate(inits):
         ctx.set_points(i, xy, mk)
     ctx.set_schedule(T0, alpha, Tt)
-    tr_out, _ = ctx.run(args.iters, seed=0, chain0=rank * T, trace_tile=0)
-    acc = float(tr_out["accepted"].mean())
-    mean_n = float(tr_out["n_after"].mean())
+    if args.full:
+        tr_out, _ = ctx.run(args.iters, seed=0, chain0=rank * T, trace_tile=0)
+        acc = float(tr_out["accepted"].mean())
+        mean_n = float(tr_out["n_after"].mean())
+    else:
+        ctx.run(args.iters, seed=0, chain0=rank * T)
 
     if world > 1:
         # communicator set-up (RCCL ring over xGMI) is not part of a step: one throw-away gather before anything is timed,
@@ -167,15 +185,23 @@ def main():
     proposals = world * T * args.steps * args.iters
     value = proposals / elapsed
     kernel_ms = float(np.mean(kms))
-    bpp = bytes_per_proposal(mean_n, n_cells, acc)
-    achieved = bpp * T * args.iters / (kernel_ms * 1e-3) / 1e9
     final_xy, _ = ctx.get_points(0)
     d = np.sqrt(((final_xy[:, None, :] - tiles[0].gt_xy[None]) ** 2).sum(-1)) if len(final_xy) else np.zeros((0, 1))
     matched = int((d.min(axis=0) <= 2).sum()) if len(final_xy) else 0
 
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the configuration of every tile after the last timed chain (seed
+        # steps - 1; tiles, model and seeds depend on the arguments only).  A tile holds at most point_capacity = 1024
+        # points (40 KB); beyond 64 MB in all only the first tiles of each rank are written.
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for i in range(min(T, (64 << 20) // (world * 1024 * 40))):
+            xy, mk = ctx.get_points(i)
+            np.save(os.path.join(args.dump_outputs, f"tile{rank * T + i:03d}_xy.npy"), xy.astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, f"tile{rank * T + i:03d}_marks.npy"), mk.astype(np.float64))
+
     lanes = {}
     lj = os.path.join(REPO, "profiles", "latest_lanes.json")
-    if os.path.exists(lj):           # committed rocprofv3 counters of the same two launches (profiles/tools/pmc_lanes.sh)
+    if args.full and os.path.exists(lj):   # committed rocprofv3 counters of the same two launches (profiles/tools/pmc_lanes.sh)
         with open(lj) as f:
             lanes = json.load(f)
 
@@ -203,7 +229,7 @@ def main():
 
     traffic, traffic_src, valu_busy = None, None, None
     tj = os.path.join(REPO, "profiles", "latest_traffic.json")
-    if os.path.exists(tj):          # PMC passes cannot run inside this timed process; this is the committed rocprofv3
+    if args.full and os.path.exists(tj):   # PMC passes cannot run inside this timed process; this is the committed rocprofv3
         with open(tj) as f:         # measurement of the same command (profiles/run_profile.sh), per launch
             t = json.load(f)
         if t.get("iters_per_launch") == args.iters and T == 1:
@@ -220,43 +246,46 @@ def main():
                         f"mpp_hrcM energies, {args.iters} RJMCMC steps per chain (T0=1, alpha=0.999), naive init",
             "iters_per_step": args.iters, "tiles_per_gpu": T, "spec_waves": args.spec, "spec_lanes": args.lanes,
             "parallelism": f"tile-parallel x{world}, one all-gather of detections" if world > 1 else "1 tile, 1 workgroup",
-            "accept_rate": acc, "mean_points": mean_n, "final_points": int(len(final_xy)),
+            **({"accept_rate": acc, "mean_points": mean_n} if args.full else {}), "final_points": int(len(final_xy)),
             "gt_matched_within_2px": matched, "gt_objects": int(len(tiles[0].gt_xy)),
         },
     }
-    # the sampler is priced against HBM bandwidth with the algorithmic bytes per proposal -- that is
-    # `roofline.frac`.  The kernel does not live under that roof (the configuration is in LDS, measured traffic is below the
-    # algorithmic bytes; one chain occupies 1 of 256 CUs and is bound by the latency of its own dependency chain): what it
-    # does with the instruction issue slots of the SIMDs it occupies is reported beside it as `roofline.issue`.
-    issue = valu_roofline("one", T * args.iters / (kernel_ms * 1e-3), 4 * T) if T == 1 else None
-    roof = {
-        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-        "traffic": traffic, "traffic_source": traffic_src, "traffic_unit": "bytes per launch",
-        "algorithmic_bytes_per_launch": bpp * T * args.iters, "algorithmic_bytes_per_proposal": bpp,
-        "kernel": "mpp_deep_kernel" if deep_stats else "mpp_chain_kernel", "kernel_ms": kernel_ms,
-        "kernel_note": ("a step of this bench = one chain of `iters` proposals = TWO launches since the hot start: mpp_chain_kernel (one "
-                        "wave per step) for the first proposals, until ~5 of 8 commit per round, then mpp_deep_kernel for the rest "
-                        f"({deep_stats['committed'] // max(1, T)} of {args.iters} here); `kernel_ms` = HIP-event time of "
-                        "both, which is what the rocprofv3 summary's two averages add up to") if deep_stats and deep_stats.get("committed", 0) and
-                       deep_stats["committed"] < T * args.iters else None,
-        "issue": issue, "occupied_cu_valu_busy_frac": valu_busy,
-        "note": "one chain = one workgroup (8 waves) = 1 of 256 CUs: `frac` prices it against the whole chip's HBM roof as SURVEY "
-                "8(d) asks; `issue.frac_of_the_simds_in_use` is the share of instruction issue slots of the 4 SIMDs it runs on; "
-                "many chains: see `batched.roofline`",
-    }
-    if deep_stats and deep_stats["rounds"]:
-        roof["deep_rounds"] = {
-            "rounds_per_launch": deep_stats["rounds"] / T, "steps_evaluated_per_committed": deep_stats["evaluated"] / max(1, deep_stats["committed"]),
-            "steps_committed_per_round": deep_stats["committed"] / deep_stats["rounds"],
-            "rounds_with_a_second_pass": deep_stats["rounds_with_change"],
-            "useful_lanes_per_wave_in_the_lane_phases": deep_stats["evaluated"] / deep_stats["rounds"] / args.spec,
-            "note": "every active lane evaluates a DIFFERENT step (no wave-uniform work repeated in 64 lanes as in the round-2 kernel): "
-                    "`useful_lanes...` of 64 lanes are active while proposals are drawn; the neighbour evaluation spreads the wave's "
-                    "(step, neighbour) pairs over all lanes",
+    if args.full:
+        bpp = bytes_per_proposal(mean_n, n_cells, acc)
+        achieved = bpp * T * args.iters / (kernel_ms * 1e-3) / 1e9
+        # the sampler is priced against HBM bandwidth with the algorithmic bytes per proposal -- that is
+        # `roofline.frac`.  The kernel does not live under that roof (the configuration is in LDS, measured traffic is below the
+        # algorithmic bytes; one chain occupies 1 of 256 CUs and is bound by the latency of its own dependency chain): what it
+        # does with the instruction issue slots of the SIMDs it occupies is reported beside it as `roofline.issue`.
+        issue = valu_roofline("one", T * args.iters / (kernel_ms * 1e-3), 4 * T) if T == 1 else None
+        roof = {
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": traffic_src, "traffic_unit": "bytes per launch",
+            "algorithmic_bytes_per_launch": bpp * T * args.iters, "algorithmic_bytes_per_proposal": bpp,
+            "kernel": "mpp_deep_kernel" if deep_stats else "mpp_chain_kernel", "kernel_ms": kernel_ms,
+            "kernel_note": ("a step of this bench = one chain of `iters` proposals = TWO launches since the hot start: mpp_chain_kernel (one "
+                            "wave per step) for the first proposals, until ~5 of 8 commit per round, then mpp_deep_kernel for the rest "
+                            f"({deep_stats['committed'] // max(1, T)} of {args.iters} here); `kernel_ms` = HIP-event time of "
+                            "both, which is what the rocprofv3 summary's two averages add up to") if deep_stats and deep_stats.get("committed", 0) and
+                           deep_stats["committed"] < T * args.iters else None,
+            "issue": issue, "occupied_cu_valu_busy_frac": valu_busy,
+            "note": "one chain = one workgroup (8 waves) = 1 of 256 CUs: `frac` prices it against the whole chip's HBM roof as SURVEY "
+                    "8(d) asks; `issue.frac_of_the_simds_in_use` is the share of instruction issue slots of the 4 SIMDs it runs on; "
+                    "many chains: see `batched.roofline`",
         }
-    result["roofline"] = roof
+        if deep_stats and deep_stats["rounds"]:
+            roof["deep_rounds"] = {
+                "rounds_per_launch": deep_stats["rounds"] / T, "steps_evaluated_per_committed": deep_stats["evaluated"] / max(1, deep_stats["committed"]),
+                "steps_committed_per_round": deep_stats["committed"] / deep_stats["rounds"],
+                "rounds_with_a_second_pass": deep_stats["rounds_with_change"],
+                "useful_lanes_per_wave_in_the_lane_phases": deep_stats["evaluated"] / deep_stats["rounds"] / args.spec,
+                "note": "every active lane evaluates a DIFFERENT step (no wave-uniform work repeated in 64 lanes as in the round-2 kernel): "
+                        "`useful_lanes...` of 64 lanes are active while proposals are drawn; the neighbour evaluation spreads the wave's "
+                        "(step, neighbour) pairs over all lanes",
+            }
+        result["roofline"] = roof
 
-    if rank == 0 and T >= 1 and not args.no_convergence:
+    if args.full and rank == 0 and T >= 1 and not args.no_convergence:
         # Wall-clock to convergence (BASELINE metric), untimed extra chain of tile 0 run in chunks:
         # (i) the whole schedule, (ii) time-to-quality = first chunk end with >= 95 % of the synthetic centres matched
         # within 2 px and the energy within 1 % of its final value.  Chunked launches continue the same Philox chain.
@@ -284,7 +313,7 @@ def main():
             "reference_probe": "reference NumPy sampler: 41.4 s for 30 257 steps of this tile (145/200 matched), BASELINE.md section 2",
         }
 
-    if args.scene > 0:
+    if args.full and args.scene > 0:
         # BASELINE config 5 (strong scaling over --gpus: ONE image, its tiles dealt to the ranks): every rank generates the
         # same image and the same seeded random-init nets, runs the nets on ITS region + halo, samples its tiles, takes part
         # in the gather / score all-reduces.  Wrapped: a failure here must not cost the headline line.
@@ -339,7 +368,7 @@ def main():
         except Exception as e:                                   # noqa: BLE001
             result["scene"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if args.mosaic > 0:
+    if args.full and args.mosaic > 0:
         # BASELINE config 4: the mosaic with the learned-weights config (no-calibration energies + logistic combinator)
         try:
             from mpp_cnn_rs_object_detection_amd.custom_types import ImageWMaps
@@ -383,7 +412,7 @@ def main():
         except Exception as e:                                   # noqa: BLE001
             result["mosaic"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if args.dataset_images > 0:
+    if args.full and args.dataset_images > 0:
         # Dataset inference (the reference's outer loop, mpp_model.py:220-262, is serial over images): the images are dealt to
         # the ranks in blocks -- what MPPModel.infer does under torchrun -- and every rank runs its block through the batched
         # path (tiles of many images in one launch).  Strong scaling over --gpus: the same images, more ranks.
@@ -448,7 +477,7 @@ def main():
         except Exception as e:                                   # noqa: BLE001
             result["dataset"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and args.batched_tiles > 0:
+    if args.full and rank == 0 and world == 1 and args.batched_tiles > 0:
         B, bt, bobj, biters = args.batched_tiles, args.batched_tile, args.batched_objects, 30257
         base = [synth.make_tile(bt, bobj, tile_id=1000 + i) for i in range(min(B, 8))]
         reps = (B + len(base) - 1) // len(base)
@@ -481,7 +510,7 @@ def main():
         }
         bctx.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle                     # the CPU restatement, timed as the baseline ("port")
         from concurrent.futures import ThreadPoolExecutor
         kd_cpu = kernels.make_kernels(maps, float(intensity[0]))

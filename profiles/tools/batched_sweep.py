@@ -5,7 +5,7 @@ out = {}
 cases = [(256, 8, 128), (256, 1, 128), (4096, 1, 128), (16384, 1, 128)]
 cases += [(t, s, c) for c in (128, 1024) for t in (512, 1024, 2048) for s in (8, 4, 2, 1)]
 for tiles, spec, cap in cases:
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--no-convergence", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "1", "--warmup", "0", "--no-convergence", "--no-cpu-baseline",
                         "--batched-tiles", str(tiles), "--batched-spec", str(spec), "--batched-capacity", str(cap)],
                        capture_output=True, text=True)
     try:

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_batched_$1; shift
 mkdir -p $OUT
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-convergence --batched-tiles 4096 $@"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline --no-convergence --batched-tiles 4096 $@"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/p1 -- python3 bench.py $ARGS > $OUT/bench.json 2> $OUT/err1.txt
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/p2 -- python3 bench.py $ARGS > /dev/null 2> $OUT/err2.txt
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/p3 -- python3 bench.py $ARGS > /dev/null 2> $OUT/err3.txt
