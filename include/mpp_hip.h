@@ -141,11 +141,17 @@ int mpp_synchronize(mpp_ctx *ctx);
  * ends when its last chain has cooled down);
  * "deep_fixed" (tests): a fixed number of steps per round instead of the adaptive depth; "deep_gain" (8..64, default 12):
  * the adaptive depth in eighths of the smoothed number of steps the last rounds committed; read-only "deep_stat0".."deep_stat3":
- * rounds, steps evaluated, rounds with a second pass, steps committed by the last mpp_run.  The chain is identical for every setting. "point_capacity": slots per tile (before mpp_set_maps), "cell_capacity" (points per
- * 32-px cell, at most 64), "auto_grow" (default 1): a chain that would exceed either capacity stops BEFORE that step and
- * mpp_run / mpp_replay double the capacity (while the chain still fits the 160 KB of LDS) and continue it -- the reference's
- * point set has no capacity (point_set/point_set.py:45-188); with 0 the call fails with -11 / -12 and the chain can be
- * continued by hand from the written-back state ("grow_events", read-only, counts the re-launches), "replicas" (before mpp_set_maps): v independent chains per tile, chain t on the maps of
+ * rounds, steps evaluated, rounds with a second pass, steps committed by the last mpp_run.  The chain is identical for every setting. "point_capacity": slots per tile (before mpp_set_maps, at most 65535: 16-bit slot indices), "cell_capacity" (points per
+ * 32-px cell, at most 2048), "auto_grow" (default 1): a chain that would exceed either capacity stops BEFORE that step and
+ * mpp_run / mpp_replay double the capacity and continue it -- the reference's point set has no capacity
+ * (point_set/point_set.py:45-188); with 0 the call fails with -11 / -12 and the chain can be continued by hand from the
+ * written-back state ("grow_events", read-only, counts the re-launches); "chain_state" (default 0, auto): a chain lives in
+ * its workgroup's LDS (160 KB); one that outgrows it -- a capacity the LDS cannot hold, or a context whose capacities exceed
+ * the LDS from the start -- continues with its state in device memory (the same chain, slower steps) while the other chains
+ * of the call and of later calls stay in LDS; 1: LDS only (such a chain fails the call with -12 / -11, a context too large
+ * for the LDS with -7); 2: every chain in device memory (tests, diagnosis); read-only "hbm_chains": chains that ran at
+ * least one launch in device memory in the last mpp_run / mpp_replay, "hbm_bytes": the device workspace held for them;
+ * -11 / -12 otherwise only remain at the limits of 2048 per cell and 65535 slots; "replicas" (before mpp_set_maps): v independent chains per tile, chain t on the maps of
  * tile t % n_tiles; "remap_table" (-1 auto, default; 0 never; 1 always): chains of a model with the
  * MPP_U_SHAPE_REMAP term read the remapped mark probabilities from [H][W][32] float64 tables built once per mpp_set_maps (as
  * the reference does, energy_setup_legacy.py:142-147) instead of evaluating three sigmoids per proposal -- the same values bit

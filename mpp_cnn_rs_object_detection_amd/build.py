@@ -20,7 +20,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibi
 # max-memory-clause schedulers: no gain or worse).  -unroll-runtime (loops whose trip count is only known at run time get an
 # unrolled body with a remainder loop): +0.6 % / +0.7 % on top.  Same arithmetic, byte-identical chains.
 _CHAIN_FLAGS = ["-mllvm", "-disable-machine-licm", "-mllvm", "-unroll-threshold=600", "-mllvm", "-unroll-runtime"]
-EXTRA = {"mpp_sampler.hip": _CHAIN_FLAGS, "mpp_deep.hip": _CHAIN_FLAGS}
+EXTRA = {"mpp_sampler.hip": _CHAIN_FLAGS, "mpp_sampler_hbm.hip": _CHAIN_FLAGS, "mpp_deep.hip": _CHAIN_FLAGS}
 
 
 def sources():
@@ -28,7 +28,7 @@ def sources():
 
 
 def deps():
-    return sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(os.path.dirname(HERE), "include", "mpp_hip.h"),
+    return sources() + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc")) + [os.path.join(os.path.dirname(HERE), "include", "mpp_hip.h"),
                                                                  os.path.abspath(__file__)]       # (the flags live here)
 
 
@@ -42,7 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                                                    for d in [src] + deps()[len(sources()):]):
             todo.append([HIPCC] + FLAGS + EXTRA.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
         objs.append(obj)
-    if todo:                                            # (the two chain-kernel files take 1.5 minutes each: side by side)
+    if todo:                                            # (the three chain-kernel files take 1.5 minutes each: side by side)
         from concurrent.futures import ThreadPoolExecutor
 
         def run(cmd):

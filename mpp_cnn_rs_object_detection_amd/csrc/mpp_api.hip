@@ -12,6 +12,13 @@
 
 extern "C" size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 extern "C" size_t mpp_chain_static_lds_bytes(int waves);
+extern "C" size_t mpp_chain_hbm_state_bytes(int cap, int ncell, int cell_cap);
+extern "C" size_t mpp_chain_hbm_lds_bytes(int spec, int rowbase_n);
+extern "C" hipError_t mpp_launch_chain_hbm(hipStream_t st, int waves, int grid, size_t lds, const DevParams *P,
+                                           const TileRef *tiles, int tile0, const long long *until, long long trace_base,
+                                           unsigned long long seed, unsigned int chain0, const mpp_proposal *tape,
+                                           int trace_tile, mpp_step_out *out, mpp_proposal *props, unsigned char *ws,
+                                           size_t ws_stride);
 extern "C" hipError_t mpp_launch_chain(hipStream_t st, int spec, int lanes, int occ, int grid, size_t lds,
                                        const DevParams *P, const TileRef *tiles, int tile0, const long long *until,
                                        long long trace_base, unsigned long long seed, unsigned int chain0, const mpp_proposal *tape,
@@ -115,6 +122,18 @@ struct mpp_ctx {
   // hipMalloc whose cost varies between 0 and 1.4 s (profiles/tools/probe_remap_cost.py) -- not worth it.
   size_t remap_budget = (size_t)2 << 30;
   int auto_grow = 1, grow_events = 0; // capacity overflow -> raise the capacity and continue (see run_chain)
+  // Where a chain's state lives (option chain_state, see run_chain): 0 auto, 1 LDS only, 2 device memory for every chain.
+  // cap / cell_cap are the context's capacities (cap is also the stride of the configuration arrays); an LDS launch runs
+  // with lds_cap / lds_cell once the two have been decoupled (0: the same as cap / cell_cap; lds_cap -1: no LDS launch fits)
+  int chain_state = 0;
+  int lds_cap = 0, lds_cell = 0;
+  std::vector<uint8_t> hbm_tile;     // per chain: an LDS launch could not hold it, it continues in device memory
+  int hbm_chains = 0;                // chains that ran at least one launch in device memory in the last mpp_run / mpp_replay
+  unsigned char *hbm_ws = nullptr;   // their workspace (contents rebuilt by every launch)
+  size_t hbm_ws_bytes = 0;
+  TileRef *d_route = nullptr;        // per-launch tile / until tables of a call whose chains are split between the two homes
+  long long *d_route_until = nullptr;
+  int route_n = 0;
   std::vector<double> intensity;
   std::vector<uint64_t> key_seed;    // per-chain Philox key / chain id (mpp_set_chain_keys); empty: the launch's seed, chain0 + tile
   std::vector<uint32_t> key_chain;
@@ -171,8 +190,8 @@ static int scratch_grid(mpp_ctx *c, int tile, int n, const int32_t **start, cons
 
 static const char *chain_error_text(int e) {
   switch (e) {
-    case 1: return "a cell of the spatial hash holds more points than cell_capacity allows and a larger one does not fit the LDS";
-    case 2: return "point capacity of the tile exceeded (a larger point_capacity does not fit the chain's LDS budget, or auto_grow is off)";
+    case 1: return "a cell of the spatial hash holds more points than cell_capacity allows";
+    case 2: return "point capacity of the tile exceeded";
     case 3: return "proposal refers to a point that does not exist or lies outside the tile";
     case 4: return "candidate list overflow (lower cell_capacity or report)";
   }
@@ -234,6 +253,9 @@ extern "C" int mpp_destroy(mpp_ctx *c) {
   if (c->g_start) (void)hipFree(c->g_start);
   if (c->g_cursor) (void)hipFree(c->g_cursor);
   if (c->g_items) (void)hipFree(c->g_items);
+  if (c->hbm_ws) (void)hipFree(c->hbm_ws);
+  if (c->d_route) (void)hipFree(c->d_route);
+  if (c->d_route_until) (void)hipFree(c->d_route_until);
   if (c->dp) (void)hipFree(c->dp);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -301,6 +323,9 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     c->cell_cap = (int)v; c->params_dirty = true;
   } else if (!strcmp(name, "auto_grow")) {
     c->auto_grow = v ? 1 : 0;
+  } else if (!strcmp(name, "chain_state")) {
+    if (v < 0 || v > 2) return fail(c, -1, "chain_state must be 0 (auto), 1 (LDS only) or 2 (device memory for every chain)");
+    c->chain_state = (int)v;
   } else if (!strcmp(name, "remap_table")) {
     if (v < -1 || v > 1) return fail(c, -1, "remap_table must be -1 (auto), 0 or 1");
     c->remap_mode = (int)v; c->remap_dirty = true;
@@ -333,6 +358,9 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "auto_grow")) return c->auto_grow;
   if (!strcmp(name, "remap_table")) return c->remap[0] ? 1 : 0;       // are the tables in use right now?
   if (!strcmp(name, "grow_events")) return c->grow_events;
+  if (!strcmp(name, "chain_state")) return c->chain_state;
+  if (!strcmp(name, "hbm_chains")) return c->hbm_chains;
+  if (!strcmp(name, "hbm_bytes")) return (int64_t)c->hbm_ws_bytes;
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)
@@ -487,6 +515,8 @@ extern "C" int mpp_set_maps(mpp_ctx *c, int n_tiles, int H, int W, const float *
   HIPCHK(c, hipMemcpyAsync(c->T, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if ((int)c->intensity.size() != c->n_tiles) c->intensity.assign(c->n_tiles, 1.0);
+  c->hbm_tile.assign(c->n_tiles, 0);
+  c->lds_cap = c->lds_cell = 0;
   c->have_maps = true;
   c->tiles_dirty = true;
   refresh_grid(c);
@@ -1070,70 +1100,202 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
     trace_base = s0;
   }
   c->last_ms = 0.0;
+  c->hbm_chains = 0;
+  if ((int)c->hbm_tile.size() != c->n_tiles) c->hbm_tile.assign(c->n_tiles, 0);
   // many chains in one launch: prefer the instantiation that lets two waves share a SIMD
   const int occ = (grid >= 1024) ? 2 : 1;
+  // Routing (chain_state 0, auto): a call runs every chain in LDS, exactly as without this path, until a chain no longer
+  // fits -- a capacity overflow that a larger LDS launch cannot hold, or a context whose capacities exceed the LDS from the
+  // start (where an LDS-only context stops with -12 / -11 / -7).  From then on the LDS launches keep the capacities
+  // that fit (lds_cap / lds_cell) and only the chains that need more -- the overflowing ones, and any whose population
+  // exceeds lds_cap -- go to mpp_chain_hbm_kernel, in later calls too.  An LDS launch must never see a chain with more points
+  // than its capacity (the kernel would clamp and write back a truncated configuration): the point counts are read back
+  // and each home gets a compacted tile / until table.  Its entries carry the chain's own Philox key (key_on = 1 with the
+  // launch's (seed, chain0 + tile) unless set by mpp_set_chain_keys), so the stream does not depend on the position.
+  std::vector<int32_t> herr(grid), hn(grid);
+  std::vector<uint8_t> in_hbm(grid, 0), ran_hbm(grid, 0);
+  std::vector<long long> h_until;
+  std::vector<TileRef> tab(grid);
+  std::vector<long long> tab_until(grid);
+  const int hbm_waves = (c->lanes == 0 && c->spec == 1) ? 1 : 8;
   // hot start: one wave per step until the chain has cooled down (ERR_HANDOVER), then deep rounds -- the same chain either way
   // (launches of a few chains only: the launch that hands over ends when its LAST chain has cooled down, the others' CUs idle
   //  until then -- 256 tiles of config 5's scene lost 3 ms to that, one tile gains 6)
-  bool hot_start = deep_nmax > 0 && c->handover && c->spec == 8 && c->lanes == 0 && trace_tile < 0 && !c->deep_fixed && n_steps >= 4096 &&
-                   grid <= c->handover_tiles && chain_lds_total(c, c->cap, c->cell_cap) <= MPP_LDS_LIMIT;
+  bool hot_start = deep_nmax > 0 && c->handover && c->spec == 8 && c->lanes == 0 && trace_tile < 0 && !c->deep_fixed && n_steps >= 4096;
+  bool hot_checked = false;
   for (;;) {
-    size_t lds = chain_lds(c, c->cap, c->cell_cap);
-    // deep rounds need room for their step reports next to the chain state: halve the round until it fits, or do without
-    int nmax = deep_nmax;
-    const int ncell_ = c->hp.nx * c->hp.ny, rb_ = c->hp.rowbase_lds ? c->H + 1 : 0, ext_ = has_classic(c->hp.model) ? 1 : 0;
-    while (nmax >= c->spec && nmax > 0 &&
-           mpp_deep_lds_bytes(c->cap, ncell_, c->cell_cap, rb_, c->spec, nmax, ext_) + mpp_deep_static_lds_bytes(c->spec) > MPP_LDS_LIMIT)
-      nmax /= 2;
-    if (nmax < c->spec || nmax < 8) nmax = 0;
-    if (c->cell_cap > 64) nmax = 0;        // (the deep kernel lists a cell's candidates in a 64-bit mask: fuller cells run one step per wave)
-    if (hot_start && nmax > 0) nmax = 0;
-    else hot_start = false;
-    if (c->hp.handover != (hot_start ? c->handover_at : 0)) { c->hp.handover = hot_start ? c->handover_at : 0; c->params_dirty = true; if ((rc = push_state(c))) return rc; }
-    if (nmax > 0) lds = mpp_deep_lds_bytes(c->cap, ncell_, c->cell_cap, rb_, c->spec, nmax, ext_);
-    else if (chain_lds_total(c, c->cap, c->cell_cap) > MPP_LDS_LIMIT)
-      return fail(c, -7, "chain state needs %zu B of LDS (> %d): lower point_capacity/cell_capacity/spec_waves or tile size",
-                  lds, MPP_LDS_LIMIT);
-    c->hp.cap = c->cap; c->hp.cell_cap = c->cell_cap;
+    // ---- the capacities of an LDS launch, and which chains it may take
+    const bool decoupled = c->lds_cap != 0;
+    const int lcap = decoupled ? c->lds_cap : c->cap, lcell = decoupled ? c->lds_cell : c->cell_cap;
+    bool route = c->chain_state == 2 || lcap < c->cap;
+    for (int t = 0; t < grid && !route; ++t) route = c->hbm_tile[tile0 + t] != 0;
+    int n_lds = grid, n_hbm = 0;
+    if (route) {
+      HIPCHK(c, hipMemcpy(hn.data(), c->n + tile0, grid * sizeof(int32_t), hipMemcpyDeviceToHost));
+      n_lds = 0;
+      for (int t = 0; t < grid; ++t) {
+        in_hbm[t] = c->chain_state == 2 || lcap < 0 || c->hbm_tile[tile0 + t] || hn[t] > lcap;
+        n_lds += in_hbm[t] ? 0 : 1;
+      }
+      n_hbm = grid - n_lds;
+    }
+    const bool split = n_hbm > 0;            // compacted tables: LDS chains first, then the HBM chains
+    int trace_l = trace_tile, trace_h = -1;
+    if (split) {
+      if (h_until.empty()) {
+        h_until.resize(grid);
+        HIPCHK(c, hipMemcpy(h_until.data(), c->until + tile0, grid * sizeof(long long), hipMemcpyDeviceToHost));
+      }
+      if (c->route_n < grid) {
+        if (c->d_route) (void)hipFree(c->d_route);
+        if (c->d_route_until) (void)hipFree(c->d_route_until);
+        c->d_route = nullptr; c->d_route_until = nullptr; c->route_n = 0;
+        HIPCHK(c, dalloc(&c->d_route, (size_t)grid)); HIPCHK(c, dalloc(&c->d_route_until, (size_t)grid));
+        c->route_n = grid;
+      }
+      trace_l = -1;
+      int il = 0, ih = n_lds;
+      for (int t = 0; t < grid; ++t) {
+        const int i = in_hbm[t] ? ih++ : il++;
+        TileRef r = c->h_tiles[tile0 + t];
+        if (!r.key_on) { r.key_on = 1; r.key_seed = seed; r.key_chain = chain0 + (uint32_t)(tile0 + t); }
+        tab[i] = r; tab_until[i] = h_until[t];
+        if (tile0 + t == trace_tile) (in_hbm[t] ? trace_h : trace_l) = i;
+        if (in_hbm[t]) ran_hbm[t] = 1;
+      }
+      HIPCHK(c, hipMemcpy(c->d_route, tab.data(), sizeof(TileRef) * grid, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->d_route_until, tab_until.data(), sizeof(long long) * grid, hipMemcpyHostToDevice));
+      int nh = 0;
+      for (int t = 0; t < grid; ++t) nh += ran_hbm[t];
+      c->hbm_chains = nh;
+    }
+    const TileRef *tiles_l = split ? c->d_route : c->d_tiles;
+    const long long *until_l = split ? c->d_route_until : c->until;
+    const int tile0_l = split ? 0 : tile0;
+    if (!hot_checked) {                      // (decided once per call, on the first launch's LDS chains)
+      hot_start = hot_start && n_lds <= c->handover_tiles && n_lds > 0 && chain_lds_total(c, lcap, lcell) <= MPP_LDS_LIMIT;
+      hot_checked = true;
+    }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (nmax > 0) {
-      int fixed = c->deep_fixed > nmax ? nmax : c->deep_fixed;
-      if (fixed > 0) { fixed = fixed / c->spec * c->spec; if (fixed < c->spec) fixed = c->spec; }
-      HIPCHK(c, mpp_launch_deep(c->stream, c->spec, occ, grid, lds, &c->hp, c->d_tiles, tile0, c->until, trace_base, seed, chain0,
-                                trace_tile, d_out, d_props, nmax, fixed, c->deep_gain, c->deep_stats, has_classic(c->hp.model) ? 1 : 0));
-    } else
-    HIPCHK(c, mpp_launch_chain(c->stream, c->spec, c->lanes, occ, grid, lds, &c->hp, c->d_tiles, tile0, c->until, trace_base, seed,
-                               chain0, d_tape, trace_tile, d_out, d_props));
+    if (n_lds > 0) {
+      size_t lds = chain_lds(c, lcap, lcell);
+      // deep rounds need room for their step reports next to the chain state: halve the round until it fits, or do without
+      int nmax = deep_nmax;
+      const int ncell_ = c->hp.nx * c->hp.ny, rb_ = c->hp.rowbase_lds ? c->H + 1 : 0, ext_ = has_classic(c->hp.model) ? 1 : 0;
+      while (nmax >= c->spec && nmax > 0 &&
+             mpp_deep_lds_bytes(lcap, ncell_, lcell, rb_, c->spec, nmax, ext_) + mpp_deep_static_lds_bytes(c->spec) > MPP_LDS_LIMIT)
+        nmax /= 2;
+      if (nmax < c->spec || nmax < 8) nmax = 0;
+      if (lcell > 64) nmax = 0;            // (the deep kernel lists a cell's candidates in a 64-bit mask: fuller cells run one step per wave)
+      if (hot_start && nmax > 0) nmax = 0;
+      else hot_start = false;
+      if (c->hp.handover != (hot_start ? c->handover_at : 0)) { c->hp.handover = hot_start ? c->handover_at : 0; c->params_dirty = true; if ((rc = push_state(c))) return rc; }
+      if (nmax > 0) lds = mpp_deep_lds_bytes(lcap, ncell_, lcell, rb_, c->spec, nmax, ext_);
+      else if (chain_lds_total(c, lcap, lcell) > MPP_LDS_LIMIT) {
+        if (c->chain_state == 1)
+          return fail(c, -7, "chain state needs %zu B of LDS (> %d): lower point_capacity/cell_capacity/spec_waves or tile size",
+                      lds, MPP_LDS_LIMIT);
+        // the context asks for more than an LDS launch holds: LDS launches keep the largest halving that fits (none: every
+        // chain in device memory), the chains that do not fit it continue in device memory
+        int nc = lcap, ne = lcell;
+        while (nc > 64 && chain_lds_total(c, nc, ne) > MPP_LDS_LIMIT) nc /= 2;
+        while (ne > 4 && chain_lds_total(c, nc, ne) > MPP_LDS_LIMIT) ne /= 2;
+        if (chain_lds_total(c, nc, ne) > MPP_LDS_LIMIT) nc = -1;
+        c->lds_cap = nc; c->lds_cell = ne;
+        continue;
+      }
+      c->hp.cap = c->cap; c->hp.cell_cap = c->cell_cap;
+      DevParams lp = c->hp;
+      lp.cap = lcap; lp.cell_cap = lcell;
+      if (nmax > 0) {
+        int fixed = c->deep_fixed > nmax ? nmax : c->deep_fixed;
+        if (fixed > 0) { fixed = fixed / c->spec * c->spec; if (fixed < c->spec) fixed = c->spec; }
+        HIPCHK(c, mpp_launch_deep(c->stream, c->spec, occ, n_lds, lds, &lp, tiles_l, tile0_l, until_l, trace_base, seed, chain0,
+                                  trace_l, d_out, d_props, nmax, fixed, c->deep_gain, c->deep_stats, has_classic(c->hp.model) ? 1 : 0));
+      } else
+      HIPCHK(c, mpp_launch_chain(c->stream, c->spec, c->lanes, occ, n_lds, lds, &lp, tiles_l, tile0_l, until_l, trace_base, seed,
+                                 chain0, d_tape, trace_l, d_out, d_props));
+    }
+    if (n_hbm > 0) {                         // the chains that outgrew the LDS: state in the workspace, capacities cap / cell_cap
+      const int ncell = c->hp.nx * c->hp.ny;
+      const size_t stride = mpp_chain_hbm_state_bytes(c->cap, ncell, c->cell_cap), need = stride * (size_t)n_hbm;
+      if (need > c->hbm_ws_bytes) {
+        if (c->hbm_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->hbm_ws); }
+        c->hbm_ws = nullptr; c->hbm_ws_bytes = 0;
+        HIPCHK(c, hipMalloc((void **)&c->hbm_ws, need));
+        c->hbm_ws_bytes = need;
+      }
+      c->hp.cap = c->cap; c->hp.cell_cap = c->cell_cap;
+      DevParams hpp = c->hp;
+      hpp.handover = 0;
+      const size_t lds = mpp_chain_hbm_lds_bytes(hbm_waves, c->hp.rowbase_lds ? c->H + 1 : 0);
+      HIPCHK(c, mpp_launch_chain_hbm(c->stream, hbm_waves, n_hbm, lds, &hpp, c->d_route, n_lds, c->d_route_until, trace_base,
+                                     seed, chain0, d_tape, trace_h, d_out, d_props, c->hbm_ws, stride));
+    }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev1));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     c->last_ms += ms;
-    std::vector<int32_t> herr(grid);
     HIPCHK(c, hipMemcpy(herr.data(), c->errd + tile0, grid * sizeof(int32_t), hipMemcpyDeviceToHost));
-    bool cell = false, point = false, cooled = false;
+    bool cell = false, point = false, cell_h = false, point_h = false, cooled = false;
     for (int t = 0; t < grid; ++t) {
-      if (herr[t] == 1) cell = true;
-      else if (herr[t] == 2) point = true;
+      if (herr[t] == 1) (in_hbm[t] ? cell_h : cell) = true;
+      else if (herr[t] == 2) (in_hbm[t] ? point_h : point) = true;
       else if (herr[t] == 5) cooled = true;
       else if (herr[t]) return fail(c, -10 - herr[t], "tile %d: %s", tile0 + t, chain_error_text(herr[t]));
     }
     if (cooled) {                          // (a launch that ended for a capacity as well grows first and keeps its hot start)
       for (int t = 0; t < grid; ++t) if (herr[t] == 5) herr[t] = 0;
       HIPCHK(c, hipMemcpy(c->errd + tile0, herr.data(), grid * sizeof(int32_t), hipMemcpyHostToDevice));
-      if (!cell && !point) { hot_start = false; continue; }
+      if (!cell && !point && !cell_h && !point_h) { hot_start = false; continue; }
     }
-    if (!cell && !point) return 0;
-    const bool can_grow = c->auto_grow != 0;
-    int new_cell = c->cell_cap, new_cap = c->cap;
-    if (cell) new_cell = c->cell_cap * 2 > MPP_CELL_CAP_MAX ? MPP_CELL_CAP_MAX : c->cell_cap * 2;
-    if (point) new_cap = c->cap * 2 > 65535 ? 65535 : c->cap * 2;
-    if (!can_grow || (cell && new_cell == c->cell_cap) || (point && new_cap == c->cap) ||
-        chain_lds_total(c, new_cap, new_cell) > MPP_LDS_LIMIT) {
+    if (!cell && !point && !cell_h && !point_h) return 0;
+    // the first stopped chain, and why it cannot go on
+    auto stop = [&](const char *why) {
       for (int t = 0; t < grid; ++t)
-        if (herr[t]) return fail(c, -10 - herr[t], "tile %d: %s", tile0 + t, chain_error_text(herr[t]));
+        if (herr[t]) return fail(c, -10 - herr[t], "tile %d: %s (%s)", tile0 + t, chain_error_text(herr[t]), why);
+      return fail(c, -1, "no stopped chain");
+    };
+    if (!c->auto_grow) return stop("auto_grow is off");
+    int new_cap = c->cap, new_cell = c->cell_cap;
+    if (cell || point) {                     // LDS chains: double the LDS launch's capacity where that still fits the LDS
+      int nl_cap = lcap, nl_cell = lcell;
+      bool r_cell = false, r_point = false;  // ... and where it does not, those chains continue in device memory
+      if (cell) {
+        const int v = lcell * 2 > MPP_CELL_CAP_MAX ? MPP_CELL_CAP_MAX : lcell * 2;
+        if (v == lcell) return stop("cell_capacity is at its limit");
+        if (chain_lds_total(c, nl_cap, v) <= MPP_LDS_LIMIT) nl_cell = v; else r_cell = true;
+      }
+      if (point) {
+        const int v = lcap * 2 > 65535 ? 65535 : lcap * 2;
+        if (v == lcap) return stop("point_capacity is at its limit 65535 (16-bit slot indices)");
+        if (chain_lds_total(c, v, nl_cell) <= MPP_LDS_LIMIT) nl_cap = v; else r_point = true;
+      }
+      if ((r_cell || r_point) && c->chain_state == 1)
+        return stop("larger capacities do not fit the chain's LDS budget and chain_state is 1: LDS only");
+      if (r_cell || r_point) {
+        if (!decoupled) { c->lds_cap = lcap; c->lds_cell = lcell; }
+        for (int t = 0; t < grid; ++t)
+          if (!in_hbm[t] && ((herr[t] == 1 && r_cell) || (herr[t] == 2 && r_point))) c->hbm_tile[tile0 + t] = 1;
+        if (r_cell) { const int v = lcell * 2 > MPP_CELL_CAP_MAX ? MPP_CELL_CAP_MAX : lcell * 2; if (v > new_cell) new_cell = v; }
+        if (r_point) { const int v = lcap * 2 > 65535 ? 65535 : lcap * 2; if (v > new_cap) new_cap = v; }
+      }
+      if (c->lds_cap != 0) { c->lds_cap = nl_cap; c->lds_cell = nl_cell; }
+      if (nl_cap > new_cap) new_cap = nl_cap;
+      if (nl_cell > new_cell) new_cell = nl_cell;
     }
-    if (point && (rc = grow_points(c, new_cap))) return rc;
+    if (point_h) {
+      if (c->cap >= 65535) return stop("point_capacity is at its limit 65535 (16-bit slot indices)");
+      const int v = c->cap * 2 > 65535 ? 65535 : c->cap * 2;
+      if (v > new_cap) new_cap = v;
+    }
+    if (cell_h) {
+      if (c->cell_cap >= MPP_CELL_CAP_MAX) return stop("cell_capacity is at its limit");
+      const int v = c->cell_cap * 2 > MPP_CELL_CAP_MAX ? MPP_CELL_CAP_MAX : c->cell_cap * 2;
+      if (v > new_cell) new_cell = v;
+    }
+    if (new_cap > c->cap && (rc = grow_points(c, new_cap))) return rc;
     c->cell_cap = new_cell;
     c->grow_events += 1;
     // clear the two overflow codes (sticky otherwise) and bring the tile table / parameters up to date

@@ -124,6 +124,58 @@ __device__ inline Lds carve(unsigned char *base, int cap, int ncell, int cell_ca
   return L;
 }
 
+// ---- the HBM-state chain (mpp_sampler_hbm.hip): a chain that outgrows the LDS keeps everything that scales with its
+// capacity -- the 11 per-point double arrays, xy, order, gate, cell_items and cell_cnt -- in its own slice of a device
+// workspace (each array 256-B aligned); the per-step buffers (edges, trig, rowbase, the stash, clip, rec, sh) and the
+// staged parameter block stay in LDS, whose footprint then no longer depends on the capacity.
+#define HBM_ALIGN 256
+__host__ __device__ inline size_t hbm_align(size_t b) { return (b + HBM_ALIGN - 1) & ~(size_t)(HBM_ALIGN - 1); }
+__host__ __device__ inline size_t hbm_state_bytes(int cap, int ncell, int cell_cap) {
+  return 11 * hbm_align((size_t)cap * sizeof(double)) + hbm_align((size_t)cap * sizeof(int)) +
+         hbm_align((size_t)cap * sizeof(unsigned short)) + hbm_align((size_t)ncell * cell_cap * sizeof(unsigned short)) +
+         hbm_align((size_t)ncell * sizeof(unsigned short)) + hbm_align((size_t)cap);
+}
+__host__ __device__ inline size_t hbm_lds_bytes(int spec, int rowbase_n, int waves) {
+  size_t b = 0;
+  b += (size_t)waves * CLIP_SLOTS * 32 * sizeof(double);
+  b += (size_t)rowbase_n * sizeof(double);
+  b += (size_t)5 * MPP_NCLASS * sizeof(double);               // edges, trig
+  b += (size_t)2 * spec * STASH * sizeof(double);
+  b += (size_t)spec * STASH * sizeof(unsigned short);
+  b = (b + 15) & ~(size_t)15;
+  b += (size_t)spec * sizeof(Rec);
+  b += 16 * sizeof(int);
+  return b + 64;
+}
+__device__ inline Lds carve_hbm(unsigned char *lds, unsigned char *ws, int cap, int ncell, int cell_cap, int spec,
+                                int rowbase_n, int waves) {
+  Lds L;
+  const size_t dc = hbm_align((size_t)cap * sizeof(double));
+  L.s = (double *)ws; L.r = (double *)(ws + dc); L.a = (double *)(ws + 2 * dc); L.ca = (double *)(ws + 3 * dc);
+  L.sa = (double *)(ws + 4 * dc); L.hl = (double *)(ws + 5 * dc); L.hw = (double *)(ws + 6 * dc);
+  L.rad = (double *)(ws + 7 * dc); L.lin = (double *)(ws + 8 * dc); L.red0 = (double *)(ws + 9 * dc);
+  L.red1 = (double *)(ws + 10 * dc);
+  size_t o = 11 * dc;
+  L.xy = (int *)(ws + o); o += hbm_align((size_t)cap * sizeof(int));
+  L.order = (unsigned short *)(ws + o); o += hbm_align((size_t)cap * sizeof(unsigned short));
+  L.cell_items = (unsigned short *)(ws + o); o += hbm_align((size_t)ncell * cell_cap * sizeof(unsigned short));
+  L.cell_cnt = (unsigned short *)(ws + o); o += hbm_align((size_t)ncell * sizeof(unsigned short));
+  L.gate = ws + o;
+  double *d = (double *)lds;
+  L.edges = d; d += 3 * MPP_NCLASS;
+  L.trig = d; d += 2 * MPP_NCLASS;
+  L.rowbase = rowbase_n > 0 ? d : nullptr; d += rowbase_n;
+  L.stash_v0 = d; d += (size_t)spec * STASH; L.stash_v1 = d; d += (size_t)spec * STASH;
+  L.clip = d; d += (size_t)waves * CLIP_SLOTS * 32;
+  unsigned short *u = (unsigned short *)d;
+  L.stash_slot = u; u += (size_t)spec * STASH;
+  size_t off = (size_t)((unsigned char *)u - lds);
+  off = (off + 15) & ~(size_t)15;
+  L.rec = (Rec *)(lds + off);
+  L.sh = (int *)(lds + off + (size_t)spec * sizeof(Rec));
+  return L;
+}
+
 // the pair terms' parameters, read ONCE per launch into registers: inside the non-unrolled loops of eval_delta every
 // P->model.pair[p].field was a scalar load followed by a wait (the chain kernel is built without machine LICM)
 // a wave-uniform value pinned to scalar registers (the parameter block may be an LDS copy, whose reads land in vector
@@ -140,6 +192,21 @@ __device__ __forceinline__ double launder_d(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 struct PairRegs { int kind, reduce, maxd2, gated; double coef, p0, max_dist; };
+// the parameter block as the chain kernel reads it: an LDS copy for chains of MPP_LDS_PARAMS_MIN_WAVES waves and more
+template <bool IN_LDS>
+__device__ __forceinline__ const DevParams *stage_params(const DevParams &Pv, int nthr) {
+  if constexpr (IN_LDS) {
+    __shared__ DevParams s_P;
+    const int *src = (const int *)&Pv;
+    int *dst = (int *)&s_P;
+    for (int i = threadIdx.x; i < (int)(sizeof(DevParams) / 4); i += nthr) dst[i] = src[i];
+    __syncthreads();
+    return &s_P;
+  } else {
+    return &Pv;
+  }
+}
+
 // The grid facts every step asks for many times.  The parameter block lives in the kernel-argument segment, every
 // P->field in the step loop is a scalar load (the kernel is built without machine LICM), and a scalar load's wait --
 // s_waitcnt lgkmcnt(0): scalar loads return out of order -- also drains every LDS read in flight.  These seven are read
@@ -189,12 +256,31 @@ __device__ __forceinline__ double finish_energy_c(const Chain &c, double lin) {
   return c.comb == MPP_C_LOGISTIC ? 2.0 * sigmoid_d(lin) - 1.0 : lin;
 }
 
+// MPP_STATE_HBM: defined to 1 by the translation unit of the HBM-state chain (mpp_sampler_hbm.hip) before it includes
+// this header; every other instantiation keeps its whole state in LDS
+#ifndef MPP_STATE_HBM
+#define MPP_STATE_HBM 0
+#endif
 __device__ __forceinline__ void wave_lds_fence() {
+#if MPP_STATE_HBM
+  // The state arrays are in device memory.  The argument below does not carry over: the LLVM AMDGPU memory model
+  // (gfx942 / gfx950 code sequences) emits nothing for a wavefront-scope fence and promises in-order completion of one
+  // wave's vector-memory operations, but it states no rule that orders one lane's global store before ANOTHER lane's
+  // later load through the vector L1 -- coherence "between the lanes of a wavefront" is asserted in prose, not given as a
+  // synchronizes-with edge of the model.  Nothing here relies on that reading: a workgroup-scope release / acquire is the
+  // model's documented way to make one thread's global stores visible to another thread of the same workgroup (it costs
+  // an s_waitcnt on the outstanding memory operations of the committing wave, once per commit step).  The lockstep tests
+  // cannot prove the absence of a race; this argument is what the HBM chain rests on.
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#else
   // LDS traffic of one wave is executed in order; this only stops the compiler from moving
   // the loads of other lanes' data above the stores that produce them
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#endif
 }
 __device__ __forceinline__ double readlane_d(double v, int lane) {
   long long b = __double_as_longlong(v);

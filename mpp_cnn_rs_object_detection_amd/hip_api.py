@@ -198,7 +198,9 @@ class MppContext:
 
     def __init__(self, device: int = 0, point_capacity: Optional[int] = None, cell_capacity: Optional[int] = None,
                  spec_waves: Optional[int] = None, spec_lanes: Optional[int] = None, replicas: Optional[int] = None,
-                 deep: Optional[int] = None):
+                 deep: Optional[int] = None, chain_state: Optional[int] = None):
+        """chain_state: where a chain's state lives -- 0 auto (LDS; a chain that outgrows it continues in device memory),
+        1 LDS only (such a chain stops with -12 / -11), 2 device memory for every chain (tests, diagnosis)."""
         self._L = load_library()
         h = C.c_void_p()
         rc = self._L.mpp_create(int(device), C.byref(h))
@@ -223,6 +225,8 @@ class MppContext:
             self.set_option("replicas", replicas)
         if deep is not None:
             self.set_option("deep", deep)
+        if chain_state is not None:
+            self.set_option("chain_state", chain_state)
         if os.environ.get("MPP_HANDOVER_TILES"):           # (experiments: the largest launch that starts hot)
             self.set_option("handover_tiles", int(os.environ["MPP_HANDOVER_TILES"]))
         if os.environ.get("MPP_HANDOVER_AT"):

@@ -451,6 +451,8 @@ class MPPModel:
         self.last_intensity = sampler.intensity
         logging.info(f"ran {len(mine)} rjmcmc chains of {total} steps in one launch in "
                      f"{time.perf_counter() - start:.2f}s (kernel {sampler.kernel_ms:.1f} ms)")
+        if sampler.hbm_chains:
+            logging.info(f"{sampler.hbm_chains} chain(s) outgrew the LDS and continued with their state in device memory")
         return sampler
 
     #: tiles sampled per launch when a dataset is inferred on one GPU: tiles of consecutive images are sampled together
@@ -496,6 +498,8 @@ class MPPModel:
         out = sampler.run(total, snaps, 1, p["init_temperature"], alpha, T_target, seed=0, chain0=0, as_arrays=on_device)
         logging.info(f"ran {len(tiles)} rjmcmc chains ({len(images)} images) of {total} steps in one launch in "
                      f"{time.perf_counter() - start:.2f}s (kernel {sampler.kernel_ms:.1f} ms)")
+        if sampler.hbm_chains:
+            logging.info(f"{sampler.hbm_chains} chain(s) outgrew the LDS and continued with their state in device memory")
         if on_device:
             aggregated = []
             for first, n in layout:

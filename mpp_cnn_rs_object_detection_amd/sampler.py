@@ -166,6 +166,7 @@ class TileBatchSampler:
 
         done = 0
         self.kernel_ms = 0.0
+        self.hbm_chains = 0                                    # chains that outgrew the LDS and ran in device memory
         for t in wanted:                                       # the state after step t = after t+1 steps
             self._run_resumable(t + 1 - done, seed, chain0)
             done = t + 1
@@ -179,6 +180,7 @@ class TileBatchSampler:
     def _run_resumable(self, n_steps: int, seed: int, chain0: int):
         self.ctx.run(n_steps, seed, chain0)
         self.kernel_ms += self.ctx.last_kernel_ms()
+        self.hbm_chains = max(self.hbm_chains, self.ctx.get_option("hbm_chains"))
 
 
 def sample_rjmcmc_batch(tiles: Sequence[ImageWMaps], rng: np.random.Generator, num_samples: int, energy_combinator,
