@@ -151,7 +151,10 @@ int mpp_synchronize(mpp_ctx *ctx);
  * of the call and of later calls stay in LDS; 1: LDS only (such a chain fails the call with -12 / -11, a context too large
  * for the LDS with -7); 2: every chain in device memory (tests, diagnosis); read-only "hbm_chains": chains that ran at
  * least one launch in device memory in the last mpp_run / mpp_replay, "hbm_bytes": the device workspace held for them;
- * -11 / -12 otherwise only remain at the limits of 2048 per cell and 65535 slots; "replicas" (before mpp_set_maps): v independent chains per tile, chain t on the maps of
+ * -11 / -12 otherwise only remain at the limits of 2048 per cell and 65535 slots; "prepass" (default 1; 0 off): a deep
+ * launch first draws the births of all its steps with a wide kernel and its chains load them (the same chain); a launch
+ * whose table would exceed "prepass_mb" (default 256, 1..16384) runs without one; read-only "prepass_used": a deep launch
+ * of the last mpp_run / mpp_replay used one; "replicas" (before mpp_set_maps): v independent chains per tile, chain t on the maps of
  * tile t % n_tiles; "remap_table" (-1 auto, default; 0 never; 1 always): chains of a model with the
  * MPP_U_SHAPE_REMAP term read the remapped mark probabilities from [H][W][32] float64 tables built once per mpp_set_maps (as
  * the reference does, energy_setup_legacy.py:142-147) instead of evaluating three sigmoids per proposal -- the same values bit

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "mpp_device.hpp"
+#include "mpp_prepass.hpp"
 
 extern "C" size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 extern "C" size_t mpp_chain_static_lds_bytes(int waves);
@@ -28,7 +29,14 @@ extern "C" size_t mpp_deep_static_lds_bytes(int waves);
 extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int grid, size_t lds, const DevParams *P,
                                       const TileRef *tiles, int tile0, const long long *until, long long trace_base,
                                       unsigned long long seed, unsigned int chain0, int trace_tile, mpp_step_out *out,
-                                      mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext);
+                                      mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext,
+                                      const PreTab *pt);
+extern "C" hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
+                                        const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
+                                        long long stride, unsigned int *cnt, unsigned long long *total);
+extern "C" hipError_t mpp_prepass_fill(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
+                                       const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
+                                       long long stride, const unsigned int *off, uint32_t *word, double *rec);
 extern "C" void mpp_launch_papangelou_tiles(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int cap,
                                             double *dE, const int32_t *grid_start, const int32_t *grid_items, int sstride, int istride);
 extern "C" void mpp_launch_grid_build_all(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int ncell,
@@ -109,6 +117,13 @@ struct mpp_ctx {
   int handover_tiles = 64;           // ... in launches of at most this many chains (64 tiles of config 4: -6 %; 256 of config 5: +4 %)
   int deep = 128, deep_fixed = 0, deep_gain = 12;   // deep_gain / 8 x the steps the last rounds committed = depth of the next (12: 4 % faster than 16 on the bench tile and on config 5's chains, 10 and 20 slower)
   unsigned long long *deep_stats = nullptr;
+  // the birth pre-pass of a deep launch (mpp_prepass.hip): prepass 1 on, 0 off (the chains draw their births themselves);
+  // a launch whose table would exceed prepass_mb MB runs without one; prepass_used: a deep launch of the last call used one
+  int prepass = 1, prepass_mb = 256, prepass_used = 0;
+  unsigned char *pre_ws = nullptr;   // the table's total, block counts and step words
+  size_t pre_ws_bytes = 0;
+  double *pre_rec = nullptr;         // its birth records
+  size_t pre_rec_bytes = 0;
   int replicas = 1, n_maps = 0;      // n_tiles = n_maps * replicas chains; chain t samples on the maps of tile t % n_maps
   int32_t *px = nullptr, *py = nullptr, *n = nullptr, *errd = nullptr;
   double *ps = nullptr, *pr = nullptr, *pa = nullptr, *T = nullptr;
@@ -254,6 +269,8 @@ extern "C" int mpp_destroy(mpp_ctx *c) {
   if (c->g_cursor) (void)hipFree(c->g_cursor);
   if (c->g_items) (void)hipFree(c->g_items);
   if (c->hbm_ws) (void)hipFree(c->hbm_ws);
+  if (c->pre_ws) (void)hipFree(c->pre_ws);
+  if (c->pre_rec) (void)hipFree(c->pre_rec);
   if (c->d_route) (void)hipFree(c->d_route);
   if (c->d_route_until) (void)hipFree(c->d_route_until);
   if (c->dp) (void)hipFree(c->dp);
@@ -331,6 +348,13 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     c->remap_mode = (int)v; c->remap_dirty = true;
   } else if (!strcmp(name, "force_accept")) {
     c->hp.force_accept = v ? 1 : 0; c->params_dirty = true;
+  } else if (!strcmp(name, "prepass")) {
+    if (v < 0 || v > 1) return fail(c, -1, "prepass must be 0 or 1");
+    c->prepass = (int)v;
+  } else if (!strcmp(name, "prepass_mb")) {
+    // (at most 16 GB: a birth's ordinal has 28 bits of its step word)
+    if (v < 1 || v > 16384) return fail(c, -1, "prepass_mb must be in 1..16384");
+    c->prepass_mb = (int)v;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -361,6 +385,9 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "chain_state")) return c->chain_state;
   if (!strcmp(name, "hbm_chains")) return c->hbm_chains;
   if (!strcmp(name, "hbm_bytes")) return (int64_t)c->hbm_ws_bytes;
+  if (!strcmp(name, "prepass")) return c->prepass;
+  if (!strcmp(name, "prepass_mb")) return c->prepass_mb;
+  if (!strcmp(name, "prepass_used")) return c->prepass_used;
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)
@@ -1057,6 +1084,46 @@ static int ensure_birth_tables(mpp_ctx *c) {
   return 0;
 }
 
+// The birth table of a deep launch (mpp_prepass.hip), on the launch's stream right before it: every chain of the launch,
+// every step it has left (at most n_steps).  pt->word stays nullptr -- the launch draws its births itself -- when the pre-pass
+// is off or the table would exceed prepass_mb.
+static int build_prepass(mpp_ctx *c, const DevParams *P, const TileRef *tiles, int tile0, int n, const long long *until,
+                         int64_t n_steps, uint64_t seed, uint32_t chain0, PreTab *pt) {
+  pt->word = nullptr; pt->rec = nullptr; pt->stride = 0;
+  if (!c->prepass || n <= 0 || n > 65535 || n_steps <= 0) return 0;       // (the chains are the grid's second dimension)
+  const long long stride = n_steps;
+  const int nblk = (int)((stride + PRE_BLOCK - 1) / PRE_BLOCK);
+  const size_t budget = (size_t)c->prepass_mb << 20;
+  const size_t cnt_off = 256, word_off = cnt_off + (((size_t)n * nblk * 4 + 255) & ~(size_t)255);
+  const size_t need = word_off + (size_t)n * stride * 4;
+  if (need > budget) return 0;
+  if (need > c->pre_ws_bytes) {
+    if (c->pre_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pre_ws); }
+    c->pre_ws = nullptr; c->pre_ws_bytes = 0;
+    HIPCHK(c, hipMalloc((void **)&c->pre_ws, need));
+    c->pre_ws_bytes = need;
+  }
+  unsigned long long *total = (unsigned long long *)c->pre_ws;
+  unsigned int *cnt = (unsigned int *)(c->pre_ws + cnt_off);
+  uint32_t *word = (uint32_t *)(c->pre_ws + word_off);
+  HIPCHK(c, mpp_prepass_count(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, total));
+  unsigned long long births = 0;
+  HIPCHK(c, hipMemcpyAsync(&births, total, sizeof births, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t rec_bytes = (size_t)births * PRE_REC_BYTES;
+  if (need + rec_bytes > budget) return 0;
+  if (rec_bytes > c->pre_rec_bytes) {
+    if (c->pre_rec) (void)hipFree(c->pre_rec);   // (the stream is idle: synchronised just above)
+    c->pre_rec = nullptr; c->pre_rec_bytes = 0;
+    HIPCHK(c, hipMalloc((void **)&c->pre_rec, rec_bytes));
+    c->pre_rec_bytes = rec_bytes;
+  }
+  HIPCHK(c, mpp_prepass_fill(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, word, c->pre_rec));
+  pt->word = word; pt->rec = c->pre_rec; pt->stride = stride;
+  c->prepass_used = 1;
+  return 0;
+}
+
 static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t seed, uint32_t chain0,
                      const mpp_proposal *d_tape, int trace_tile, mpp_step_out *d_out, mpp_proposal *d_props) {
   if (!c->have_kernels) return fail(c, -1, "mpp_set_kernels has not been called");
@@ -1101,6 +1168,7 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
   }
   c->last_ms = 0.0;
   c->hbm_chains = 0;
+  c->prepass_used = 0;
   if ((int)c->hbm_tile.size() != c->n_tiles) c->hbm_tile.assign(c->n_tiles, 0);
   // many chains in one launch: prefer the instantiation that lets two waves share a SIMD
   const int occ = (grid >= 1024) ? 2 : 1;
@@ -1210,8 +1278,10 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
       if (nmax > 0) {
         int fixed = c->deep_fixed > nmax ? nmax : c->deep_fixed;
         if (fixed > 0) { fixed = fixed / c->spec * c->spec; if (fixed < c->spec) fixed = c->spec; }
+        PreTab pt{nullptr, nullptr, 0};
+        if (!ext_ && (rc = build_prepass(c, &lp, tiles_l, tile0_l, n_lds, until_l, n_steps, seed, chain0, &pt))) return rc;
         HIPCHK(c, mpp_launch_deep(c->stream, c->spec, occ, n_lds, lds, &lp, tiles_l, tile0_l, until_l, trace_base, seed, chain0,
-                                  trace_l, d_out, d_props, nmax, fixed, c->deep_gain, c->deep_stats, has_classic(c->hp.model) ? 1 : 0));
+                                  trace_l, d_out, d_props, nmax, fixed, c->deep_gain, c->deep_stats, ext_, &pt));
       } else
       HIPCHK(c, mpp_launch_chain(c->stream, c->spec, c->lanes, occ, n_lds, lds, &lp, tiles_l, tile0_l, until_l, trace_base, seed,
                                  chain0, d_tape, trace_l, d_out, d_props));

@@ -1352,13 +1352,18 @@ __device__ __forceinline__ void draw_birth(const Chain &c, const uint32_t w[8], 
     return;
   }
 }
-template <bool LANE>
+// BIRTHS = false: the caller has the births from elsewhere (the deep kernel's pre-pass table, mpp_prepass.hip); a birth
+// step then only gets draw_head's fields, and the instantiation carries no birth draw
+template <bool LANE, bool BIRTHS = true>
 __device__ __forceinline__ void draw_proposal(const Chain &c, const uint32_t w[8], int n, Rec &r, int *keep, uint32_t k0, uint32_t k1,
                               uint64_t step, uint32_t chain, MapVals *pmv) {
   const DevParams *P = c.P;
   const int k = draw_head<LANE>(c, w, r, k0, k1, step, chain);
   *keep = 0;
-  if (k == MPP_K_UBIRTH || k == MPP_K_DBIRTH) { draw_birth<LANE>(c, w, k, r, keep, pmv); return; }
+  if (k == MPP_K_UBIRTH || k == MPP_K_DBIRTH) {
+    if constexpr (BIRTHS) draw_birth<LANE>(c, w, k, r, keep, pmv);
+    return;
+  }
   if (n == 0) return;
   r.tidx = (int)mulhi32(w[2], (uint32_t)n);
   r.tslot = c.L.order[r.tidx];
@@ -1414,6 +1419,27 @@ __device__ __forceinline__ void draw_proposal(const Chain &c, const uint32_t w[8
   r.ax = fx; r.ay = fy; r.as = q.s; r.ar = q.r; r.aa = q.a;
 }
 
+// the geometry of the rectangle a lane-form step adds (what of it the step keeps from its target comes from the target's cached values)
+__device__ __forceinline__ void deep_add_geo(const Chain &c, Rec &r, int keep) {
+  const Lds &L = c.L;
+  r.hl = r.hw = r.ca = r.sa = r.rad = 0.0;
+  if (r.has_add) {
+    Geo g;
+    g.x = r.ax; g.y = r.ay; g.hl = g.hw = g.ca = g.sa = 0.0;
+    double rad = 0.0;
+    if (keep & KEEP_SIZE) { g.hl = L.hl[r.tslot]; g.hw = L.hw[r.tslot]; rad = L.rad[r.tslot]; }
+    else {
+      double length = (2.0 * r.as) / (1.0 + r.ar), width = r.ar * length;
+      g.hl = length / 2.0; g.hw = width / 2.0;
+      rad = geo_radius(g);
+    }
+    if (keep & KEEP_TRIG) { g.ca = L.ca[r.tslot]; g.sa = L.sa[r.tslot]; }
+    else if (keep & KEEP_EDGE_ANGLE) { g.ca = L.trig[r.acls]; g.sa = L.trig[MPP_NCLASS + r.acls]; }
+    else { double al = r.aa + MPP_PI / 2.0; g.ca = cos(al); g.sa = sin(al); }
+    r.hl = g.hl; r.hw = g.hw; r.ca = g.ca; r.sa = g.sa; r.rad = rad;
+  }
+}
+
 // n-independent parts of the forward / backward proposal probabilities.  The symmetric Gaussian
 // kernels have qf == qb, which cancels in the Green ratio: their pdf is evaluated only for traces.
 __device__ __forceinline__ void proposal_densities(const Chain &c, Rec &r, bool tracing, int keep, bool coop) {
@@ -1457,6 +1483,25 @@ __device__ __forceinline__ void proposal_densities(const Chain &c, Rec &r, bool 
   }
 }
 
+// the lane form's unit terms and proposal densities of a step's added rectangle (deep rounds, mpp_deep.hip, and the birth
+// pre-pass, mpp_prepass.hip)
+// `contrast_pre`: the ContrastEnergy term of the added rectangle, computed by the whole wave beforehand (or nullptr)
+template <bool EXT>
+__device__ __forceinline__ void deep_pre(const Chain &c, Rec &r, int keep, bool tracing, const MapVals &pmv, const double *contrast_pre) {
+  const DevParams *P = c.P;
+  const Lds &L = c.L;
+  MapVals mv{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
+  if (keep & KEEP_MV) mv = pmv;
+  else if (r.has_add) mv = load_map_vals_w(P, c.h.W, c.t, L.edges, Rect{r.ax, r.ay, r.as, r.ar, r.aa});
+  proposal_densities(c, r, tracing, keep, false);
+  r.dE = 0.0; r.n_stash = 0; r.lin_a = 0.0; r.gate_a = 1; r.ra0 = r.ra1 = 0.0;
+  if (r.has_add) {
+    Rect add{r.ax, r.ay, r.as, r.ar, r.aa};
+    Geo g;
+    g.x = add.x; g.y = add.y; g.hl = r.hl; g.hw = r.hw; g.ca = r.ca; g.sa = r.sa;
+    unit_part_mv<EXT>(P, c.t, mv, add, g, &r.lin_a, &r.gate_a, nullptr, false, contrast_pre);
+  }
+}
 // base_kernels.py:55-64,100-115 ; transform_kernels.py forward/backward_probability
 __device__ __forceinline__ void green_terms(const DevParams *P, const Rec &r, int n, double intensity, double *fwd,
                                             double *bwd) {

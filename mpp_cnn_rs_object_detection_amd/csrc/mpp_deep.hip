@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "mpp_chain.hpp"
+#include "mpp_prepass.hpp"
 
 #define DEEP_NMAX_LIMIT 256      // most steps of one round (deeper rounds commit no more: the first conflict ends them)
 #define DEEP_CLIST 192         // candidate neighbours a wave collects before it evaluates them (>= 64: one cell's entries fit)
@@ -134,43 +135,6 @@ __device__ __forceinline__ void write_slot_1(const Chain &c, int slot, const Rec
 // evaluate() of mpp_chain.hpp in its lane form, in two halves around the ONE call of eval_delta_lane the kernel has (the
 // step's evaluation and, for a step that commits, the second pass that writes the neighbours' reductions go through the
 // same call site: with two, the inliner leaves a real call behind and the chain state lives in scratch memory)
-// the geometry of the rectangle a step adds (what of it the step keeps from its target comes from the target's cached values)
-__device__ __forceinline__ void deep_add_geo(const Chain &c, Rec &r, int keep) {
-  const Lds &L = c.L;
-  r.hl = r.hw = r.ca = r.sa = r.rad = 0.0;
-  if (r.has_add) {
-    Geo g;
-    g.x = r.ax; g.y = r.ay; g.hl = g.hw = g.ca = g.sa = 0.0;
-    double rad = 0.0;
-    if (keep & KEEP_SIZE) { g.hl = L.hl[r.tslot]; g.hw = L.hw[r.tslot]; rad = L.rad[r.tslot]; }
-    else {
-      double length = (2.0 * r.as) / (1.0 + r.ar), width = r.ar * length;
-      g.hl = length / 2.0; g.hw = width / 2.0;
-      rad = geo_radius(g);
-    }
-    if (keep & KEEP_TRIG) { g.ca = L.ca[r.tslot]; g.sa = L.sa[r.tslot]; }
-    else if (keep & KEEP_EDGE_ANGLE) { g.ca = L.trig[r.acls]; g.sa = L.trig[MPP_NCLASS + r.acls]; }
-    else { double al = r.aa + MPP_PI / 2.0; g.ca = cos(al); g.sa = sin(al); }
-    r.hl = g.hl; r.hw = g.hw; r.ca = g.ca; r.sa = g.sa; r.rad = rad;
-  }
-}
-// `contrast_pre`: the ContrastEnergy term of the added rectangle, computed by the whole wave beforehand (or nullptr)
-template <bool EXT>
-__device__ __forceinline__ void deep_pre(const Chain &c, Rec &r, int keep, bool tracing, const MapVals &pmv, const double *contrast_pre) {
-  const DevParams *P = c.P;
-  const Lds &L = c.L;
-  MapVals mv{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
-  if (keep & KEEP_MV) mv = pmv;
-  else if (r.has_add) mv = load_map_vals_w(P, c.h.W, c.t, L.edges, Rect{r.ax, r.ay, r.as, r.ar, r.aa});
-  proposal_densities(c, r, tracing, keep, false);
-  r.dE = 0.0; r.n_stash = 0; r.lin_a = 0.0; r.gate_a = 1; r.ra0 = r.ra1 = 0.0;
-  if (r.has_add) {
-    Rect add{r.ax, r.ay, r.as, r.ar, r.aa};
-    Geo g;
-    g.x = add.x; g.y = add.y; g.hl = r.hl; g.hw = r.hw; g.ca = r.ca; g.sa = r.sa;
-    unit_part_mv<EXT>(P, c.t, mv, add, g, &r.lin_a, &r.gate_a, nullptr, false, contrast_pre);
-  }
-}
 __device__ __forceinline__ void deep_post(const Chain &c, Rec &r, int n, double T, bool tracing) {
   double fwd, bwd;
   green_terms(c.P, r, n, c.t.intensity, &fwd, &bwd);
@@ -693,13 +657,32 @@ __device__ __forceinline__ void deep_mutate(const Chain &c, const Rec &r, int n,
 }
 __device__ __forceinline__ unsigned long long low_mask(int k) { return k <= 0 ? 0ull : (k >= 64 ? ~0ull : ((1ull << k) - 1ull)); }
 
+// a birth step's proposal, geometry and unit terms from the pre-pass table (what draw_proposal, deep_add_geo and deep_pre
+// give a birth lane; mpp_prepass.hip computes them with those functions)
+__device__ __forceinline__ void deep_load_birth(const PreTab &pt, unsigned int ord, int k, Rec &r) {
+  const double2 *q = (const double2 *)(pt.rec + (size_t)ord * PRE_REC_DOUBLES);
+  const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(q5.y);
+  r.kernel = k; r.tidx = -1; r.tslot = -1; r.has_rem = 0; r.has_add = 1; r.pid = -1; r.ncls = -1; r.acls = 0; r._pad2 = 0;
+  r.aux0 = r.aux1 = 0.0; r.rx = r.ry = 0;
+  r.u_acc = q0.x; r.qf = q0.y; r.qb = 1.0;
+  r.ax = (int)(bits & 0xffffu); r.ay = (int)((bits >> 16) & 0xffffu); r.gate_a = (int)(bits >> 32);
+  r.as = q1.x; r.ar = q1.y; r.aa = q2.x; r.lin_a = q2.y;
+  r.hl = q3.x; r.hw = q3.y; r.ca = q4.x; r.sa = q4.y; r.rad = q5.x;
+  r.dE = 0.0; r.n_stash = 0; r.ra0 = r.ra1 = 0.0;
+}
+
 // EXT: the instantiation that knows the classic image energies (mpp_classics.hpp): every lane rasterises its own rectangle
-template <int WAVES, bool DIAG, int OCC, bool EXT>
+// TAB: the births come from the pre-pass table `pt` (mpp_prepass.hip; not with EXT), and with eight waves the sorted steps
+//      are dealt by cost
+template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB>
 __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
                                                                  const long long *until, long long trace_base,
                                                                  unsigned long long seed, unsigned int chain0, int trace_tile,
                                                                  mpp_step_out *out, mpp_proposal *props, int nmax,
-                                                                 int fixed_depth, int gain8, unsigned long long *stats) {
+                                                                 int fixed_depth, int gain8, unsigned long long *stats,
+                                                                 PreTab pt) {
+  static_assert(!(TAB && EXT), "the pre-pass table is built for the instantiations without classic image energies");
   const bool by_type = (gain8 & 0x100) == 0;      // (bit 8 of the gain word: deal the sorted steps in blocks instead -- A/B tests)
   gain8 &= 0xff;
   constexpr int NCH = DEEP_NMAX_LIMIT / 64;              // chunks of 64 step reports a lane may have to look at
@@ -820,12 +803,14 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     // ---- A: kernel type of step done + e, counting sort by type over the workgroup
     int kt = 15;
     uint32_t w0[4] = {0u, 0u, 0u, 0u};
+    uint32_t pword = 0u;                        // (TAB) the step's word of the pre-pass table, requested here, used after (1)
     if (act0 && e < lim) {
       const uint64_t s = (uint64_t)(step0 + done + e);
       philox4x32_10((uint32_t)s, (uint32_t)(s >> 32), 0u, chain_t, k0, k1, w0);
       const double uk = u53(w0[0], w0[1]);
       kt = 0;
       while (kt < P->n_kernels - 1 && P->p_cum[kt] <= uk) ++kt;
+      if (TAB && (kt == MPP_K_UBIRTH || kt == MPP_K_DBIRTH)) pword = pt.word[(size_t)blockIdx.x * pt.stride + done + e];
     }
     unsigned long long same = 0ull;
     int cnt_lane = 0;                           // lane k: steps of type k in this wave
@@ -859,6 +844,8 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     const int first = __shfl(excl + pre, kt & 15, WAVE);
     if (kt != 15) {
       const int p = first + rank;
+      // (TAB: a birth reads none of its words past the type: word 2 carries its ordinal in the table instead)
+      if (TAB && (kt == MPP_K_UBIRTH || kt == MPP_K_DBIRTH)) w0[2] = pword >> 4;
       D.pw[p] = make_uint4(w0[0], w0[1], w0[2], w0[3]);
       D.poff[p] = (unsigned short)e;
     }
@@ -870,7 +857,33 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     //      otherwise -- or should a type have more than 64 steps -- the sorted steps are dealt to the waves in blocks.
     int es = e;
     mine = act0 && e < lim;
-    if (WAVES == 8 && by_type && !EXT) {           // (EXT: the contrast terms are evaluated one rectangle at a time per wave -- equal shares)
+    if (TAB && WAVES == 8 && by_type) {
+      // by cost (profiles/prepass.md; cycles of a round's wave before barrier (3)).  With the births' draw in the table, the
+      // data-driven transform is the slowest kernel by far -- its draw and its neighbour pass: its steps go to two waves,
+      // split in sorted order; the two uniform kernels share a wave; every other kernel keeps a wave of its own.  Waves w
+      // and w + 4 share a SIMD: each of the two transform halves shares it with a light wave (the data-driven birth,
+      // the uniform pair), wave 0 -- it extends the temperature ring -- gets the lightest.
+      int t_[MPP_NKERNEL];
+#pragma unroll
+      for (int k = 0; k < MPP_NKERNEL; ++k) t_[k] = __builtin_amdgcn_readlane(tot, k);
+      // sorted segments: [0, b1) uniform birth + death, [b1, b2) data-driven birth, [b2, b3) data-driven death,
+      // [b3, b4) Gaussian translation, [b4, b5) and [b5, b6) the data-driven translation, [b6, b7) Gaussian transform,
+      // [b7, b8) data-driven transform
+      const int b1 = t_[MPP_K_UBIRTH] + t_[MPP_K_UDEATH], b2 = b1 + t_[MPP_K_DBIRTH], b3 = b2 + t_[MPP_K_DDEATH];
+      const int b4 = b3 + t_[MPP_K_GTRANS], b5 = b4 + (t_[MPP_K_DTRANS] + 1) / 2, b6 = b4 + t_[MPP_K_DTRANS];
+      const int b7 = b6 + t_[MPP_K_GTRANSF], b8 = b7 + t_[MPP_K_DTRANSF];
+      const bool fits = b8 == lim && b1 <= WAVE && b2 - b1 <= WAVE && b3 - b2 <= WAVE && b4 - b3 <= WAVE && b5 - b4 <= WAVE &&
+                        b6 - b5 <= WAVE && b7 - b6 <= WAVE && b8 - b7 <= WAVE;
+      if (fits) {
+        // wave:     0   1   2   3   4   5   6   7
+        // segment: b1  0   b2  b3  b4  b5  b7  b6   (its first position)
+        const int w = c.wave;
+        const int lo = w == 0 ? b1 : w == 1 ? 0 : w == 2 ? b2 : w == 3 ? b3 : w == 4 ? b4 : w == 5 ? b5 : w == 6 ? b7 : b6;
+        const int hi = w == 0 ? b2 : w == 1 ? b1 : w == 2 ? b3 : w == 3 ? b4 : w == 4 ? b5 : w == 5 ? b6 : w == 6 ? b8 : b7;
+        mine = c.lane < hi - lo;
+        es = lo + c.lane;
+      }
+    } else if (WAVES == 8 && by_type && !EXT) {           // (EXT: the contrast terms are evaluated one rectangle at a time per wave -- equal shares)
       bool fits = true;
 #pragma unroll
       for (int k = 0; k < MPP_NKERNEL; ++k) {
@@ -896,12 +909,22 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       const uint4 wv = D.pw[es];
       w[0] = wv.x; w[1] = wv.y; w[2] = wv.z; w[3] = wv.w;
       const uint64_t s = (uint64_t)(step0 + done + myoff);
-      philox4x32_10((uint32_t)s, (uint32_t)(s >> 32), 1u, chain_t, k0, k1, w + 4);
-      draw_proposal<true>(c, w, n, r, &keep, k0, k1, s, chain_t, &pmv);
+      bool pre_b = false;                      // (TAB) a birth: the table has it all
+      if (TAB) {
+        const double uk = u53(w[0], w[1]);
+        int k = 0;
+        while (k < P->n_kernels - 1 && P->p_cum[k] <= uk) ++k;
+        pre_b = k == MPP_K_UBIRTH || k == MPP_K_DBIRTH;
+        if (pre_b) deep_load_birth(pt, w[2], k, r);
+      }
+      if (!pre_b) {
+        philox4x32_10((uint32_t)s, (uint32_t)(s >> 32), 1u, chain_t, k0, k1, w + 4);
+        draw_proposal<true, !TAB>(c, w, n, r, &keep, k0, k1, s, chain_t, &pmv);
+      }
       DPH(3);
       if (r.kernel >= MPP_K_SPLIT) { r.valid = 0; r.kernel = -1; }
       if (r.valid && r.has_add && (r.ax < 0 || r.ax >= c.h.H || r.ay < 0 || r.ay >= c.h.W)) { r.valid = 0; r.kernel = -1; }
-      if (r.valid) {
+      if (r.valid && !pre_b) {
         deep_add_geo(c, r, keep);
         if (!EXT) deep_pre<EXT>(c, r, keep, tracing, pmv, nullptr);
       }
@@ -1199,33 +1222,36 @@ extern "C" size_t mpp_deep_static_lds_bytes(int waves) {
   return waves >= MPP_LDS_PARAMS_MIN_WAVES ? ((sizeof(DevParams) + 15) & ~(size_t)15) : 0;
 }
 
-template <int WAVES, bool DIAG, int OCC, bool EXT>
+template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB>
 static hipError_t launch_deep_d(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
                                 const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
                                 int trace_tile, mpp_step_out *out, mpp_proposal *props, int nmax, int fixed_depth, int gain8,
-                                unsigned long long *stats) {
-  hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT>,
+                                unsigned long long *stats, const PreTab &pt) {
+  hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
-                     trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats);
+  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
+                     trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, pt);
   return hipGetLastError();
 }
 
 // waves = waves per chain (1, 2, 4, 8); nmax = most steps of one round (a power of two, waves <= nmax <= 64 * waves, <= 256);
 // ext: a classic image energy among the unit terms (built for 1 and 8 waves, like the one-wave-per-step kernels)
+// pt: the launch's birth table (mpp_prepass.hip), or pt->word == nullptr: the chains draw their births themselves
 extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int grid, size_t lds, const DevParams *P,
                                       const TileRef *tiles, int tile0, const long long *until, long long trace_base,
                                       unsigned long long seed, unsigned int chain0, int trace_tile, mpp_step_out *out,
-                                      mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext) {
-  const bool diag = out || props;
-#define GO(W, O, X)                                                                                                       \
-  return diag ? launch_deep_d<W, true, O, X>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats) \
-              : launch_deep_d<W, false, O, X>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats)
+                                      mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext,
+                                      const PreTab *pt) {
+  const bool diag = out || props, tab = pt->word != nullptr && !ext;
+#define GO_(W, O, X, T)                                                                                                   \
+  return diag ? launch_deep_d<W, true, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt) \
+              : launch_deep_d<W, false, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
+#define GO(W, O, X) do { if (!(X) && tab) { GO_(W, O, false, true); } GO_(W, O, X, false); } while (0)
   if (ext) {
     switch (waves) {
-      case 1: GO(1, 1, true);
-      case 8: GO(8, 2, true);
+      case 1: GO_(1, 1, true, false);
+      case 8: GO_(8, 2, true, false);
     }
     return hipErrorNotSupported;
   }
@@ -1236,5 +1262,6 @@ extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int gr
     case 8: GO(8, 2, false);
   }
 #undef GO
+#undef GO_
   return hipErrorInvalidValue;
 }

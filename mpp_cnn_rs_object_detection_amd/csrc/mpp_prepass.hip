@@ -1,0 +1,141 @@
+// mpp_prepass.hip -- the birth pre-pass of a deep launch (table layout: mpp_prepass.hpp).
+//
+// Three kernels on the launch's stream, one thread per step of every chain of the launch:
+//   count  kernel type of each step (Philox block 0), births per block of PRE_BLOCK steps;
+//   scan   the births' ordinals: exclusive prefix of the block counts over all chains (one workgroup);
+//   fill   per step its word (type | ordinal), per birth its record: draw_head / draw_birth (lane forms), deep_add_geo and
+//          deep_pre -- the very functions the deep kernel ran for a birth lane, so the record holds its bits.
+// The host reads the number of births back between scan and fill (the records' size; a table over the prepass_mb budget
+// is not built and the launch draws its births itself).
+#include "mpp_chain.hpp"
+#include "mpp_prepass.hpp"
+
+// the Philox key of chain `tile`, formed as the chain kernels form it (mpp_deep.hip, mpp_chain_body.inc)
+__device__ __forceinline__ void pre_key(const TileRef &t, unsigned long long seed, uint32_t chain0, int tile, uint32_t *k0,
+                                        uint32_t *k1, uint32_t *chain) {
+  const unsigned long long seed_t = t.key_on ? (unsigned long long)t.key_seed : seed;
+  *chain = t.key_on ? t.key_chain : chain0 + (uint32_t)tile;
+  *k0 = (uint32_t)seed_t; *k1 = (uint32_t)(seed_t >> 32);
+}
+__device__ __forceinline__ int pre_type(const DevParams *P, uint32_t a, uint32_t b) {
+  const double uk = u53(a, b);
+  int kt = 0;
+  while (kt < P->n_kernels - 1 && P->p_cum[kt] <= uk) ++kt;
+  return kt;
+}
+__device__ __forceinline__ bool is_birth(int kt) { return kt == MPP_K_UBIRTH || kt == MPP_K_DBIRTH; }
+
+// grid (blocks of steps, chains)
+__global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_count_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
+                                                                      const long long *until, unsigned long long seed,
+                                                                      unsigned int chain0, int nblk, long long stride,
+                                                                      unsigned int *cnt) {
+  const int ch = blockIdx.y, tile = tile0 + ch;
+  const TileRef t = tiles[tile];
+  const long long rel = (long long)blockIdx.x * PRE_BLOCK + threadIdx.x, s = *t.step + rel;
+  bool birth = false;
+  if (s < until[tile] && rel < stride) {
+    uint32_t k0, k1, chain, w[4];
+    pre_key(t, seed, chain0, tile, &k0, &k1, &chain);
+    philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 0u, chain, k0, k1, w);
+    birth = is_birth(pre_type(&Pv, w[0], w[1]));
+  }
+  const int c = __syncthreads_count(birth);
+  if (threadIdx.x == 0) cnt[(size_t)ch * nblk + blockIdx.x] = (unsigned int)c;
+}
+
+// in place: cnt[i] <- sum of cnt[0 .. i-1]; *total <- sum of all
+__global__ __launch_bounds__(1024) void mpp_prepass_scan_kernel(unsigned int *cnt, long long n, unsigned long long *total) {
+  __shared__ unsigned long long part[1024];
+  const int tid = threadIdx.x;
+  unsigned long long carry = 0;
+  for (long long i0 = 0; i0 < n; i0 += 1024) {
+    const long long i = i0 + tid;
+    const unsigned long long v = i < n ? cnt[i] : 0u;
+    part[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const unsigned long long x = tid >= off ? part[tid - off] : 0ull;
+      __syncthreads();
+      part[tid] += x;
+      __syncthreads();
+    }
+    if (i < n) cnt[i] = (unsigned int)(carry + part[tid] - v);
+    carry += part[1023];
+    __syncthreads();
+  }
+  if (tid == 0) *total = carry;
+}
+
+// grid (blocks of steps, chains); off: the scanned block counts
+__global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
+                                                                     const long long *until, unsigned long long seed,
+                                                                     unsigned int chain0, int nblk, long long stride,
+                                                                     const unsigned int *off, uint32_t *word, double *rec) {
+  __shared__ double s_edges[3 * MPP_NCLASS];
+  __shared__ unsigned int s_wcnt[PRE_BLOCK / WAVE];
+  const DevParams *P = &Pv;
+  const int ch = blockIdx.y, tile = tile0 + ch, tid = threadIdx.x;
+  for (int i = tid; i < 3 * MPP_NCLASS; i += PRE_BLOCK) s_edges[i] = P->maps.edges[i / MPP_NCLASS][i % MPP_NCLASS];
+  Chain c;
+  c.P = P; c.t = tiles[tile];
+  load_hot(c);
+  c.L = Lds{};
+  c.L.edges = s_edges;          // (what the chain copies to LDS; the birth CDF's row level is read from the tile: same values)
+  c.L.rowbase = nullptr;
+  c.lane = tid & (WAVE - 1);
+  c.wave = tid / WAVE;
+  const long long s0 = *c.t.step, rel = (long long)blockIdx.x * PRE_BLOCK + tid, s = s0 + rel;
+  const bool in = s < until[tile] && rel < stride;
+  uint32_t k0, k1, chain, w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  pre_key(c.t, seed, chain0, tile, &k0, &k1, &chain);
+  int kt = 15;
+  if (in) {
+    philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 0u, chain, k0, k1, w);
+    kt = pre_type(P, w[0], w[1]);
+  }
+  const bool birth = in && is_birth(kt);
+  // the births' ordinals in step order: the block's base, then the waves before mine, then the lanes before mine
+  const unsigned long long m = __ballot(birth);
+  if (c.lane == 0) s_wcnt[c.wave] = (unsigned int)__popcll(m);
+  __syncthreads();
+  unsigned int ord = off[(size_t)ch * nblk + blockIdx.x] + (unsigned int)__popcll(m & ((1ull << c.lane) - 1ull));
+  for (int v = 0; v < c.wave; ++v) ord += s_wcnt[v];
+  if (in) word[(size_t)ch * stride + rel] = (uint32_t)kt | (birth ? ord << 4 : 0u);
+  if (!birth) return;
+  philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 1u, chain, k0, k1, w + 4);
+  Rec r;
+  r.valid = 1; r.accepted = 0; r._pad = 0; r.n_stash = 0; r.gate_a = 1;
+  const int k = draw_head<true>(c, w, r, k0, k1, (uint64_t)s, chain);
+  int keep = 0;
+  MapVals pmv{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
+  draw_birth<true>(c, w, k, r, &keep, &pmv);
+  deep_add_geo(c, r, keep);
+  deep_pre<false>(c, r, keep, false, pmv, nullptr);
+  double2 *o = (double2 *)(rec + (size_t)ord * PRE_REC_DOUBLES);
+  const unsigned long long bits = (unsigned long long)((unsigned int)(r.ax & 0xffff) | ((unsigned int)r.ay << 16)) |
+                                  ((unsigned long long)(unsigned int)r.gate_a << 32);
+  o[0] = make_double2(r.u_acc, r.qf);
+  o[1] = make_double2(r.as, r.ar);
+  o[2] = make_double2(r.aa, r.lin_a);
+  o[3] = make_double2(r.hl, r.hw);
+  o[4] = make_double2(r.ca, r.sa);
+  o[5] = make_double2(r.rad, __longlong_as_double((long long)bits));
+}
+
+// ---- host-side launchers ----------------------------------------------------------------------------
+extern "C" hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
+                                        const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
+                                        long long stride, unsigned int *cnt, unsigned long long *total) {
+  hipLaunchKernelGGL(mpp_prepass_count_kernel, dim3(nblk, n_chains), dim3(PRE_BLOCK), 0, st, *P, tiles, tile0, until, seed,
+                     chain0, nblk, stride, cnt);
+  hipLaunchKernelGGL(mpp_prepass_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (long long)nblk * n_chains, total);
+  return hipGetLastError();
+}
+extern "C" hipError_t mpp_prepass_fill(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
+                                       const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
+                                       long long stride, const unsigned int *off, uint32_t *word, double *rec) {
+  hipLaunchKernelGGL(mpp_prepass_fill_kernel, dim3(nblk, n_chains), dim3(PRE_BLOCK), 0, st, *P, tiles, tile0, until, seed,
+                     chain0, nblk, stride, off, word, rec);
+  return hipGetLastError();
+}

@@ -1,6 +1,7 @@
 #!/bin/bash
-# registers / scratch of every instantiation of the chain kernel in a built object:
-#   bash profiles/tools/kernel_regs.sh [path/to/mpp_sampler.o]
+# registers / scratch of every instantiation of the chain kernels in a built object:
+#   bash profiles/tools/kernel_regs.sh [path/to/mpp_sampler.o | path/to/mpp_deep.o]
+# mpp_chain_kernel: WAVES,LPW,DIAG,OCC,SM,FAST; mpp_deep_kernel: WAVES,DIAG,OCC,EXT[,TAB]
 obj=${1:-mpp_cnn_rs_object_detection_amd/csrc/mpp_sampler.o}
 tmp=$(mktemp -d)
 B=/opt/rocm/lib/llvm/bin
@@ -11,9 +12,17 @@ import re, sys
 txt = sys.stdin.read()
 for blk in re.split(r"\n\s+- \.agpr_count", txt)[1:]:
     name = re.search(r"\.name:\s+(\S+)", blk)
-    if not name or "mpp_chain_kernel" not in name.group(1): continue
+    if not name: continue
+    n = name.group(1)
     g = lambda k: re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)
-    targs = re.search(r"ILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)E", name.group(1))
-    print("WAVES,LPW,DIAG,OCC,SM,FAST =", ",".join(targs.groups()) if targs else name.group(1), " vgpr", g("vgpr_count"), "spill", g("vgpr_spill_count"), "sgpr", g("sgpr_count"), "scratch", g("private_segment_fixed_size"))
+    if "mpp_chain_kernel" in n:
+        targs = re.search(r"ILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)E", n)
+        label = "WAVES,LPW,DIAG,OCC,SM,FAST = " + (",".join(targs.groups()) if targs else n)
+    elif "mpp_deep_kernel" in n:
+        targs = re.search(r"ILi(\d+)ELb(\d)ELi(\d+)ELb(\d)E(?:Lb(\d)E)?", n)
+        label = "deep WAVES,DIAG,OCC,EXT,TAB = " + (",".join(v for v in targs.groups() if v is not None) if targs else n)
+    else:
+        continue
+    print(label, " vgpr", g("vgpr_count"), "spill", g("vgpr_spill_count"), "sgpr", g("sgpr_count"), "sgpr_spill", g("sgpr_spill_count"), "scratch", g("private_segment_fixed_size"))
 ' | sort
 rm -rf $tmp
