@@ -300,6 +300,23 @@ int mpp_conv3x3_stem(mpp_ctx *ctx, const float *x, int H, int W, const float *wp
 int mpp_shapenet_heads(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b,
                        float *marks_size, float *marks_ratio, float *marks_angle);
 
+/* Window forms of the five epilogues above, for a forward that walks a large image in crops: the crop's network output
+ * as above, its extent H x W (which decides where the divergence is one-sided, exactly as in the full-crop call), and a
+ * window of wh x ww pixels at (wx0, wy0) in crop coordinates.  Only the window's pixels are computed; det / marks point to
+ * the window's first pixel in a larger map whose rows are ld_det / ld_marks pixels apart (marks: 32 floats per pixel).
+ * Per pixel the result is bit for bit the full-crop call's; nothing outside the window is written.  A window outside the
+ * crop or a pitch smaller than ww: -1 and a message. */
+int mpp_posnet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
+                            int wx0, int wy0, int wh, int ww, float *det, int ld_det);
+int mpp_shapenet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0, int wh, int ww,
+                              float *marks, int ld_marks);
+int mpp_posnet_epilogue_nhwc_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
+                                 double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det);
+int mpp_shapenet_epilogue_nhwc_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, int wx0, int wy0,
+                                   int wh, int ww, float *marks, int ld_marks);
+int mpp_shapenet_heads_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b, int wx0, int wy0,
+                           int wh, int ww, float *marks_size, float *marks_ratio, float *marks_angle, int ld_marks);
+
 /* IoU matrix of convex quadrilaterals for the DOTA task-1 evaluation: a [n][8], b [m][8] (x1 y1 .. x4 y4, either
  * orientation) -> out [n][m] = |A_i n B_j| / (|A_i| + |B_j| - |A_i n B_j|), or -1 where the axis-aligned extents
  * (inclusive-pixel +1 convention) do not overlap.  Stands in for `polyiou.iou_poly` and the hbb pre-filter of

@@ -87,6 +87,16 @@ extern "C" void mpp_launch_posnet_epilogue(hipStream_t st, const float *out, int
                                            float b, float *det);
 extern "C" void mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits, int H, int W, int ldh, int ldw,
                                              float *marks);
+extern "C" void mpp_launch_posnet_epilogue_win(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b,
+                                               int wx0, int wy0, int wh, int ww, float *dst, int ld_dst);
+extern "C" int mpp_launch_shapenet_epilogue_win(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
+                                                float *dst, int ld_dst);
+extern "C" int mpp_launch_posnet_epilogue_nhwc_win(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w,
+                                                   float b, int wx0, int wy0, int wh, int ww, float *dst, int ld_dst);
+extern "C" int mpp_launch_shapenet_epilogue_nhwc_win(hipStream_t st, const void *logits, int elem_bytes, int ldw, int wx0, int wy0,
+                                                     int wh, int ww, float *dst, int ld_dst);
+extern "C" int mpp_launch_shapenet_heads_win(hipStream_t st, const float *h, int ldw, const float *wh, const float *bh, int wx0, int wy0,
+                                             int wh_, int ww, float *m0, float *m1, float *m2, int ld_dst);
 
 #define MPP_LDS_LIMIT (160 * 1024)
 #define MPP_CELL_CAP_MAX 2048    // entries of a 32-px cell of the spatial hash (16-bit counts); what fits the LDS decides
@@ -1534,5 +1544,66 @@ extern "C" int mpp_shapenet_epilogue(mpp_ctx *c, int H, int W, int ldh, int ldw,
   HIPCHK(c, hipSetDevice(c->device));
   mpp_launch_shapenet_epilogue(c->stream, logits, H, W, ldh, ldw, marks);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// ---- window forms of the epilogues: the window (wx0, wy0, wh x ww) of an H x W crop into a full-image map -------------------
+static int bad_window(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, int wx0, int wy0, int wh, int ww, int ld_dst) {
+  if (H <= 0 || W <= 0 || ldh < H || ldw < W) return fail(c, -1, "%s: bad crop extent", what);
+  if (wx0 < 0 || wy0 < 0 || wh <= 0 || ww <= 0 || wx0 > H - wh || wy0 > W - ww)
+    return fail(c, -1, "%s: window (%d, %d, %d x %d) outside the %d x %d crop", what, wx0, wy0, wh, ww, H, W);
+  if (ld_dst < ww) return fail(c, -1, "%s: destination pitch %d smaller than the window width %d", what, ld_dst, ww);
+  return 0;
+}
+extern "C" int mpp_posnet_epilogue_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
+                                       int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
+  if (!c || !pos_out || !det) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "posnet_epilogue_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_det)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  mpp_launch_posnet_epilogue_win(c->stream, pos_out, H, W, ldh, ldw, (float)div_w, (float)div_b, wx0, wy0, wh, ww, det, ld_det);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+extern "C" int mpp_shapenet_epilogue_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0, int wh, int ww,
+                                         float *marks, int ld_marks) {
+  if (!c || !logits || !marks) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "shapenet_epilogue_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (mpp_launch_shapenet_epilogue_win(c->stream, logits, ldh, ldw, wx0, wy0, wh, ww, marks, ld_marks))
+    return fail(c, -1, "shapenet_epilogue_win: marks must be 16-byte aligned");
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+extern "C" int mpp_posnet_epilogue_nhwc_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
+                                            double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
+  if (!c || !pos_out || !det) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "posnet_epilogue_nhwc_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_det)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (mpp_launch_posnet_epilogue_nhwc_win(c->stream, pos_out, elem_bytes, H, W, ldw, (float)div_w, (float)div_b, wx0, wy0, wh, ww, det,
+                                          ld_det))
+    return fail(c, -1, "posnet_epilogue_nhwc_win: element type must be float32 or bfloat16");
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+extern "C" int mpp_shapenet_epilogue_nhwc_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, int wx0,
+                                              int wy0, int wh, int ww, float *marks, int ld_marks) {
+  if (!c || !logits || !marks) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "shapenet_epilogue_nhwc_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int e = mpp_launch_shapenet_epilogue_nhwc_win(c->stream, logits, elem_bytes, ldw, wx0, wy0, wh, ww, marks, ld_marks);
+  if (e == -1) return fail(c, -1, "shapenet_epilogue_nhwc_win: element type must be float32 or bfloat16");
+  if (e == -2) return fail(c, -1, "shapenet_epilogue_nhwc_win: logits and marks must be 16-byte aligned");
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+extern "C" int mpp_shapenet_heads_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b, int wx0,
+                                      int wy0, int wh, int ww, float *marks_size, float *marks_ratio, float *marks_angle, int ld_marks) {
+  if (!c || !h || !w || !b || !marks_size || !marks_ratio || !marks_angle) return fail(c, -1, "bad shapenet_heads arguments");
+  if (bad_window(c, "shapenet_heads_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = mpp_launch_shapenet_heads_win(c->stream, h, ldw, w, b, wx0, wy0, wh, ww, marks_size, marks_ratio, marks_angle, ld_marks);
+  if (rc == -2 && (((uintptr_t)h | (uintptr_t)marks_size | (uintptr_t)marks_ratio | (uintptr_t)marks_angle) & 15))
+    return fail(c, -1, "shapenet_heads_win: the activations and the mark maps must be 16-byte aligned");
+  if (rc) return fail(c, -2, "shapenet_heads_win launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }

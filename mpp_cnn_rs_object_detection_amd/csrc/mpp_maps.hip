@@ -231,6 +231,88 @@ extern "C" void mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits
                      marks, vec_ok);
 }
 
+// ---- window forms of the two epilogues (the tiled forward: unet.py, chunk_plan) ----------------------------------------
+// A crop's epilogue restricted to the window (wx0, wy0, wh x ww) of its H x W extent: H x W still decides where the
+// differences are one-sided; the window's pixels go to dst (the window's first pixel in a full-image map) with a row pitch
+// of ld_dst pixels.  Per pixel the arithmetic, in its order, of the full-crop kernel above (the build forms no FMA:
+// -ffp-contract=off), so a window is the full-crop map restricted to it bit for bit; nothing outside it is written.
+__global__ __launch_bounds__(256) void k_posnet_epilogue_win(const float *out, int H, int W, int ldh, int ldw, float w, float b,
+                                                             int wx0, int wy0, int wh, int ww, float *dst, int ld_dst, int vec_ok) {
+  const int j4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, r = blockIdx.y;
+  if (j4 >= ww || r >= wh) return;
+  const int x = wx0 + r, y4 = wy0 + j4;
+  const size_t plane = (size_t)ldh * ldw;
+  const float *v0 = out, *v1 = out + plane, *mk = out + 2 * plane;
+  float *drow = dst + (size_t)r * ld_dst;
+  if (vec_ok && x > 0 && x < H - 1 && y4 > 0 && y4 + 4 < W && j4 + 4 <= ww) {
+    const float4 up = *(const float4 *)(v0 + (size_t)(x - 1) * ldw + y4), dn = *(const float4 *)(v0 + (size_t)(x + 1) * ldw + y4);
+    const float4 c = *(const float4 *)(v1 + (size_t)x * ldw + y4), m4 = *(const float4 *)(mk + (size_t)x * ldw + y4);
+    const float left = v1[(size_t)x * ldw + y4 - 1], right = v1[(size_t)x * ldw + y4 + 4];
+    const float g0[4] = {(dn.x - up.x) / 2.0f, (dn.y - up.y) / 2.0f, (dn.z - up.z) / 2.0f, (dn.w - up.w) / 2.0f};
+    const float g1[4] = {(c.y - left) / 2.0f, (c.z - c.x) / 2.0f, (c.w - c.y) / 2.0f, (right - c.z) / 2.0f};
+    const float mm[4] = {m4.x, m4.y, m4.z, m4.w};
+    float res[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float mask = 1.0f / (1.0f + expf(-mm[i]));
+      float score = w * ((g0[i] + g1[i]) * mask) + b;
+      res[i] = 1.0f / (1.0f + expf(-score));
+    }
+    *(float4 *)(drow + j4) = make_float4(res[0], res[1], res[2], res[3]);
+  } else {
+    for (int j = j4; j < min(j4 + 4, ww); ++j) drow[j] = posnet_pixel(v0, v1, mk, x, wy0 + j, H, W, ldw, w, b);
+  }
+}
+extern "C" void mpp_launch_posnet_epilogue_win(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b,
+                                               int wx0, int wy0, int wh, int ww, float *dst, int ld_dst) {
+  // (a det window can start at any pixel: float4 stores only where the destination rows are 16-byte aligned)
+  int vec_ok = (ldw % 4 == 0) && (wy0 % 4 == 0) && (ld_dst % 4 == 0) && (((uintptr_t)out & 15) == 0) &&
+               (((uintptr_t)dst & 15) == 0) && (((size_t)ldh * ldw) % 4 == 0);
+  hipLaunchKernelGGL(k_posnet_epilogue_win, dim3((ww + 1023) / 1024, wh), dim3(256), 0, st, out, H, W, ldh, ldw, w, b, wx0, wy0,
+                     wh, ww, dst, ld_dst, vec_ok);
+}
+__global__ __launch_bounds__(256) void k_shapenet_epilogue_win(const float *logits, int ldh, int ldw, int wx0, int wy0, int ww,
+                                                               float *dst, int ld_dst, int vec_ok) {
+  __shared__ float tile[MPP_NCLASS][WAVE + 1];
+  const int r = blockIdx.y, j0 = blockIdx.x * WAVE, x = wx0 + r, y0 = wy0 + j0;
+  const size_t plane = (size_t)ldh * ldw;
+  if (vec_ok && j0 + WAVE <= ww) {
+    const int px4 = (threadIdx.x & 15) * 4, ch0 = threadIdx.x >> 4;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int ch = ch0 + 16 * h;
+      const float4 v = *(const float4 *)(logits + ch * plane + (size_t)x * ldw + y0 + px4);
+      tile[ch][px4] = v.x; tile[ch][px4 + 1] = v.y; tile[ch][px4 + 2] = v.z; tile[ch][px4 + 3] = v.w;
+    }
+  } else {
+    const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    for (int ch = grp; ch < MPP_NCLASS; ch += 4) tile[ch][lane] = j0 + lane < ww ? logits[ch * plane + (size_t)x * ldw + y0 + lane] : 0.f;
+  }
+  __syncthreads();
+  const int p = threadIdx.x >> 2, q = threadIdx.x & 3;
+  float v[8], m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { v[i] = tile[q * 8 + i][p]; m = fmaxf(m, v[i]); }
+  m = fmaxf(m, __shfl_xor(m, 1, WAVE)); m = fmaxf(m, __shfl_xor(m, 2, WAVE));
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { v[i] = expf(v[i] - m); s += v[i]; }
+  s += __shfl_xor(s, 1, WAVE); s += __shfl_xor(s, 2, WAVE);
+  if (j0 + p < ww) {
+    float4 *d = (float4 *)(dst + ((size_t)r * ld_dst + j0 + p) * MPP_NCLASS + q * 8);
+    d[0] = make_float4(v[0] / s, v[1] / s, v[2] / s, v[3] / s);
+    d[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
+  }
+}
+extern "C" int mpp_launch_shapenet_epilogue_win(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
+                                                float *dst, int ld_dst) {
+  if ((uintptr_t)dst & 15) return -2;                  // (a pixel's 32 classes are 128 bytes: every window row is aligned)
+  int vec_ok = (ldw % 4 == 0) && (wy0 % 4 == 0) && (((uintptr_t)logits & 15) == 0) && (((size_t)ldh * ldw) % 4 == 0);
+  hipLaunchKernelGGL(k_shapenet_epilogue_win, dim3((ww + WAVE - 1) / WAVE, wh), dim3(256), 0, st, logits, ldh, ldw, wx0, wy0, ww,
+                     dst, ld_dst, vec_ok);
+  return 0;
+}
+
 // ---- conv epilogue of the U-Nets' DoubleConv blocks ----------------------------------------------------------
 // y = max(0, x * scale[c] + shift[c]) in place on a [planes][hw] tensor (plane p belongs to channel p % C):
 // BatchNorm(eval) folded with the convolution bias, plus the ReLU, in ONE pass over the activation instead of the
@@ -488,6 +570,81 @@ extern "C" int mpp_launch_shapenet_epilogue_nhwc(hipStream_t st, const void *log
   const unsigned grid = (unsigned)((threads + 255) / 256);
   if (elem_bytes == 4) hipLaunchKernelGGL(k_shapenet_epilogue_nhwc<4>, dim3(grid), dim3(256), 0, st, logits, H, W, ldw, marks);
   else if (elem_bytes == 2) hipLaunchKernelGGL(k_shapenet_epilogue_nhwc<2>, dim3(grid), dim3(256), 0, st, logits, H, W, ldw, marks);
+  else return -1;
+  return 0;
+}
+
+// window forms (see k_posnet_epilogue_win): the window (wx0, wy0, wh x ww) of the H x W crop into dst, row pitch ld_dst pixels
+template <int EB>
+__global__ __launch_bounds__(256) void k_posnet_epilogue_nhwc_win(const void *out, int H, int W, int ldw, float w, float b, int wx0,
+                                                                  int wy0, int wh, int ww, float *dst, int ld_dst) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+  if (j >= ww || r >= wh) return;
+  const int x = wx0 + r, y = wy0 + j;
+  auto at = [&](int i, int jj, int ch) -> float { return ld_elem<EB>(out, ((size_t)i * ldw + jj) * 3 + ch); };
+  float g0, g1;
+  if (H == 1) g0 = 0.f;
+  else if (x == 0) g0 = at(1, y, 0) - at(0, y, 0);
+  else if (x == H - 1) g0 = at(x, y, 0) - at(x - 1, y, 0);
+  else g0 = (at(x + 1, y, 0) - at(x - 1, y, 0)) / 2.0f;
+  if (W == 1) g1 = 0.f;
+  else if (y == 0) g1 = at(x, 1, 1) - at(x, 0, 1);
+  else if (y == W - 1) g1 = at(x, y, 1) - at(x, y - 1, 1);
+  else g1 = (at(x, y + 1, 1) - at(x, y - 1, 1)) / 2.0f;
+  float mask = 1.0f / (1.0f + expf(-at(x, y, 2)));
+  float score = w * ((g0 + g1) * mask) + b;
+  dst[(size_t)r * ld_dst + j] = 1.0f / (1.0f + expf(-score));
+}
+template <int EB>
+__global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc_win(const void *logits, int ldw, int wx0, int wy0, int wh, int ww,
+                                                                    float *dst, int ld_dst) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t pix = t >> 2;
+  const int q = (int)(t & 3);
+  const bool live = pix < (size_t)wh * ww;         // the 4 lanes of a pixel are live together; dead lanes still shuffle
+  const int r = live ? (int)(pix / (size_t)ww) : 0, j = live ? (int)(pix % (size_t)ww) : 0;
+  const size_t src = ((size_t)(wx0 + r) * ldw + wy0 + j) * MPP_NCLASS + q * 8;
+  float v[8], m = -INFINITY;
+  if (EB == 4) {
+    const float4 a = *(const float4 *)((const float *)logits + src), c = *(const float4 *)((const float *)logits + src + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+  } else {
+    const uint4 a = *(const uint4 *)((const unsigned short *)logits + src);
+    const unsigned int wd[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[2 * k] = bf16_to_f32((unsigned short)(wd[k] & 0xffffu)); v[2 * k + 1] = bf16_to_f32((unsigned short)(wd[k] >> 16)); }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m = fmaxf(m, v[i]);
+  m = fmaxf(m, __shfl_xor(m, 1, WAVE)); m = fmaxf(m, __shfl_xor(m, 2, WAVE));
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { v[i] = expf(v[i] - m); s += v[i]; }
+  s += __shfl_xor(s, 1, WAVE); s += __shfl_xor(s, 2, WAVE);
+  if (live) {
+    float4 *d = (float4 *)(dst + ((size_t)r * ld_dst + j) * MPP_NCLASS + q * 8);
+    d[0] = make_float4(v[0] / s, v[1] / s, v[2] / s, v[3] / s);
+    d[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
+  }
+}
+extern "C" int mpp_launch_posnet_epilogue_nhwc_win(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w,
+                                                   float b, int wx0, int wy0, int wh, int ww, float *dst, int ld_dst) {
+  const dim3 grid((ww + 255) / 256, wh);
+  if (elem_bytes == 4)
+    hipLaunchKernelGGL(k_posnet_epilogue_nhwc_win<4>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, wx0, wy0, wh, ww, dst, ld_dst);
+  else if (elem_bytes == 2)
+    hipLaunchKernelGGL(k_posnet_epilogue_nhwc_win<2>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, wx0, wy0, wh, ww, dst, ld_dst);
+  else return -1;
+  return 0;
+}
+extern "C" int mpp_launch_shapenet_epilogue_nhwc_win(hipStream_t st, const void *logits, int elem_bytes, int ldw, int wx0, int wy0,
+                                                     int wh, int ww, float *dst, int ld_dst) {
+  if (((uintptr_t)logits & 15) || ((uintptr_t)dst & 15)) return -2;
+  const unsigned grid = (unsigned)(((size_t)wh * ww * 4 + 255) / 256);
+  if (elem_bytes == 4)
+    hipLaunchKernelGGL(k_shapenet_epilogue_nhwc_win<4>, dim3(grid), dim3(256), 0, st, logits, ldw, wx0, wy0, wh, ww, dst, ld_dst);
+  else if (elem_bytes == 2)
+    hipLaunchKernelGGL(k_shapenet_epilogue_nhwc_win<2>, dim3(grid), dim3(256), 0, st, logits, ldw, wx0, wy0, wh, ww, dst, ld_dst);
   else return -1;
   return 0;
 }

@@ -26,7 +26,8 @@ ABI_SYMBOLS = [
     "mpp_get_option", "mpp_set_maps", "mpp_set_image", "mpp_set_model", "mpp_set_kernels", "mpp_set_points", "mpp_get_points",
     "mpp_count", "mpp_get_points_all", "mpp_pack_detections", "mpp_total_energy", "mpp_delta_batch", "mpp_delta_vectors", "mpp_papangelou", "mpp_merge_score", "mpp_naive_init", "mpp_set_schedule",
     "mpp_replay", "mpp_run", "mpp_set_chain_keys", "mpp_step_index", "mpp_last_kernel_ms", "mpp_posnet_epilogue",
-    "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_quad_iou", "mpp_philox4x32", "mpp_abi_version",
+    "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
+    "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_philox4x32", "mpp_abi_version",
 ]
 
 
@@ -132,6 +133,11 @@ def load_library(path: Optional[str] = None):
         "mpp_affine_relu": (i32, [vp, vp, i32, i32, i64, i32, vp, vp]),
         "mpp_posnet_epilogue_nhwc": (i32, [vp, i32, i32, i32, i32, vp, i32, dbl, dbl, vp]),
         "mpp_shapenet_epilogue_nhwc": (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
+        "mpp_posnet_epilogue_win": (i32, [vp, i32, i32, i32, i32, vp, dbl, dbl, i32, i32, i32, i32, vp, i32]),
+        "mpp_shapenet_epilogue_win": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32]),
+        "mpp_posnet_epilogue_nhwc_win": (i32, [vp, i32, i32, i32, i32, vp, i32, dbl, dbl, i32, i32, i32, i32, vp, i32]),
+        "mpp_shapenet_epilogue_nhwc_win": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32]),
+        "mpp_shapenet_heads_win": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32]),
         "mpp_nhwc_glue": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
         "mpp_quad_iou": (i32, [vp, i32, vp, i32, vp, vp, i32]),
         "mpp_philox4x32": (None, [vp, vp, vp]),
@@ -571,6 +577,57 @@ class MppContext:
         self._check(self._L.mpp_shapenet_heads(self._h, H, W, ldh, ldw, _ptr(h), _ptr(w), _ptr(b), _ptr(marks[0]), _ptr(marks[1]),
                                                _ptr(marks[2])))
 
+    # -- window forms: the window (wx0, wy0, h x w) of an H x W crop, written through a view of a larger map --------------
+    def posnet_epilogue_win(self, pos_out, H: int, W: int, wx0: int, wy0: int, div_w: float, div_b: float, det_win):
+        """``posnet_epilogue`` of the crop ``pos_out`` ([3,ldh,ldw] float32, contiguous), restricted to the window at (wx0, wy0)
+        whose size is ``det_win``'s: det_win is an [h,w] float32 view with unit column stride, e.g. ``det[a:a+h, b:b+w]``."""
+        ldh, ldw = _planar_shape(pos_out, 3)
+        h, w, ld = _window_view(det_win, 1)
+        self._check(self._L.mpp_posnet_epilogue_win(self._h, H, W, ldh, ldw, _ptr(pos_out), float(div_w), float(div_b), int(wx0),
+                                                    int(wy0), h, w, _ptr(det_win), ld))
+
+    def shapenet_epilogue_win(self, logits, H: int, W: int, wx0: int, wy0: int, marks_win):
+        """``shapenet_epilogue`` of one head's crop logits ([32,ldh,ldw] float32, contiguous) into the window ``marks_win``:
+        an [h,w,32] float32 view of a mark map with contiguous pixels, e.g. ``marks[a:a+h, b:b+w]``."""
+        ldh, ldw = _planar_shape(logits, NCLASS)
+        h, w, ld = _window_view(marks_win, NCLASS)
+        self._check(self._L.mpp_shapenet_epilogue_win(self._h, H, W, ldh, ldw, _ptr(logits), int(wx0), int(wy0), h, w,
+                                                      _ptr(marks_win), ld))
+
+    def posnet_epilogue_nhwc_win(self, pos_out, H: int, W: int, wx0: int, wy0: int, div_w: float, div_b: float, det_win):
+        """``posnet_epilogue_win`` on a [1,3,ldh,ldw] channels-last float32 / bfloat16 network output"""
+        ldh, ldw, ch = nhwc_shape(pos_out)
+        if ch != 3:
+            raise ValueError("posnet output must have 3 channels")
+        h, w, ld = _window_view(det_win, 1)
+        self._check(self._L.mpp_posnet_epilogue_nhwc_win(self._h, H, W, ldh, ldw, _ptr(pos_out), int(pos_out.element_size()),
+                                                         float(div_w), float(div_b), int(wx0), int(wy0), h, w, _ptr(det_win), ld))
+
+    def shapenet_epilogue_nhwc_win(self, logits, H: int, W: int, wx0: int, wy0: int, marks_win):
+        """``shapenet_epilogue_win`` on a [1,32,ldh,ldw] channels-last float32 / bfloat16 head output"""
+        ldh, ldw, ch = nhwc_shape(logits)
+        if ch != NCLASS:
+            raise ValueError(f"a shapenet head must have {NCLASS} channels")
+        h, w, ld = _window_view(marks_win, NCLASS)
+        self._check(self._L.mpp_shapenet_epilogue_nhwc_win(self._h, H, W, ldh, ldw, _ptr(logits), int(logits.element_size()),
+                                                           int(wx0), int(wy0), h, w, _ptr(marks_win), ld))
+
+    def shapenet_heads_win(self, hid, w, b, H: int, W: int, wx0: int, wy0: int, marks_win):
+        """``shapenet_heads`` of the crop activations ``hid`` restricted to the window at (wx0, wy0); marks_win: three
+        [h,w,32] float32 views of the mark maps with the same shape and strides"""
+        import torch
+        ldh, ldw, c = nhwc_shape(hid)
+        if c != 32 or hid.dtype != torch.float32 or tuple(w.shape) != (3, 32, 32) or tuple(b.shape) != (3, 32) or len(marks_win) != 3:
+            raise ValueError("shapenet_heads_win: float32 channels-last activations of 32 channels, w [3,32,32], b [3,32]")
+        if not (w.is_contiguous() and b.is_contiguous()):
+            raise ValueError("shapenet_heads_win: contiguous weights")
+        views = [_window_view(m, NCLASS) for m in marks_win]
+        if len(set(views)) != 1:
+            raise ValueError("shapenet_heads_win: the three mark windows differ in shape or pitch")
+        h, wd, ld = views[0]
+        self._check(self._L.mpp_shapenet_heads_win(self._h, H, W, ldh, ldw, _ptr(hid), _ptr(w), _ptr(b), int(wx0), int(wy0), h, wd,
+                                                   _ptr(marks_win[0]), _ptr(marks_win[1]), _ptr(marks_win[2]), ld))
+
     # -- evaluation --------------------------------------------------------------------------------
     def quad_iou(self, a, b) -> np.ndarray:
         """IoU matrix [n][m] of convex quads a [n][8] and b [m][8] (-1: axis-aligned extents apart)."""
@@ -587,6 +644,31 @@ def nhwc_shape(x):
     if x.dim() != 4 or x.shape[0] != 1 or not x.is_contiguous(memory_format=torch.channels_last):
         raise ValueError("expected a [1,C,H,W] tensor in channels_last memory format")
     return int(x.shape[2]), int(x.shape[3]), int(x.shape[1])
+
+
+def _planar_shape(x, channels: int):
+    """(ldh, ldw) of a contiguous float32 [channels,ldh,ldw] (or [1,channels,ldh,ldw]) tensor; raises otherwise."""
+    import torch
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[0] != 1) \
+            or x.shape[-3] != channels:
+        raise ValueError(f"expected a contiguous float32 [{channels},H,W] tensor")
+    return int(x.shape[-2]), int(x.shape[-1])
+
+
+def _window_view(v, channels: int):
+    """(h, w, row pitch in pixels) of a float32 window view: [h,w] with unit column stride (channels 1) or [h,w,channels] with
+    contiguous pixels (a slice of a larger map); raises otherwise."""
+    import torch
+    shape = (int(v.shape[0]), int(v.shape[1])) if v.dim() >= 2 else None
+    ok = v.dtype == torch.float32 and v.is_cuda and shape is not None and v.dim() == (2 if channels == 1 else 3)
+    if ok and channels > 1:
+        ok = int(v.shape[2]) == channels and v.stride(2) == 1 and v.stride(1) == channels and v.stride(0) % channels == 0
+    elif ok:
+        ok = v.stride(1) == 1
+    if not ok or (shape[0] > 1 and v.stride(0) < channels * shape[1]):
+        raise ValueError(f"expected a float32 CUDA window view [h,w{',' + str(channels) if channels > 1 else ''}] with contiguous "
+                         "pixels and rows at least one window row apart")
+    return shape[0], shape[1], max(v.stride(0) // channels, shape[1])
 
 
 def philox(ctr, key) -> np.ndarray:

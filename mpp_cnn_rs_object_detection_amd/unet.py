@@ -16,6 +16,7 @@ disappears.
 from __future__ import annotations
 
 import json
+import logging
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -183,11 +184,73 @@ def halo_crop(region, shape, halo: int = HALO, align: int = 8):
     return (max(0, x0 - halo) // align * align, min(H, x1 + halo), max(0, y0 - halo) // align * align, min(W, y1 + halo))
 
 
+def padded_pixels(shape, depth: int) -> int:
+    """pixels the nets see for an image of ``shape`` (H, W): both sides padded to a multiple of 2**depth (pad_before_infer)"""
+    div = 2 ** depth
+    return -(-int(shape[0]) // div) * div * (-(-int(shape[1]) // div) * div)
+
+
+def _axis_cuts(lo: int, hi: int, n: int, halo: int, align: int):
+    """Per core length c (a multiple of ``align``), the cuts of [lo, hi) into cores -- interior cuts on multiples of c,
+    hence of align -- with the largest and the summed padded crop extent along this axis."""
+    out, a0 = [], lo // align * align
+    for c in range(align, -(-(hi - a0) // align) * align + 1, align):
+        cuts = [lo] + list(range(a0 + c, hi, c)) + [hi]
+        ext = [-(-(min(n, b1 + halo) - max(0, b0 - halo) // align * align) // align) * align for b0, b1 in zip(cuts, cuts[1:])]
+        out.append((max(ext), sum(ext), cuts))
+    return out
+
+
+def chunk_plan(shape, max_pixels: int, depth: int, halo: int = HALO, region=None):
+    """Crops for a forward under a budget: a list of (core, crop), both (x0, x1, y0, y1).  The cores tile ``region``
+    (default: the whole image of ``shape``) exactly, with edges on multiples of 2**depth except at the region's bottom and
+    right; each crop is ``halo_crop(core, shape, halo, 2**depth)``, whose padded size (``pad_before_infer``) is at most
+    ``max_pixels``.  Of all such grids of equal cores, the one whose crops hold the fewest padded pixels in total (the halo
+    overhead), then the one with fewer crops.  Raises ValueError when even the smallest cores do not fit.
+
+    A crop's padded extent along one axis depends on that axis's cuts only, so the total is (sum over row bands) x (sum over
+    column bands) and the largest crop is (largest row extent) x (largest column extent): the search runs per axis."""
+    H, W = int(shape[0]), int(shape[1])
+    x0, x1, y0, y1 = (0, H, 0, W) if region is None else (int(v) for v in region)
+    if not (0 <= x0 < x1 <= H and 0 <= y0 < y1 <= W):
+        raise ValueError(f"region {region} is empty or outside the {H} x {W} image")
+    align = 2 ** depth
+    rows, cols = _axis_cuts(x0, x1, H, halo, align), _axis_cuts(y0, y1, W, halo, align)
+    cols.sort(key=lambda o: o[0])
+    best, best_col, col_max = None, None, []
+    for m, tot, cuts in cols:                 # best_col[i]: the fewest summed pixels among the i + 1 narrowest options
+        if best_col is None or (tot, len(cuts)) < (best_col[1], len(best_col[2])):
+            best_col = (m, tot, cuts)
+        col_max.append((m, best_col))
+    for m, tot, cuts in rows:
+        fit = [c for cm, c in col_max if cm * m <= max_pixels]
+        if not fit:
+            continue
+        c = fit[-1]
+        key = (tot * c[1], (len(cuts) - 1) * (len(c[2]) - 1))
+        if best is None or key < best[0]:
+            best = (key, cuts, c[2])
+    if best is None:
+        raise ValueError(f"no plan fits {max_pixels} pixels per forward: the smallest crop ({align}-px cores plus a {halo}-px halo) "
+                         f"pads to {min(r[0] for r in rows) * min(c[0] for c in cols)} pixels")
+    _, rc, cc = best
+    return [((a, b, c, d), halo_crop((a, b, c, d), (H, W), halo, align)) for a, b in zip(rc, rc[1:]) for c, d in zip(cc, cc[1:])]
+
+
+#: bytes of the output maps per image pixel: det (4) + three [32] float32 mark rows (384)
+MAP_BYTES_PER_PIXEL = 388
+#: peak device memory of one forward per padded pixel, the maps excluded, float32 on an MI355X (torch.cuda.max_memory_allocated,
+#: profiles/unet_tiled.md): 852 B on the fused channels-last path (1024^2 to 4096^2), 978 B on the module path (640^2, 992^2);
+#: the larger, rounded up, sizes the budget of the out-of-memory fallback
+FORWARD_BYTES_PER_PIXEL = 980
+
+
 class ScoreMapNets:
     """PosNet + ShapeNet inference on one GPU with the fused HIP epilogues."""
 
     def __init__(self, posnet: PosNet, shapenet: ShapeNet, device: int = 0, div_clf: Tuple[float, float] = None,
-                 dtype: torch.dtype = torch.float32, ctx=None, layout: Optional[str] = None):
+                 dtype: torch.dtype = torch.float32, ctx=None, layout: Optional[str] = None,
+                 max_forward_pixels: Optional[int] = None):
         from .hip_api import MppContext
         self.device = torch.device("cuda", device)
         # "nhwc": channels-last activations, everything between two convolutions in one `mpp_nhwc_glue` pass;
@@ -210,6 +273,9 @@ class ScoreMapNets:
         # 512x512 3.4 ms vs 4.8 ms; 2048x2048 41 ms (nchw) / 36 ms (nhwc) float32, 31 / 15 ms bfloat16
         self.min_fused_pixels = 1 << 20
         self._fold_cache = {}
+        # at most this many padded pixels per forward (None: the whole image at once); see infer
+        self.max_forward_pixels = max_forward_pixels
+        self._keep = None
 
     # -- fused inference path: conv (MIOpen) + ONE pass of bias/BatchNorm/ReLU (mpp_affine_relu) per convolution ------
     def _folded(self, conv: nn.Conv2d, bn: nn.BatchNorm2d):
@@ -341,10 +407,56 @@ class ScoreMapNets:
         return x
 
     @torch.no_grad()
-    def infer(self, image) -> Tuple[Tensor, List[Tensor]]:
-        """image: [H,W,3] float in [0,1] (numpy or tensor) -> det [H,W] f32, marks 3 x [H,W,32] f32, on the GPU."""
+    def infer(self, image, max_pixels: Optional[int] = None) -> Tuple[Tensor, List[Tensor]]:
+        """image: [H,W,3] float in [0,1] (numpy or tensor) -> det [H,W] f32, marks 3 x [H,W,32] f32, on the GPU.
+
+        ``max_pixels`` (default: the ``max_forward_pixels`` given at construction; None: no limit) bounds the padded
+        pixels of one forward: a larger image is walked in crops (``chunk_plan``), each crop's epilogues writing its core
+        straight into the full maps.  Each core is bit for bit ``infer_region(image, core)``.  A whole-image forward that
+        runs out of device memory is retried that way under a budget taken from the free memory."""
+        img = self._upload(image)
+        H, W = img.shape[1:]
+        depth = self.pos.backbone.depth
+        budget = self.max_forward_pixels if max_pixels is None else max_pixels
+        if budget is not None and padded_pixels((H, W), depth) > budget:
+            return self._infer_tiled(lambda a, b, c, d: img[:, a:b, c:d], (H, W), chunk_plan((H, W), budget, depth))
+        try:
+            return self._forward(img)
+        except torch.cuda.OutOfMemoryError:
+            pass                # (handled outside the except clause: the traceback's frames hold the partial outputs)
+        torch.cuda.synchronize(self.device)
+        self._keep = None
+        torch.cuda.empty_cache()
+        free = torch.cuda.mem_get_info(self.device)[0]
+        budget = int(0.8 * (free - MAP_BYTES_PER_PIXEL * H * W) / FORWARD_BYTES_PER_PIXEL)
+        plan = chunk_plan((H, W), max(budget, 1), depth)
+        logging.warning(f"score maps: the {H} x {W} forward ran out of device memory; tiled under {budget} pixels per forward "
+                        f"({len(plan)} crops)")
+        return self._infer_tiled(lambda a, b, c, d: img[:, a:b, c:d], (H, W), plan)
+
+    def _upload(self, image) -> Tensor:
+        """[H,W,>=3] numpy / tensor -> [3,H,W] float32 on the device"""
         img = torch.as_tensor(np.asarray(image) if not torch.is_tensor(image) else image)
-        img = img[..., :3].permute(2, 0, 1).float().to(self.device)
+        return img[..., :3].permute(2, 0, 1).float().to(self.device)
+
+    def _infer_tiled(self, crop_of, shape, plan, origin=(0, 0)) -> Tuple[Tensor, List[Tensor]]:
+        """Maps of shape (h, w) whose pixel (0, 0) is image pixel ``origin``, from ``plan`` (``chunk_plan``): the forward of each
+        crop (``crop_of(x0, x1, y0, y1)``: the [3,h,w] device picture) writes its core through the window epilogues.  A crop's
+        intermediates are released before the next crop's forward, so the peak is one crop's forward plus the maps."""
+        h, w = shape
+        det = torch.empty((h, w), dtype=torch.float32, device=self.device)
+        marks = [torch.empty((h, w, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
+        ox, oy = origin
+        for (x0, x1, y0, y1), (cx0, cx1, cy0, cy1) in plan:
+            self._keep = None
+            sl = (slice(x0 - ox, x1 - ox), slice(y0 - oy, y1 - oy))
+            self._forward(crop_of(cx0, cx1, cy0, cy1), (x0 - cx0, y0 - cy0, det[sl], [m[sl] for m in marks]))
+        self._keep = None
+        return det, marks
+
+    def _forward(self, img: Tensor, win=None) -> Tuple[Tensor, List[Tensor]]:
+        """Both nets and their epilogues on the whole of img [3,H,W]; ``win`` = (wx0, wy0, det, marks): only that window of
+        the maps, written into the given views (det [h,w], marks 3 x [h,w,32]) instead of new maps."""
         H, W = img.shape[1:]
         padded, _ = pad_before_infer(img, self.pos.backbone.depth)
         x = padded.unsqueeze(0).contiguous()
@@ -352,13 +464,19 @@ class ScoreMapNets:
         big = padded.shape[1] * padded.shape[2] >= self.min_fused_pixels
         if self.layout == "nhwc" and self.fused and big and padded.shape[1] >= 16 and padded.shape[2] >= 16:
             xi = padded.permute(1, 2, 0).contiguous().unsqueeze(0).permute(0, 3, 1, 2)      # [1,3,H,W] over NHWC memory
-            det = torch.empty((H, W), dtype=torch.float32, device=self.device)
-            marks = [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
+            if win is None:
+                det = torch.empty((H, W), dtype=torch.float32, device=self.device)
+                marks = [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
+            else:
+                wx0, wy0, det, marks = win
             cur = torch.cuda.current_stream(self.device)
 
             def pos_part():
                 pos_out = self._cl(self._head(self.pos.final_layer, self._backbone_nhwc(self.pos.backbone, xi)))
-                self.ctx.posnet_epilogue_nhwc(pos_out, H, W, self.div_w, self.div_b, det)
+                if win is None:
+                    self.ctx.posnet_epilogue_nhwc(pos_out, H, W, self.div_w, self.div_b, det)
+                else:
+                    self.ctx.posnet_epilogue_nhwc_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
                 return pos_out
 
             def shp_part():
@@ -368,11 +486,17 @@ class ScoreMapNets:
                     # the three 1x1 heads, their biases and the softmax in ONE pass over h (csrc/mpp_conv.hip): 8.6 GB of
                     # traffic on a 4096 x 4096 image instead of 38 GB
                     h = self._cl(h)
-                    self.ctx.shapenet_heads(h, heads[0], heads[1], H, W, marks)
+                    if win is None:
+                        self.ctx.shapenet_heads(h, heads[0], heads[1], H, W, marks)
+                    else:
+                        self.ctx.shapenet_heads_win(h, heads[0], heads[1], H, W, wx0, wy0, marks)
                     return h
                 logits = [self._cl(self._head(fl[0], h)) for fl in self.shp.final_layers]
                 for k in range(3):
-                    self.ctx.shapenet_epilogue_nhwc(logits[k], H, W, marks[k])
+                    if win is None:
+                        self.ctx.shapenet_epilogue_nhwc(logits[k], H, W, marks[k])
+                    else:
+                        self.ctx.shapenet_epilogue_nhwc_win(logits[k], H, W, wx0, wy0, marks[k])
                 return logits
 
             if self.two_streams:
@@ -389,7 +513,7 @@ class ScoreMapNets:
                 for st in self._streams:
                     cur.wait_stream(st)
                 self.ctx.set_stream(cur.cuda_stream)
-                for t in [det] + marks:
+                for t in [det, xi] + marks:          # (det / marks: written there; xi: read there)
                     for st in self._streams:
                         t.record_stream(st)
                 self._keep = tuple(keep)
@@ -406,31 +530,45 @@ class ScoreMapNets:
             else:
                 pos_out = self.pos(x)
                 logits = self.shp(x)
-        return self._epilogues(pos_out, logits, H, W)
+        return self._epilogues(pos_out, logits, H, W, win)
 
     @torch.no_grad()
-    def infer_region(self, image, region) -> Tuple[Tensor, List[Tensor]]:
+    def infer_region(self, image, region, max_pixels: Optional[int] = None) -> Tuple[Tensor, List[Tensor]]:
         """Score maps of the image region ``(x0, x1, y0, y1)`` only: the nets run on the region plus ``HALO`` pixels
         (origin rounded down to a multiple of 2**depth so that pooling and the bottom/right zero padding of
         ``pad_before_infer`` fall as they do on the whole image, crop clamped to the image so that image borders
         keep their reflect padding / one-sided differences); everything an interior crop border can influence lies
         inside the halo, which is cut off.  Up to the convolution library's choice of algorithm per shape the result
         equals ``infer(image)[region]`` -- this is how a rank of a multi-GPU run gets the maps of its own tiles
-         without a forward over the whole image."""
+         without a forward over the whole image.  Under a budget (``max_pixels``, as in ``infer``) that the
+        region's crop exceeds, the region is built from a ``chunk_plan`` over it."""
         x0, x1, y0, y1 = (int(v) for v in region)
-        cx0, cx1, cy0, cy1 = halo_crop(region, tuple(image.shape[:2]), align=2 ** self.pos.backbone.depth)
-        det, marks = self.infer(image[cx0:cx1, cy0:cy1])
+        depth = self.pos.backbone.depth
+        cx0, cx1, cy0, cy1 = halo_crop(region, tuple(image.shape[:2]), align=2 ** depth)
+        budget = self.max_forward_pixels if max_pixels is None else max_pixels
+        if budget is not None and padded_pixels((cx1 - cx0, cy1 - cy0), depth) > budget:
+            plan = chunk_plan(tuple(image.shape[:2]), budget, depth, region=region)
+            return self._infer_tiled(lambda a, b, c, d: self._upload(image[a:b, c:d]), (x1 - x0, y1 - y0), plan, origin=(x0, y0))
+        det, marks = self.infer(image[cx0:cx1, cy0:cy1], max_pixels=max_pixels)
         sl = (slice(x0 - cx0, x1 - cx0), slice(y0 - cy0, y1 - cy0))
         return det[sl], [m[sl] for m in marks]
 
-    def _epilogues(self, pos_out: Tensor, logits: List[Tensor], H: int, W: int) -> Tuple[Tensor, List[Tensor]]:
+    def _epilogues(self, pos_out: Tensor, logits: List[Tensor], H: int, W: int, win=None) -> Tuple[Tensor, List[Tensor]]:
         pos_out = pos_out[0].float().contiguous()
         logits = [t[0].float().contiguous() for t in logits]
-        det = torch.empty((H, W), dtype=torch.float32, device=self.device)
-        marks = [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
+        if win is None:
+            det = torch.empty((H, W), dtype=torch.float32, device=self.device)
+            marks = [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
+        else:
+            wx0, wy0, det, marks = win
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        self.ctx.posnet_epilogue(pos_out, H, W, self.div_w, self.div_b, det)
-        for k in range(3):
-            self.ctx.shapenet_epilogue(logits[k], H, W, marks[k])
+        if win is None:
+            self.ctx.posnet_epilogue(pos_out, H, W, self.div_w, self.div_b, det)
+            for k in range(3):
+                self.ctx.shapenet_epilogue(logits[k], H, W, marks[k])
+        else:
+            self.ctx.posnet_epilogue_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
+            for k in range(3):
+                self.ctx.shapenet_epilogue_win(logits[k], H, W, wx0, wy0, marks[k])
         self._keep = (pos_out, logits)        # alive until the kernels on this stream have consumed them
         return det, marks
