@@ -324,6 +324,27 @@ int mpp_shapenet_heads_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const f
  * README.md:22-30).  on_device != 0: a, b, out are device pointers. */
 int mpp_quad_iou(mpp_ctx *ctx, int n, const double *a, int m, const double *b, double *out, int on_device);
 
+/* The CNN-only baseline's detection step (csrc/mpp_detect.hip): the PosNet / ShapeNet inference of
+ * position_net/pos_net_model.py:376-380 and shape_net/shape_net_model.py:283-288 (and naive_detection,
+ * sample_rjmcmc.py:23-27) on a whole score map.  det [H][ld] float32, xy [cap][2] int32 (row, col) and scores [cap] float32
+ * are device pointers; n_candidates / n_kept are host pointers; the ctx's stream, synchronous up to the last kernel.
+ *  - candidates: det > (float)threshold when strict (PosNet), det >= (float)threshold otherwise (ShapeNet's PosNet call,
+ *    naive_detection) -- a float32 compare against the threshold rounded to float32, as NumPy compares a float32 array
+ *    with a Python float (k_naive_init's compare is in double and is not this one);
+ *  - rank: value descending, ties toward the larger row-major flat index r*W + c (-0 ties with +0);
+ *  - NMS: in rank order a candidate is kept iff every kept candidate ranked above it lies at sqrt(dx^2+dy^2) > nms_distance
+ *    (double; utils/nms.py:68-110), 0 <= nms_distance <= 32 (else -1);
+ *  - output: the kept centres and their scores in pick (rank) order.  No cap of its own: if more than cap are kept it
+ *    returns -13, *n_kept = the number needed, and writes nothing to xy / scores.  H*W >= 2^31: -1.
+ * Read-only option "detect_launches": the resolve launches of the last call.  -9: a resolve that stopped making progress. */
+int mpp_detect_centers(mpp_ctx *ctx, int H, int W, int ld, const float *det, double threshold, int strict, double nms_distance,
+                       int cap, int32_t *xy, float *scores, int64_t *n_candidates, int64_t *n_kept);
+/* The argmax class of each of the three mark maps m0..m2 [H][ld][32] float32 (first maximum, a NaN wins: np.argmax) at the
+ * n pixels xy [n][2] (row, col): classes [n][3] int32, -1 for a pixel outside the map -- output_vector_to_value
+ * (shape_net/mappings.py:145-157) at ShapeNet's centres.  All device pointers, the ctx's stream (asynchronous). */
+int mpp_mark_classes(mpp_ctx *ctx, int H, int W, int ld, const float *m0, const float *m1, const float *m2, int n,
+                     const int32_t *xy, int32_t *classes);
+
 void mpp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 int mpp_abi_version(void);
 

@@ -4,7 +4,8 @@
     python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
-hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``).  ``-p train -m mpp`` learns the
+hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the CNN-only baseline's detections (DOTA hbb /
+obb files), ``-p eval`` scores those.  ``-p train -m mpp`` learns the
 energy weights (manual / ordering / integral criterion) and calibrates; the training loops of the two
 U-Nets are outside this build.  With ``torchrun --nproc-per-node N`` the images of the dataset are
 dealt to N GPUs (one gather of the results at the end; RCCL).
@@ -84,45 +85,96 @@ def load_nets(mpp_config, device, max_forward_pixels=None):
 
 
 class ScoreMapWriter:
-    """``-m posnet|shapenet -p infer``: write the reference's hand-off pickles
-    (``pos_net_model.py:407-424`` / ``shape_net_model.py:353-381``)."""
+    """``-m posnet|shapenet -p infer|eval|infereval``: the reference's hand-off pickles (``pos_net_model.py:407-424`` /
+    ``shape_net_model.py:353-381``) and the CNN-only baseline's detections.
+
+    * posnet: candidates ``map > min_confidence``, distance NMS on the device, 12-px boxes in DOTA hbb files (ground truth:
+      the same boxes at the annotated centres);
+    * shapenet: centres from the PosNet named by ``config["inference"]["pos_model"]`` (``>=``, NMS; one forward gives both
+      maps) or, without it, the annotated centres with score 1; a rectangle per centre from the argmax marks, in DOTA obb
+      files.  ``eval`` runs ``dota_eval`` (hbb / obb) over the five IoU thresholds."""
 
     def __init__(self, config, kind, dataset, device, max_forward_pixels=None):
         from mpp_cnn_rs_object_detection_amd import unet
         from mpp_cnn_rs_object_detection_amd.paths import get_model_base_path
-        self.kind, self.config = kind, config
+        self.kind, self.config, self.device = kind, config, device
         self.dataset = dataset or config["data_loader"]["dataset"]
-        d = os.path.join(get_model_base_path(), kind, config["model_name"])
+        self.model_dir = os.path.join(get_model_base_path(), kind, config["model_name"])
+        d = self.model_dir
         self.pos, self.shp = unet.PosNet(), unet.ShapeNet()
         if not unet.load_torch_model(self.pos if kind == "posnet" else self.shp, d):
             raise FileNotFoundError(f"no model.pt / checkpoint_*.pt under {d}")
-        self.nets = unet.ScoreMapNets(self.pos, self.shp, device=device, div_clf=unet.load_div_clf(d),
+        self.pos_model = config.get("inference", {}).get("pos_model") if kind == "shapenet" else None
+        div_dir = d
+        if self.pos_model:
+            div_dir = os.path.join(get_model_base_path(), "posnet", self.pos_model)
+            if not unet.load_torch_model(self.pos, div_dir):
+                raise FileNotFoundError(f"no model.pt / checkpoint_*.pt under {div_dir} (inference.pos_model)")
+        self.nets = unet.ScoreMapNets(self.pos, self.shp, device=device, div_clf=unet.load_div_clf(div_dir),
                                       max_forward_pixels=max_forward_pixels)
 
-    def infer(self, subset, overwrite=True, **_):
+    def infer(self, subset, min_confidence=0.2, overwrite=True, **_):
+        import logging
         import pickle
         import re
+        import numpy as np
         from matplotlib import pyplot as plt
+        from mpp_cnn_rs_object_detection_amd import cnn_detection as cd
         from mpp_cnn_rs_object_detection_amd import mappings
+        from mpp_cnn_rs_object_detection_amd.dota_results import DOTAResultsTranslator
         from mpp_cnn_rs_object_detection_amd.paths import fetch_data_paths, get_inference_path
+        from mpp_cnn_rs_object_detection_amd.shapes import rect_to_poly
         out_dir = get_inference_path(self.config["model_name"], self.dataset, subset)
         os.makedirs(out_dir, exist_ok=True)
-        for pf in fetch_data_paths(self.dataset, subset)["images"]:
+        posnet = self.kind == "posnet"
+        dota = DOTAResultsTranslator(self.dataset, subset, out_dir, "hbb" if posnet else "obb", all_classes=["vehicle"])
+        if not posnet and not self.pos_model:
+            logging.warning("no position inference model specified in config, falling back to using ground truth")
+        paths = fetch_data_paths(self.dataset, subset)
+        for pf, af in zip(paths["images"], paths["annotations"]):
             pid = int(re.match(r"([0-9]+).*.png", os.path.split(pf)[1]).group(1))
             out = os.path.join(out_dir, f"{pid:04}_results.pkl")
             if os.path.exists(out) and not overwrite:
                 continue
+            with open(af, "rb") as f:
+                labels = pickle.load(f)
+            gt_centers, gt_params = np.asarray(labels["centers"]), labels["parameters"]
+            vehicle = lambda n: ["vehicle"] * n
             det, marks = self.nets.infer(plt.imread(pf)[:, :, :3])
-            if self.kind == "posnet":
-                res = {"detection_map": det.cpu().numpy(), "detection_type": "map"}
+            if posnet:
+                det_np = det.cpu().numpy()
+                cand = np.array(np.where(det_np > min_confidence)).T
+                centers, scores, n_cand = cd.detect_centers(det, min_confidence, strict=True)
+                assert n_cand == len(cand), (n_cand, len(cand))
+                res = {"detection_map": det_np, "detection_type": "map", "detection": cand,
+                       "detection_score": det_np[cand[:, 0], cand[:, 1]]}
+                gt_poly = cd.box_polygons(cd.posnet_boxes(gt_centers))
+                dota.add_gt(image_id=pid, polygons=gt_poly, difficulty=labels["difficult"], flip_coor=False,
+                            categories=vehicle(len(gt_poly)))
+                dota.add_detections(image_id=pid, scores=scores, bbox=cd.posnet_boxes(centers), flip_coor=False,
+                                    class_names=vehicle(len(scores)))
             else:
-                res = {"output": [m.permute(2, 0, 1).unsqueeze(0).cpu().numpy() for m in marks],
-                       "mappings": mappings.default_mappings()}
+                if self.pos_model:
+                    centers, scores, _ = cd.detect_centers(det, min_confidence, strict=False)
+                else:
+                    centers, scores = gt_centers.astype(np.int64).reshape(-1, 2), np.ones(len(gt_centers))
+                maps = mappings.default_mappings()
+                params = cd.mark_params(marks, centers, maps)
+                polys = cd.shapenet_polygons(centers, params)
+                res = {"output": [m.permute(2, 0, 1).unsqueeze(0).cpu().numpy() for m in marks], "mappings": maps,
+                       "detection": polys, "detection_type": "poly", "detection_center": centers, "detection_score": scores,
+                       "detection_params": [tuple(p) for p in params], "pos_model": self.pos_model}
+                gt_poly = np.array([rect_to_poly(c, short=p[0], long=p[1], angle=p[2]) for c, p in zip(gt_centers, gt_params)])
+                dota.add_gt(image_id=pid, polygons=gt_poly, difficulty=labels["difficult"], categories=vehicle(len(gt_poly)))
+                dota.add_detections(image_id=pid, scores=scores, polygons=polys, flip_coor=True, class_names=vehicle(len(scores)))
             with open(out, "wb") as f:
                 pickle.dump(res, f)
+        dota.save()
 
     def eval(self):
-        raise NotImplementedError
+        from mpp_cnn_rs_object_detection_amd.dota_eval import dota_eval
+        return dota_eval(model_dir=self.model_dir, dataset=self.dataset, subset="val",
+                         det_type="hbb" if self.kind == "posnet" else "obb", device=self.device)
 
 
 if __name__ == "__main__":

@@ -10,6 +10,7 @@
 
 #include "mpp_device.hpp"
 #include "mpp_prepass.hpp"
+#include "mpp_detect.hpp"
 
 extern "C" size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 extern "C" size_t mpp_chain_static_lds_bytes(int waves);
@@ -169,6 +170,7 @@ struct mpp_ctx {
   // uniform grid over one tile's configuration for the from-scratch energies (built per call; see mpp_scratch.hip)
   int32_t *g_start = nullptr, *g_cursor = nullptr, *g_items = nullptr;
   int g_cells = 0, g_cap = 0, grid_min_points = 256;
+  DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
 };
 
 static int fail(mpp_ctx *c, int code, const char *fmt, ...) {
@@ -283,6 +285,7 @@ extern "C" int mpp_destroy(mpp_ctx *c) {
   if (c->pre_rec) (void)hipFree(c->pre_rec);
   if (c->d_route) (void)hipFree(c->d_route);
   if (c->d_route_until) (void)hipFree(c->d_route_until);
+  mpp_detect_free(&c->detect);
   if (c->dp) (void)hipFree(c->dp);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -398,6 +401,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "prepass")) return c->prepass;
   if (!strcmp(name, "prepass_mb")) return c->prepass_mb;
   if (!strcmp(name, "prepass_used")) return c->prepass_used;
+  if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)
@@ -1538,6 +1542,25 @@ extern "C" int mpp_quad_iou(mpp_ctx *c, int n, const double *a, int m, const dou
   }
   (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
   return rc;
+}
+// ---- the CNN-only baseline's detection step (mpp_detect.hip) ------------------------------------------------------------
+extern "C" int mpp_detect_centers(mpp_ctx *c, int H, int W, int ld, const float *det, double threshold, int strict,
+                                  double nms_distance, int cap, int32_t *xy, float *scores, int64_t *n_candidates,
+                                  int64_t *n_kept) {
+  if (!c) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  return mpp_detect_run(c->stream, &c->detect, H, W, ld, det, threshold, strict, nms_distance, cap, xy, scores, n_candidates,
+                        n_kept, &c->err);
+}
+extern "C" int mpp_mark_classes(mpp_ctx *c, int H, int W, int ld, const float *m0, const float *m1, const float *m2, int n,
+                                const int32_t *xy, int32_t *classes) {
+  if (!c || H < 0 || W < 0 || ld < W || n < 0 || (n > 0 && (!m0 || !m1 || !m2 || !xy || !classes)))
+    return fail(c, -1, "bad mark_classes arguments");
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  mpp_launch_mark_classes(c->stream, H, W, ld, m0, m1, m2, n, xy, classes);
+  HIPCHK(c, hipGetLastError());
+  return 0;
 }
 extern "C" int mpp_shapenet_epilogue(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *logits, float *marks) {
   if (!c || !logits || !marks || H <= 0 || W <= 0 || ldh < H || ldw < W) return fail(c, -1, "bad epilogue arguments");

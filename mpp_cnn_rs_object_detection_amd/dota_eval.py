@@ -6,6 +6,11 @@ Mirror of the reference's ``metrics/dota_eval.py:16-87`` (same arguments, same `
 module ``polyiou`` of an un-vendored clone (``README.md:22-30``); here ``voc_eval`` keeps the devkit's signature and
 matching rule, and the rotated IoUs of one image come from ONE launch of ``mpp_quad_iou`` (``csrc/mpp_metrics.hip``)
 -- there is no CPU fallback: without the HIP library this module raises.
+
+``det_type="hbb"`` (PosNet's axis-aligned boxes, detection lines ``id score x1 y1 x2 y2``): each box becomes the quad
+(x1,y1) (x2,y1) (x2,y2) (x1,y2) and goes through the same task-1 evaluator -- the fix the reference's comment on its
+broken hbb branch names (``metrics/dota_eval.py:48-49``).  The IoU is the continuous area ratio of task 1, not the
+devkit's task-2 convention of inclusive pixel boxes (+1 on each side).
 """
 from __future__ import annotations
 
@@ -57,9 +62,29 @@ def _convex(q: np.ndarray) -> np.ndarray:
     return np.all(cr >= -1e-9, axis=1) | np.all(cr <= 1e-9, axis=1)
 
 
+def hbb_to_quads(boxes) -> np.ndarray:
+    """[n, 8] quads (x1,y1, x2,y1, x2,y2, x1,y2) of axis-aligned boxes [n, 4] (x1, y1, x2, y2)"""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    return b[:, [0, 1, 2, 1, 2, 3, 0, 3]]
+
+
+def parse_detections(lines: List[str], det_type: str = "obb"):
+    """image ids, confidences and [n, 8] quads of detection lines ``id score`` + 8 coordinates (obb) or 4 (hbb)"""
+    splitlines = [x.strip().split(" ") for x in lines if x.strip()]
+    image_ids = [x[0] for x in splitlines]
+    confidence = np.array([float(x[1]) for x in splitlines])
+    n_coord = 4 if det_type == "hbb" else 8
+    if any(len(x) != 2 + n_coord for x in splitlines):
+        raise ValueError(f"{det_type} detection lines must hold an image id, a score and {n_coord} coordinates")
+    BB = np.array([[float(z) for z in x[2:]] for x in splitlines], dtype=np.float64).reshape(-1, n_coord)
+    return image_ids, confidence, hbb_to_quads(BB) if det_type == "hbb" else BB
+
+
 def voc_eval(detpath: str, annopath: str, imagesetfile: str, classname: str, ovthresh: float = 0.5,
-             use_07_metric: bool = False, ctx: Optional["hip_api.MppContext"] = None, device: int = 0):
-    """rec, prec, ap = voc_eval(...) -- arguments and matching rule of the devkit's task-1 ``voc_eval``."""
+             use_07_metric: bool = False, ctx: Optional["hip_api.MppContext"] = None, device: int = 0,
+             det_type: str = "obb"):
+    """rec, prec, ap = voc_eval(...) -- arguments and matching rule of the devkit's task-1 ``voc_eval``; ``det_type="hbb"``
+    reads 4-coordinate detection lines as axis-aligned quads."""
     own = ctx is None
     if own:
         ctx = hip_api.MppContext(device)
@@ -76,10 +101,7 @@ def voc_eval(detpath: str, annopath: str, imagesetfile: str, classname: str, ovt
         npos += int(np.sum(~difficult))
         class_recs[name] = {"bbox": bbox, "difficult": difficult, "det": np.zeros(len(R), bool)}
     with open(detpath.format(classname)) as f:
-        splitlines = [x.strip().split(" ") for x in f.readlines() if x.strip()]
-    image_ids = [x[0] for x in splitlines]
-    confidence = np.array([float(x[1]) for x in splitlines])
-    BB = np.array([[float(z) for z in x[2:]] for x in splitlines], dtype=np.float64).reshape(-1, 8)
+        image_ids, confidence, BB = parse_detections(f.readlines(), det_type)
     if not _convex(BB).all():
         raise ValueError("non-convex detection quadrilateral")
     sorted_ind = np.argsort(-confidence)
@@ -126,9 +148,6 @@ def voc_eval(detpath: str, annopath: str, imagesetfile: str, classname: str, ovt
 
 def dota_eval(model_dir: str, dataset: str, subset: str, det_type: str, postfix: str = "", device: int = 0) -> dict:
     assert det_type in ["obb", "hbb"]
-    if det_type != "obb":
-        raise NotImplementedError("only the oriented-box task is evaluated (the reference's hbb branch is marked broken, "
-                                  "metrics/dota_eval.py:49)")
     model_name = os.path.split(model_dir.rstrip("/"))[1]
     dota_files_path = os.path.join(get_inference_path(model_name=model_name, dataset=dataset, subset=subset), "dota" + postfix)
     det_path = os.path.join(dota_files_path, "det", r"{:s}.txt")
@@ -142,7 +161,7 @@ def dota_eval(model_dir: str, dataset: str, subset: str, det_type: str, postfix:
         results, classaps = {}, []
         for classname in classnames:
             rec, prec, ap = voc_eval(det_path, annot_path, image_set_file, classname, ovthresh=iou_t,
-                                     use_07_metric=False, ctx=ctx)
+                                     use_07_metric=False, ctx=ctx, det_type=det_type)
             classaps.append(ap)
             print(f"ap : {ap}")
             results[classname] = {"ap": ap, "precision": prec.tolist(), "recall": rec.tolist()}

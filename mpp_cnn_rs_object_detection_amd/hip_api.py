@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "mpp_count", "mpp_get_points_all", "mpp_pack_detections", "mpp_total_energy", "mpp_delta_batch", "mpp_delta_vectors", "mpp_papangelou", "mpp_merge_score", "mpp_naive_init", "mpp_set_schedule",
     "mpp_replay", "mpp_run", "mpp_set_chain_keys", "mpp_step_index", "mpp_last_kernel_ms", "mpp_posnet_epilogue",
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
-    "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_philox4x32", "mpp_abi_version",
+    "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_philox4x32", "mpp_abi_version",
 ]
 
 
@@ -140,6 +140,8 @@ def load_library(path: Optional[str] = None):
         "mpp_shapenet_heads_win": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32]),
         "mpp_nhwc_glue": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
         "mpp_quad_iou": (i32, [vp, i32, vp, i32, vp, vp, i32]),
+        "mpp_detect_centers": (i32, [vp, i32, i32, i32, vp, dbl, i32, dbl, i32, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "mpp_mark_classes": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
         "mpp_philox4x32": (None, [vp, vp, vp]),
         "mpp_abi_version": (i32, []),
     }
