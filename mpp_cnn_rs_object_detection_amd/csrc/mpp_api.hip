@@ -34,10 +34,12 @@ extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int gr
                                       const PreTab *pt);
 extern "C" hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                                         const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
-                                        long long stride, unsigned int *cnt, unsigned long long *total);
+                                        long long stride, unsigned int *cnt, unsigned long long *total, unsigned int *qcnt,
+                                        unsigned long long *qtot);
 extern "C" hipError_t mpp_prepass_fill(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                                        const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
-                                       long long stride, const unsigned int *off, uint32_t *word, double *rec);
+                                       long long stride, const unsigned int *off, uint32_t *word, double *rec,
+                                       const unsigned int *qcnt, uint32_t *qoff, QEnt *qent);
 extern "C" void mpp_launch_papangelou_tiles(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int cap,
                                             double *dE, const int32_t *grid_start, const int32_t *grid_items, int sstride, int istride);
 extern "C" void mpp_launch_grid_build_all(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int ncell,
@@ -131,6 +133,9 @@ struct mpp_ctx {
   // the birth pre-pass of a deep launch (mpp_prepass.hip): prepass 1 on, 0 off (the chains draw their births themselves);
   // a launch whose table would exceed prepass_mb MB runs without one; prepass_used: a deep launch of the last call used one
   int prepass = 1, prepass_mb = 256, prepass_used = 0;
+  // ... and with it the steps of every kernel type in queues (prepass_queues 1), from which the rounds of a chain of eight
+  // waves take their steps (the deep kernel's QUE instantiation); prepass_queues_used: a deep launch of the last call did
+  int prepass_queues = 1, prepass_queues_used = 0;
   unsigned char *pre_ws = nullptr;   // the table's total, block counts and step words
   size_t pre_ws_bytes = 0;
   double *pre_rec = nullptr;         // its birth records
@@ -368,6 +373,9 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     // (at most 16 GB: a birth's ordinal has 28 bits of its step word)
     if (v < 1 || v > 16384) return fail(c, -1, "prepass_mb must be in 1..16384");
     c->prepass_mb = (int)v;
+  } else if (!strcmp(name, "prepass_queues")) {
+    if (v < 0 || v > 1) return fail(c, -1, "prepass_queues must be 0 or 1");
+    c->prepass_queues = (int)v;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -401,6 +409,8 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "prepass")) return c->prepass;
   if (!strcmp(name, "prepass_mb")) return c->prepass_mb;
   if (!strcmp(name, "prepass_used")) return c->prepass_used;
+  if (!strcmp(name, "prepass_queues")) return c->prepass_queues;
+  if (!strcmp(name, "prepass_queues_used")) return c->prepass_queues_used;
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
@@ -1100,17 +1110,26 @@ static int ensure_birth_tables(mpp_ctx *c) {
 
 // The birth table of a deep launch (mpp_prepass.hip), on the launch's stream right before it: every chain of the launch,
 // every step it has left (at most n_steps).  pt->word stays nullptr -- the launch draws its births itself -- when the pre-pass
-// is off or the table would exceed prepass_mb.
+// is off or the table would exceed prepass_mb; pt->qoff stays nullptr -- births only -- when the queues would.
 static int build_prepass(mpp_ctx *c, const DevParams *P, const TileRef *tiles, int tile0, int n, const long long *until,
                          int64_t n_steps, uint64_t seed, uint32_t chain0, PreTab *pt) {
-  pt->word = nullptr; pt->rec = nullptr; pt->stride = 0;
+  *pt = PreTab{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
   if (!c->prepass || n <= 0 || n > 65535 || n_steps <= 0) return 0;       // (the chains are the grid's second dimension)
   const long long stride = n_steps;
   const int nblk = (int)((stride + PRE_BLOCK - 1) / PRE_BLOCK);
   const size_t budget = (size_t)c->prepass_mb << 20;
   const size_t cnt_off = 256, word_off = cnt_off + (((size_t)n * nblk * 4 + 255) & ~(size_t)255);
-  const size_t need = word_off + (size_t)n * stride * 4;
-  if (need > budget) return 0;
+  const size_t need_b = word_off + (size_t)n * stride * 4;
+  if (need_b > budget) return 0;
+  // the queues (mpp_prepass.hpp): only the deep kernel of eight waves with the cost deal reads them, and only the eight kernels
+  // without split / merge have one; offsets are 32-bit
+  const size_t qtot_off = (need_b + 255) & ~(size_t)255, qcnt_off = qtot_off + (((size_t)n * 8 + 255) & ~(size_t)255),
+               qoff_off = qcnt_off + (((size_t)n * MPP_NKERNEL * nblk * 4 + 255) & ~(size_t)255),
+               qent_off = qoff_off + (((size_t)n * stride * 4 + 255) & ~(size_t)255),
+               need_q = qent_off + (size_t)n * stride * sizeof(QEnt);
+  const bool queues = c->prepass_queues && c->spec == 8 && (c->deep_gain & 0x100) == 0 && P->n_kernels <= MPP_K_SPLIT &&
+                      stride < 0x7fffffffll && need_q <= budget;
+  const size_t need = queues ? need_q : need_b;
   if (need > c->pre_ws_bytes) {
     if (c->pre_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->pre_ws); }
     c->pre_ws = nullptr; c->pre_ws_bytes = 0;
@@ -1120,21 +1139,32 @@ static int build_prepass(mpp_ctx *c, const DevParams *P, const TileRef *tiles, i
   unsigned long long *total = (unsigned long long *)c->pre_ws;
   unsigned int *cnt = (unsigned int *)(c->pre_ws + cnt_off);
   uint32_t *word = (uint32_t *)(c->pre_ws + word_off);
-  HIPCHK(c, mpp_prepass_count(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, total));
+  unsigned long long *qtot = queues ? (unsigned long long *)(c->pre_ws + qtot_off) : nullptr;
+  unsigned int *qcnt = queues ? (unsigned int *)(c->pre_ws + qcnt_off) : nullptr;
+  uint32_t *qoff = queues ? (uint32_t *)(c->pre_ws + qoff_off) : nullptr;
+  QEnt *qent = queues ? (QEnt *)(c->pre_ws + qent_off) : nullptr;
+  HIPCHK(c, mpp_prepass_count(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, total, qcnt, qtot));
   unsigned long long births = 0;
   HIPCHK(c, hipMemcpyAsync(&births, total, sizeof births, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t rec_bytes = (size_t)births * PRE_REC_BYTES;
-  if (need + rec_bytes > budget) return 0;
+  // the queues and the birth records together over the budget: the births table alone may still fit (the queues' counts
+  // are then left unused)
+  const bool use_q = queues && need_q + rec_bytes <= budget;
+  if ((use_q ? need_q : need_b) + rec_bytes > budget) return 0;
+  if (!use_q) { qtot = nullptr; qcnt = nullptr; qoff = nullptr; qent = nullptr; }
   if (rec_bytes > c->pre_rec_bytes) {
     if (c->pre_rec) (void)hipFree(c->pre_rec);   // (the stream is idle: synchronised just above)
     c->pre_rec = nullptr; c->pre_rec_bytes = 0;
     HIPCHK(c, hipMalloc((void **)&c->pre_rec, rec_bytes));
     c->pre_rec_bytes = rec_bytes;
   }
-  HIPCHK(c, mpp_prepass_fill(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, word, c->pre_rec));
+  HIPCHK(c, mpp_prepass_fill(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, word, c->pre_rec, qcnt,
+                             qoff, qent));
   pt->word = word; pt->rec = c->pre_rec; pt->stride = stride;
+  pt->qoff = qoff; pt->qent = qent; pt->qcnt = qcnt; pt->qtot = qtot; pt->qnblk = nblk;
   c->prepass_used = 1;
+  if (use_q) c->prepass_queues_used = 1;
   return 0;
 }
 
@@ -1183,6 +1213,7 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
   c->last_ms = 0.0;
   c->hbm_chains = 0;
   c->prepass_used = 0;
+  c->prepass_queues_used = 0;
   if ((int)c->hbm_tile.size() != c->n_tiles) c->hbm_tile.assign(c->n_tiles, 0);
   // many chains in one launch: prefer the instantiation that lets two waves share a SIMD
   const int occ = (grid >= 1024) ? 2 : 1;
@@ -1292,7 +1323,7 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
       if (nmax > 0) {
         int fixed = c->deep_fixed > nmax ? nmax : c->deep_fixed;
         if (fixed > 0) { fixed = fixed / c->spec * c->spec; if (fixed < c->spec) fixed = c->spec; }
-        PreTab pt{nullptr, nullptr, 0};
+        PreTab pt{nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
         if (!ext_ && (rc = build_prepass(c, &lp, tiles_l, tile0_l, n_lds, until_l, n_steps, seed, chain0, &pt))) return rc;
         HIPCHK(c, mpp_launch_deep(c->stream, c->spec, occ, n_lds, lds, &lp, tiles_l, tile0_l, until_l, trace_base, seed, chain0,
                                   trace_l, d_out, d_props, nmax, fixed, c->deep_gain, c->deep_stats, ext_, &pt));

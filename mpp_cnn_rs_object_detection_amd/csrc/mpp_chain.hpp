@@ -26,6 +26,7 @@
 //    The chain is bit-for-bit the sequential one for every SPEC.
 #pragma once
 #include "mpp_device.hpp"
+#include "mpp_prepass.hpp"
 
 #define STASH 32              // neighbour updates remembered per speculative step
 #define MPP_LDS_PARAMS_MIN_WAVES 4   // chains with at least this many waves read the parameter block from an LDS copy
@@ -1354,6 +1355,9 @@ __device__ __forceinline__ void draw_birth(const Chain &c, const uint32_t w[8], 
 }
 // BIRTHS = false: the caller has the births from elsewhere (the deep kernel's pre-pass table, mpp_prepass.hip); a birth
 // step then only gets draw_head's fields, and the instantiation carries no birth draw
+// (draw_head_q / draw_tail_q below repeat the arithmetic of the steps with a target for the pre-pass queues, split into its
+// state-free and state-dependent parts: a change here must be made there too -- tests/test_gpu_prepass_queue.py compares
+// the two paths bit for bit)
 template <bool LANE, bool BIRTHS = true>
 __device__ __forceinline__ void draw_proposal(const Chain &c, const uint32_t w[8], int n, Rec &r, int *keep, uint32_t k0, uint32_t k1,
                               uint64_t step, uint32_t chain, MapVals *pmv) {
@@ -1416,6 +1420,72 @@ __device__ __forceinline__ void draw_proposal(const Chain &c, const uint32_t w[8
   // data-driven transform branch -- r.ax came out as 0 -- when the kernel grew; ROCm 7.2 hipcc)
   int fx = q.x, fy = q.y;
   asm volatile("" : "+v"(fx), "+v"(fy));
+  r.ax = fx; r.ay = fy; r.as = q.s; r.ar = q.r; r.aa = q.a;
+}
+
+// draw_proposal() in two parts for the steps of the pre-pass queues (mpp_prepass.hpp, the deep kernel's QUE instantiation):
+// the head depends on the step's Philox blocks 0 and 1 alone -- the pre-pass computes it for every step with a target (deaths,
+// translations, transforms) and keeps it in the step's queue entry -- the tail, in the lane form, finishes the proposal
+// against the configuration.  Together they run the operations of draw_proposal<true>() on the same values: the same bits.
+__device__ __forceinline__ void draw_head_q(const DevParams *P, int k, const uint32_t w[8], QEnt &e) {
+  e.w2 = w[2]; e.u_acc = u53(w[6], w[7]); e.a = 0.0; e.b = 0.0;
+  double z0 = 0.0, z1 = 0.0;
+  if (k == MPP_K_GTRANS || k == MPP_K_GTRANSF) box_muller(k == MPP_K_GTRANS ? w[3] : w[4], k == MPP_K_GTRANS ? w[4] : w[5], &z0, &z1);
+  if (k == MPP_K_GTRANS) {
+    e.a = P->kern.sigma_trans * z0; e.b = P->kern.sigma_trans * z1;
+  } else if (k == MPP_K_DTRANS) {
+    e.a = u53(w[3], w[4]);
+  } else if (k == MPP_K_GTRANSF) {
+    const int pid = (int)mulhi32(w[3], 3u);
+    e.a = P->kern.sigma_transform * (P->maps.vmax[pid] - P->maps.vmin[pid]) * z0; e.b = (double)pid;
+  } else if (k == MPP_K_DTRANSF) {
+    e.a = u32d(w[4]); e.b = (double)mulhi32(w[3], 3u);
+  }
+}
+__device__ __forceinline__ void draw_tail_q(const Chain &c, int k, const QEnt &e, int n, Rec &r, int *keep) {
+  const DevParams *P = c.P;
+  r.kernel = k; r.tidx = -1; r.tslot = -1; r.has_rem = 0; r.has_add = 0; r.pid = -1; r.ncls = -1; r.acls = 0; r._pad2 = 0;
+  r.aux0 = r.aux1 = 0.0; r.ax = r.ay = 0; r.as = r.ar = r.aa = 0.0; r.rx = r.ry = 0;
+  r.u_acc = e.u_acc;
+  *keep = 0;
+  if (n == 0) return;
+  r.tidx = (int)mulhi32(e.w2, (uint32_t)n);
+  r.tslot = c.L.order[r.tidx];
+  r.has_rem = 1;
+  Rect q = load_rect(c.L, r.tslot);
+  r.rx = q.x; r.ry = q.y;
+  if (k == MPP_K_UDEATH || k == MPP_K_DDEATH) return;
+  r.has_add = 1;
+  if (k == MPP_K_GTRANS) {
+    const double d0 = e.a, d1 = e.b;
+    int nx = (int)((double)q.x + d0), ny = (int)((double)q.y + d1);
+    q.x = min(max(nx, 0), c.h.H - 1); q.y = min(max(ny, 0), c.h.W - 1);
+    r.aux0 = d0; r.aux1 = d1;
+    *keep = KEEP_TRIG | KEEP_SIZE;
+  } else if (k == MPP_K_DTRANS) {
+    int ex, ey;
+    window_draw_lane(c, q.x, q.y, e.a, &ex, &ey);
+    q.x = ex; q.y = ey;
+    *keep = KEEP_TRIG | KEEP_SIZE;
+  } else if (k == MPP_K_GTRANSF) {
+    const int pid = (int)e.b;
+    const double d = e.a;
+    set_mark(q, pid, wrap_mark(P, pid, mark_of(q, pid) + d));
+    r.pid = pid; r.aux0 = d;
+    *keep = pid == 2 ? KEEP_SIZE : KEEP_TRIG;
+  } else {
+    const int pid = (int)e.b;
+    int cls;
+    const int oc = value_to_class_tab(P, c.L.edges + pid * MPP_NCLASS, pid, mark_of(q, pid));
+    double pb = 0.0;
+    r.qf = row_prob(c, pid, q.x, q.y, 0, true, e.a, &cls, oc, &pb);
+    r.qb = pb;
+    set_mark(q, pid, c.L.edges[pid * MPP_NCLASS + cls]);
+    r.pid = pid; r.ncls = cls; r.acls = cls;
+    *keep = (pid == 2 ? KEEP_SIZE : KEEP_TRIG) | KEEP_QFB | (pid == 2 ? KEEP_EDGE_ANGLE : 0);
+  }
+  int fx = q.x, fy = q.y;
+  asm volatile("" : "+v"(fx), "+v"(fy));     // (as in draw_proposal)
   r.ax = fx; r.ay = fy; r.as = q.s; r.ar = q.r; r.aa = q.a;
 }
 

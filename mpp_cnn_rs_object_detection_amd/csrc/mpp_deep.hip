@@ -672,10 +672,25 @@ __device__ __forceinline__ void deep_load_birth(const PreTab &pt, unsigned int o
   r.dE = 0.0; r.n_stash = 0; r.ra0 = r.ra1 = 0.0;
 }
 
+// (QUE) the queues a wave serves: queue a, and for wave 1 queue b (wave 1: the uniform birth, a, and the uniform death, b;
+// waves 4 and 5: the even and the odd entries of the data-driven translation's queue); ca / cb the position of the first
+// entry not committed yet, ea / eb the end of the queue -- positions in the chain's part (reg) of pt.qoff / pt.qent;
+// xa / xb the steps (offsets in the round) of my entries of queues a and b (or of the other parity), 0xffffffff past the end.
+// Empty in the other instantiations: their code is the one they had before the queues.
+template <bool Q> struct DeepQueues {};
+template <> struct DeepQueues<true> {
+  int qt_a, ca, ea, cb, eb;
+  size_t reg;
+  uint32_t xa, xb;
+};
+
 // EXT: the instantiation that knows the classic image energies (mpp_classics.hpp): every lane rasterises its own rectangle
 // TAB: the births come from the pre-pass table `pt` (mpp_prepass.hip; not with EXT), and with eight waves the sorted steps
 //      are dealt by cost
-template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB>
+// QUE: (with TAB, eight waves, the cost deal) every wave takes its steps from the pre-pass queues of its kernel types, in the
+//      same deal: no kernel type, no sort, no Philox block in the round (the round's window ends early where a wave would
+//      have more than 64 steps)
+template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false>
 __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
                                                                  const long long *until, long long trace_base,
                                                                  unsigned long long seed, unsigned int chain0, int trace_tile,
@@ -683,6 +698,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
                                                                  int fixed_depth, int gain8, unsigned long long *stats,
                                                                  PreTab pt) {
   static_assert(!(TAB && EXT), "the pre-pass table is built for the instantiations without classic image energies");
+  static_assert(!QUE || (TAB && WAVES == 8), "the queues are dealt to eight waves");
   const bool by_type = (gain8 & 0x100) == 0;      // (bit 8 of the gain word: deal the sorted steps in blocks instead -- A/B tests)
   gain8 &= 0xff;
   constexpr int NCH = DEEP_NMAX_LIMIT / 64;              // chunks of 64 step reports a lane may have to look at
@@ -788,6 +804,20 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   int myoff = 0, lim = 0, committed = 0, cur_n = n, nb0 = 0, nb1 = 0, nbr = 0, ring_todo = 0;
   long long ring_from = 0;
   double Tm = 0.0;
+  DeepQueues<QUE> qs;                           // (QUE) the wave's cursors into the queues
+  if constexpr (QUE) {
+    const int w = c.wave;
+    qs.qt_a = w == 0 ? MPP_K_DBIRTH : w == 1 ? MPP_K_UBIRTH : w == 2 ? MPP_K_DDEATH : w == 3 ? MPP_K_GTRANS
+            : w <= 5 ? MPP_K_DTRANS : w == 6 ? MPP_K_DTRANSF : MPP_K_GTRANSF;
+    const unsigned int *qc = pt.qcnt + (size_t)blockIdx.x * MPP_NKERNEL * pt.qnblk;
+    const int qend = (int)pt.qtot[blockIdx.x];
+    qs.ca = __builtin_amdgcn_readfirstlane((int)qc[(size_t)qs.qt_a * pt.qnblk]);
+    qs.ea = __builtin_amdgcn_readfirstlane(qs.qt_a + 1 < MPP_NKERNEL ? (int)qc[(size_t)(qs.qt_a + 1) * pt.qnblk] : qend);
+    qs.cb = __builtin_amdgcn_readfirstlane((int)qc[(size_t)MPP_K_UDEATH * pt.qnblk]);
+    qs.eb = __builtin_amdgcn_readfirstlane((int)qc[(size_t)(MPP_K_UDEATH + 1) * pt.qnblk]);
+    qs.reg = (size_t)blockIdx.x * (size_t)pt.stride;
+    qs.xa = qs.xb = 0xffffffffu;
+  }
   while (stage == 0 || (done < n_steps && err == 0)) {
     bool do_eval = my_commit && r.n_stash > 2;  // stage 0: the steps that commit and change more neighbours than they could note
     DPH_T0();
@@ -797,6 +827,72 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     const int Lw = N / WAVES;                   // active lanes per wave
     const long long left = n_steps - done;
     lim = left < (long long)N ? (int)left : N;
+    if constexpr (QUE) {
+      int kq = 0;                               // my kernel type
+      QEnt qe;                                  // my entry
+      qe.off = 0u; qe.w2 = 0u; qe.u_acc = 0.0; qe.a = 0.0; qe.b = 0.0;
+      // ---- A: my entries, and where the round's window must end for every wave to have at most 64 steps
+      const uint32_t d32 = (uint32_t)done;
+      const bool pair = c.wave == 4 || c.wave == 5;
+      const int ia = pair ? qs.ca + 2 * c.lane + (c.wave == 5 ? 1 : 0) : qs.ca + c.lane;
+      const int ib = pair ? qs.ca + 2 * c.lane + (c.wave == 5 ? 0 : 1) : qs.cb + c.lane;
+      qs.xa = ia < qs.ea ? pt.qoff[qs.reg + ia] - d32 : 0xffffffffu;
+      qs.xb = (pair || c.wave == 1) && ib < (pair ? qs.ea : qs.eb) ? pt.qoff[qs.reg + ib] - d32 : 0xffffffffu;
+      if (c.wave != 1 && ia < qs.ea) qe = pt.qent[qs.reg + ia];
+      uint32_t cut = (uint32_t)lim;
+      if (c.wave == 1) {
+        const uint32_t a63 = (uint32_t)__builtin_amdgcn_readlane((int)qs.xa, 63), b63 = (uint32_t)__builtin_amdgcn_readlane((int)qs.xb, 63);
+        if (a63 < cut) cut = a63 + 1u;
+        if (b63 < cut) cut = b63 + 1u;
+        if (__popcll(__ballot(qs.xa < cut)) + __popcll(__ballot(qs.xb < cut)) > WAVE) {       // (then 32 of each at most)
+          const uint32_t a32 = (uint32_t)__builtin_amdgcn_readlane((int)qs.xa, 32), b32 = (uint32_t)__builtin_amdgcn_readlane((int)qs.xb, 32);
+          cut = min(cut, min(a32, b32));
+        }
+      } else {
+        const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)(c.wave == 4 ? qs.xb : qs.xa), 63);   // (a pair: entry 127)
+        if (last < cut) cut = last + 1u;
+      }
+      if (c.lane == 0) D.tcnt[c.wave] = (unsigned short)cut;
+      DPH(0);
+      __syncthreads();                          // (1) also: the changes of the previous round are in place
+      DPH(1);
+      uint32_t lq = (uint32_t)lim;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) lq = min(lq, (uint32_t)D.tcnt[w]);
+      lim = (int)lq;
+      mine = qs.xa < lq;
+      kq = qs.qt_a;
+      myoff = (int)qs.xa;
+      if (c.wave == 1) {                        // lanes [0, na) the uniform births, [na, na + nb) the uniform deaths
+        const int na = __popcll(__ballot(qs.xa < lq)), nb = __popcll(__ballot(qs.xb < lq));
+        const int d = c.lane - na;
+        mine = c.lane < na + nb;
+        kq = c.lane < na ? MPP_K_UBIRTH : MPP_K_UDEATH;
+        const int iq = c.lane < na ? qs.ca + c.lane : qs.cb + d;
+        if (mine) { qe = pt.qent[qs.reg + iq]; myoff = (int)(qe.off - d32); }
+      }
+      if (!mine) myoff = 0;
+      DPH(2);
+      // ---- B: evaluate my step (the TAB path below, its head from the entry instead of Philox words)
+      r.valid = 0; r.kernel = 0; r.accepted = 0; r.has_rem = r.has_add = 0; r.tslot = -1; r.tidx = -1;
+      if (mine) {
+        Tm = D.tring[(int)((done + myoff) & (long long)rmask)];
+        r.valid = 1;
+        int keep = 0;
+        const bool pre_b = kq == MPP_K_UBIRTH || kq == MPP_K_DBIRTH;      // a birth: the table has it all
+        if (pre_b) deep_load_birth(pt, qe.w2, kq, r);
+        else draw_tail_q(c, kq, qe, n, r, &keep);
+        DPH(3);
+        if (r.valid && r.has_add && (r.ax < 0 || r.ax >= c.h.H || r.ay < 0 || r.ay >= c.h.W)) { r.valid = 0; r.kernel = -1; }
+        if (r.valid && !pre_b) {
+          const MapVals pmv{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
+          deep_add_geo(c, r, keep);
+          deep_pre<false>(c, r, keep, tracing, pmv, nullptr);
+        }
+      }
+      do_eval = mine && r.valid && (r.has_rem || r.has_add);
+      DPH(4);
+    } else {
     const bool act0 = c.lane < Lw;
     const int e = c.wave * Lw + c.lane;         // my offset when the types are computed, my sorted position afterwards
 
@@ -953,6 +1049,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     if (EXT && mine && r.valid) deep_pre<EXT>(c, r, keep_x, tracing, pmv_x, have_cpre ? &cpre : nullptr);
     do_eval = mine && r.valid && (r.has_rem || r.has_add);
     DPH(4);
+    }
     }
     // ---- the neighbours' part of dE (energy_graph.py:139-225) for all steps of the wave; stage 0 writes their cached
     //      reductions
@@ -1141,6 +1238,13 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       cur = wq + 1;
     }
 
+    if constexpr (QUE) {                        // the entries the round committed leave the queues
+      const uint32_t cm = (uint32_t)committed;
+      const int na = __popcll(__ballot(qs.xa < cm)), nb = __popcll(__ballot(qs.xb < cm));
+      if (c.wave == 1) { qs.ca += na; qs.cb += nb; }
+      else qs.ca += na + nb;                    // (nb: the other parity of a pair, 0 elsewhere)
+    }
+
     // ---- D: apply the committed changes
     my_commit = false;
     if (mine) {
@@ -1222,28 +1326,32 @@ extern "C" size_t mpp_deep_static_lds_bytes(int waves) {
   return waves >= MPP_LDS_PARAMS_MIN_WAVES ? ((sizeof(DevParams) + 15) & ~(size_t)15) : 0;
 }
 
-template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB>
+template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false>
 static hipError_t launch_deep_d(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
                                 const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
                                 int trace_tile, mpp_step_out *out, mpp_proposal *props, int nmax, int fixed_depth, int gain8,
                                 unsigned long long *stats, const PreTab &pt) {
-  hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB>,
+  hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
+  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
                      trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, pt);
   return hipGetLastError();
 }
 
 // waves = waves per chain (1, 2, 4, 8); nmax = most steps of one round (a power of two, waves <= nmax <= 64 * waves, <= 256);
 // ext: a classic image energy among the unit terms (built for 1 and 8 waves, like the one-wave-per-step kernels)
-// pt: the launch's birth table (mpp_prepass.hip), or pt->word == nullptr: the chains draw their births themselves
+// pt: the launch's birth table (mpp_prepass.hip), or pt->word == nullptr: the chains draw their births themselves; with
+// pt->qoff, eight waves and the cost deal (gain8 without bit 8), the rounds take their steps from the table's queues
 extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int grid, size_t lds, const DevParams *P,
                                       const TileRef *tiles, int tile0, const long long *until, long long trace_base,
                                       unsigned long long seed, unsigned int chain0, int trace_tile, mpp_step_out *out,
                                       mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext,
                                       const PreTab *pt) {
   const bool diag = out || props, tab = pt->word != nullptr && !ext;
+  if (tab && pt->qoff != nullptr && waves == 8 && (gain8 & 0x100) == 0)
+    return diag ? launch_deep_d<8, true, 2, false, true, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
+                : launch_deep_d<8, false, 2, false, true, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt);
 #define GO_(W, O, X, T)                                                                                                   \
   return diag ? launch_deep_d<W, true, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt) \
               : launch_deep_d<W, false, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)

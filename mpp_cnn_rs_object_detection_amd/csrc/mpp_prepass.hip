@@ -7,6 +7,9 @@
 //          deep_pre -- the very functions the deep kernel ran for a birth lane, so the record holds its bits.
 // The host reads the number of births back between scan and fill (the records' size; a table over the prepass_mb budget
 // is not built and the launch draws its births itself).
+// With the queues (qcnt / qoff non-null) count also counts every type per block, a second scan -- one workgroup per chain --
+// turns those counts into queue positions, and fill writes every step's queue entry: the head of its proposal
+// (draw_head_q), or, for a birth, its ordinal in the records.
 #include "mpp_chain.hpp"
 #include "mpp_prepass.hpp"
 
@@ -29,25 +32,33 @@ __device__ __forceinline__ bool is_birth(int kt) { return kt == MPP_K_UBIRTH || 
 __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_count_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
                                                                       const long long *until, unsigned long long seed,
                                                                       unsigned int chain0, int nblk, long long stride,
-                                                                      unsigned int *cnt) {
+                                                                      unsigned int *cnt, unsigned int *qcnt) {
   const int ch = blockIdx.y, tile = tile0 + ch;
   const TileRef t = tiles[tile];
   const long long rel = (long long)blockIdx.x * PRE_BLOCK + threadIdx.x, s = *t.step + rel;
-  bool birth = false;
+  int kt = 15;
   if (s < until[tile] && rel < stride) {
     uint32_t k0, k1, chain, w[4];
     pre_key(t, seed, chain0, tile, &k0, &k1, &chain);
     philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 0u, chain, k0, k1, w);
-    birth = is_birth(pre_type(&Pv, w[0], w[1]));
+    kt = pre_type(&Pv, w[0], w[1]);
   }
-  const int c = __syncthreads_count(birth);
+  const int c = __syncthreads_count(is_birth(kt));
   if (threadIdx.x == 0) cnt[(size_t)ch * nblk + blockIdx.x] = (unsigned int)c;
+  if (qcnt) {
+    for (int k = 0; k < MPP_NKERNEL; ++k) {
+      const int ck = __syncthreads_count(kt == k);
+      if (threadIdx.x == 0) qcnt[((size_t)ch * MPP_NKERNEL + k) * nblk + blockIdx.x] = (unsigned int)ck;
+    }
+  }
 }
 
-// in place: cnt[i] <- sum of cnt[0 .. i-1]; *total <- sum of all
+// in place: cnt[i] <- sum of cnt[0 .. i-1]; *total <- sum of all -- for each of the grid's segments of n counts
 __global__ __launch_bounds__(1024) void mpp_prepass_scan_kernel(unsigned int *cnt, long long n, unsigned long long *total) {
   __shared__ unsigned long long part[1024];
   const int tid = threadIdx.x;
+  cnt += (size_t)blockIdx.x * n;
+  total += blockIdx.x;
   unsigned long long carry = 0;
   for (long long i0 = 0; i0 < n; i0 += 1024) {
     const long long i = i0 + tid;
@@ -71,9 +82,11 @@ __global__ __launch_bounds__(1024) void mpp_prepass_scan_kernel(unsigned int *cn
 __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
                                                                      const long long *until, unsigned long long seed,
                                                                      unsigned int chain0, int nblk, long long stride,
-                                                                     const unsigned int *off, uint32_t *word, double *rec) {
+                                                                     const unsigned int *off, uint32_t *word, double *rec,
+                                                                     const unsigned int *qcnt, uint32_t *qoff, QEnt *qent) {
   __shared__ double s_edges[3 * MPP_NCLASS];
   __shared__ unsigned int s_wcnt[PRE_BLOCK / WAVE];
+  __shared__ unsigned int s_tcnt[PRE_BLOCK / WAVE][MPP_NKERNEL];
   const DevParams *P = &Pv;
   const int ch = blockIdx.y, tile = tile0 + ch, tid = threadIdx.x;
   for (int i = tid; i < 3 * MPP_NCLASS; i += PRE_BLOCK) s_edges[i] = P->maps.edges[i / MPP_NCLASS][i % MPP_NCLASS];
@@ -102,6 +115,32 @@ __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevPa
   unsigned int ord = off[(size_t)ch * nblk + blockIdx.x] + (unsigned int)__popcll(m & ((1ull << c.lane) - 1ull));
   for (int v = 0; v < c.wave; ++v) ord += s_wcnt[v];
   if (in) word[(size_t)ch * stride + rel] = (uint32_t)kt | (birth ? ord << 4 : 0u);
+  if (qoff) {
+    // my position in my type's queue: the block's first, then the waves before mine, then the lanes before mine
+    unsigned long long same = 0ull;
+    unsigned int cnt_lane = 0;
+#pragma unroll
+    for (int k = 0; k < MPP_NKERNEL; ++k) {
+      const unsigned long long mk = __ballot(kt == k);
+      if (kt == k) same = mk;
+      if (c.lane == k) cnt_lane = (unsigned int)__popcll(mk);
+    }
+    if (c.lane < MPP_NKERNEL) s_tcnt[c.wave][c.lane] = cnt_lane;
+    __syncthreads();
+    if (in) {
+      unsigned int pos = qcnt[((size_t)ch * MPP_NKERNEL + kt) * nblk + blockIdx.x] + (unsigned int)__popcll(same & ((1ull << c.lane) - 1ull));
+      for (int v = 0; v < c.wave; ++v) pos += s_tcnt[v][kt];
+      QEnt e;
+      e.off = (uint32_t)rel; e.w2 = ord; e.u_acc = 0.0; e.a = 0.0; e.b = 0.0;
+      if (!birth) {
+        philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 1u, chain, k0, k1, w + 4);
+        draw_head_q(P, kt, w, e);
+      }
+      const size_t at = (size_t)ch * stride + pos;
+      qoff[at] = (uint32_t)rel;
+      qent[at] = e;
+    }
+  }
   if (!birth) return;
   philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 1u, chain, k0, k1, w + 4);
   Rec r;
@@ -126,16 +165,19 @@ __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevPa
 // ---- host-side launchers ----------------------------------------------------------------------------
 extern "C" hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                                         const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
-                                        long long stride, unsigned int *cnt, unsigned long long *total) {
+                                        long long stride, unsigned int *cnt, unsigned long long *total, unsigned int *qcnt,
+                                        unsigned long long *qtot) {
   hipLaunchKernelGGL(mpp_prepass_count_kernel, dim3(nblk, n_chains), dim3(PRE_BLOCK), 0, st, *P, tiles, tile0, until, seed,
-                     chain0, nblk, stride, cnt);
+                     chain0, nblk, stride, cnt, qcnt);
   hipLaunchKernelGGL(mpp_prepass_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (long long)nblk * n_chains, total);
+  if (qcnt) hipLaunchKernelGGL(mpp_prepass_scan_kernel, dim3(n_chains), dim3(1024), 0, st, qcnt, (long long)nblk * MPP_NKERNEL, qtot);
   return hipGetLastError();
 }
 extern "C" hipError_t mpp_prepass_fill(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                                        const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
-                                       long long stride, const unsigned int *off, uint32_t *word, double *rec) {
+                                       long long stride, const unsigned int *off, uint32_t *word, double *rec,
+                                       const unsigned int *qcnt, uint32_t *qoff, QEnt *qent) {
   hipLaunchKernelGGL(mpp_prepass_fill_kernel, dim3(nblk, n_chains), dim3(PRE_BLOCK), 0, st, *P, tiles, tile0, until, seed,
-                     chain0, nblk, stride, off, word, rec);
+                     chain0, nblk, stride, off, word, rec, qcnt, qoff, qent);
   return hipGetLastError();
 }

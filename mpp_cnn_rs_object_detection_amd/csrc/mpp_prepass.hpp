@@ -14,10 +14,31 @@
 // and per birth (ordinal, over all chains of the launch) PRE_REC_DOUBLES values, six 16-byte pairs:
 //   (u_acc, qf) (as, ar) (aa, lin_a) (hl, hw) (ca, sa) (rad, bits: ax | ay << 16 | (gate_a) << 32)
 // (qb of a birth is always 1: proposal_densities() sets it so for both births)
+//
+// With the queues (option prepass_queues, 8 waves, mpp_deep.hip's QUE instantiation) the pre-pass also sorts every chain's
+// steps by kernel type, in step order within a type -- one queue per type -- so that a deep round finds its steps without
+// computing a single type:
+//   qcnt[(chain * MPP_NKERNEL + t) * nblk + b]  (scanned, per chain) the queue position of the first type-t step of block b:
+//                                               qcnt[(chain * MPP_NKERNEL + t) * nblk] is where queue t starts, qtot[chain]
+//                                               where the last one ends
+//   qoff[chain * stride + p]                    the step (s - step0) at queue position p
+//   qent[chain * stride + p]                    what of that step does not depend on the configuration (QEnt)
+struct QEnt {
+  uint32_t off;                // s - step0
+  uint32_t w2;                 // Philox word 2 (the target: mulhi32(w2, n)); a birth: its ordinal in `rec`
+  double u_acc;                // the accept test's uniform (births: in their record)
+  double a, b;                 // the kernel's own draw: Gaussian translation sigma * (z0, z1); data-driven translation
+                               // u53(w3, w4); Gaussian transform the mark offset and pid; data-driven transform u32d(w4) and pid
+};
 struct PreTab {
   const uint32_t *word;
   const double *rec;
   long long stride;
+  const uint32_t *qoff;        // nullptr: no queues
+  const QEnt *qent;
+  const unsigned int *qcnt;
+  const unsigned long long *qtot;
+  int qnblk;
 };
 #define PRE_REC_DOUBLES 12
 #define PRE_REC_BYTES (PRE_REC_DOUBLES * 8)
