@@ -345,6 +345,81 @@ int mpp_detect_centers(mpp_ctx *ctx, int H, int W, int ld, const float *det, dou
 int mpp_mark_classes(mpp_ctx *ctx, int H, int W, int ld, const float *m0, const float *m1, const float *m2, int n,
                      const int32_t *xy, int32_t *classes);
 
+/* ---- training the U-Nets (csrc/mpp_train.hip) ------------------------------------------------------------------------
+ * The training images of a dataset, resident on the device: images uint8 [H][W][3] back to back (img_off[i] bytes from
+ * images, img_hw[i] = {H, W}); the objects of image i are rows obj_start[i] .. obj_start[i+1]-1 of centers [n][2] int32
+ * (row, col) and params [n][3] float64 (a, b, angle), in annotation order.  All device pointers. */
+typedef struct mpp_train_data {
+  const uint8_t *images;
+  const int64_t *img_off;
+  const int32_t *img_hw;
+  const int32_t *obj_start;
+  const int32_t *centers;
+  const double *params;
+  int32_t n_images;
+  int32_t _pad;
+} mpp_train_data;
+/* What the labels are made of.  kind 0: PosNet (models/position_net/data_loaders.py:23-118, target uvec or vec, a numeric
+ * max_distance, sigma_dil); kind 1: ShapeNet (models/shape_net/data_loaders.py:41-118, mask_mode shapes) with the three
+ * value mappings: n_classes <= 32 lower bin edges per mark, cyclic[k] for the angle. */
+typedef struct mpp_train_labels {
+  int32_t kind;
+  int32_t uvec;
+  double max_distance;
+  double sigma_dil;
+  int32_t n_classes;
+  int32_t cyclic[3];
+  double edges[3][MPP_NCLASS];
+} mpp_train_labels;
+/* Outputs of mpp_train_batch, device pointers (NULL: not written, except patch and sums).  nb = ceil(P / MPP_TRAIN_BAND).
+ *  patch [B][3][P][P] float32 (value / 255);
+ *  PosNet: vec [B][2][P][P], mask [B][P][P], dil (center_binary_map_dil) [B][P][P], dist (distance to the nearest centre)
+ *  [B][P][P], all float32;  ShapeNet: cls [3][B][P][P] uint8 (value_class_map), cover [B][P][P] uint8 (the union of the
+ *  object masks; loss_mask = cover / sum of the patch's cover);
+ *  sums [B][nb][2] float64: per row band of a patch, the count of mask (PosNet) or cover (ShapeNet) pixels and the sum of
+ *  dil (PosNet);  status [1] int32: the largest object count of a patch that exceeded MPP_TRAIN_MAX_OBJ (0: none). */
+typedef struct mpp_train_out {
+  float *patch;
+  float *vec;
+  float *mask;
+  float *dil;
+  float *dist;
+  uint8_t *cls;
+  uint8_t *cover;
+  double *sums;
+  int32_t *status;
+} mpp_train_out;
+#define MPP_TRAIN_BAND 16          /* rows of a patch per workgroup of mpp_train_batch */
+#define MPP_TRAIN_MAX_OBJ 1024     /* objects of one patch held in LDS */
+#define MPP_TRAIN_MAX_P 1024
+enum {
+  MPP_AUG_GEOMETRIC = 1,           /* D4: rotation by k*90 deg (p 0.5), then a vertical / horizontal / both flip (p 0.5) */
+  MPP_AUG_MEDIUM = 2,              /* photometric part of data/augmentation.py:22-40 that is one formula per op */
+  MPP_AUG_STRONG = 4,              /* ... of :43-72 */
+  MPP_AUG_PERTURB = 8              /* ShapeNet: class perturbation {0: 0.8, +1: 0.1, -1: 0.1} per object and mark */
+};
+/* One batch of B patches of P x P (P even, 8..MPP_TRAIN_MAX_P) from the resident images: desc [B][3] int32 = (image, anchor
+ * row, anchor col) device array; the patch is the read at anchor - P/2 with zeros outside the image (utils/images.py:4-23),
+ * its objects those with anchor - P/2 <= centre < anchor - P/2 + P (data/patch_dataset.py:41-89).  flags: MPP_AUG_*.  Every
+ * random draw is Philox4x32-10 with key (seed, epoch) and counter (batch, patch, stream, index): the same arguments give
+ * the same batch bit for bit.  One launch on the ctx's stream (asynchronous).  -1: bad arguments. */
+int mpp_train_batch(mpp_ctx *ctx, const mpp_train_data *data, const mpp_train_labels *labels, int B, int P,
+                    const int32_t *desc, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, const mpp_train_out *out);
+/* PointingVectorLoss (model_parts/losses/pos_loss.py:36-115; learn_mask, compute_relevant, balanced_mask_loss,
+ * vec_loss_on_prod, no focal loss) of out [B][3][P][P] float32 against vec / mask / dil of mpp_train_batch.  with_div 1
+ * (training, pos_net_model.py:116-138): also the divergence classifier conv(div(out[:, :2]) * sigmoid(out[:, 2]); w, b)
+ * against dil, w and b float32 device scalars.  res [8] float64 (device): vec_loss, mask_loss, div_loss, loss, dL/dw,
+ * dL/db; grad [B][3][P][P] float32 = dL/dout (NULL: losses only).  One launch on the ctx's stream (asynchronous). */
+int mpp_posnet_loss(mpp_ctx *ctx, int B, int P, const float *out, const float *vec, const float *mask, const float *dil,
+                    const double *sums, int with_div, const float *w, const float *b, float *grad, double *res);
+/* PixelCELoss (model_parts/losses/pixel_ce_loss.py:20-57, no focal loss) of the three heads l0..l2 [B][n_classes][P][P]
+ * float32 against cls / cover / sums of mpp_train_batch: per head the cross-entropy times loss_mask summed over the
+ * pixels, averaged over the batch (float64 sums).  res [8] float64 (device): loss_feat0..2, loss; g0..g2 = dL/dlogits
+ * (NULL: losses only).  One launch on the ctx's stream (asynchronous). */
+int mpp_shapenet_loss(mpp_ctx *ctx, int B, int P, int n_classes, const float *l0, const float *l1, const float *l2,
+                      const uint8_t *cls, const uint8_t *cover, const double *sums, float *g0, float *g1, float *g2,
+                      double *res);
+
 void mpp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 int mpp_abi_version(void);
 

@@ -6,8 +6,8 @@
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
 hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the CNN-only baseline's detections (DOTA hbb /
 obb files), ``-p eval`` scores those.  ``-p train -m mpp`` learns the
-energy weights (manual / ordering / integral criterion) and calibrates; the training loops of the two
-U-Nets are outside this build.  With ``torchrun --nproc-per-node N`` the images of the dataset are
+energy weights (manual / ordering / integral criterion) and calibrates; ``-p train -m posnet|shapenet`` trains the two
+U-Nets on one GPU (batches built and losses computed by HIP kernels, ``unet_training.train_unet``).  With ``torchrun --nproc-per-node N`` the images of the dataset are
 dealt to N GPUs (one gather of the results at the end; RCCL).
 """
 import argparse
@@ -42,6 +42,12 @@ def main():
         config = json.load(f)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     overwrite_results = args.overwrite and args.procedure != "train"
+
+    if args.procedure == "train" and args.model in ("posnet", "shapenet"):
+        from mpp_cnn_rs_object_detection_amd.unet_training import train_unet
+        train_unet(config, args.model, dataset=args.dataset, device=local_rank, overwrite=args.overwrite, resume=args.resume)
+        print("done !")
+        return
 
     if args.model == "mpp":
         from mpp_cnn_rs_object_detection_amd.mpp_model import MPPModel

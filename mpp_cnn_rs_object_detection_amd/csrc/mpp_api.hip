@@ -11,6 +11,7 @@
 #include "mpp_device.hpp"
 #include "mpp_prepass.hpp"
 #include "mpp_detect.hpp"
+#include "mpp_train.hpp"
 
 extern "C" size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 extern "C" size_t mpp_chain_static_lds_bytes(int waves);
@@ -176,6 +177,7 @@ struct mpp_ctx {
   int32_t *g_start = nullptr, *g_cursor = nullptr, *g_items = nullptr;
   int g_cells = 0, g_cap = 0, grid_min_points = 256;
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
+  TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
 };
 
 static int fail(mpp_ctx *c, int code, const char *fmt, ...) {
@@ -291,6 +293,7 @@ extern "C" int mpp_destroy(mpp_ctx *c) {
   if (c->d_route) (void)hipFree(c->d_route);
   if (c->d_route_until) (void)hipFree(c->d_route_until);
   mpp_detect_free(&c->detect);
+  mpp_train_ws_free(&c->train);
   if (c->dp) (void)hipFree(c->dp);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1591,6 +1594,48 @@ extern "C" int mpp_mark_classes(mpp_ctx *c, int H, int W, int ld, const float *m
   HIPCHK(c, hipSetDevice(c->device));
   mpp_launch_mark_classes(c->stream, H, W, ld, m0, m1, m2, n, xy, classes);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// ---- training the U-Nets (mpp_train.hip) ----------------------------------------------------------------------------
+extern "C" int mpp_train_batch(mpp_ctx *c, const mpp_train_data *data, const mpp_train_labels *labels, int B, int P,
+                               const int32_t *desc, int flags, uint32_t seed, uint32_t epoch, uint32_t batch,
+                               const mpp_train_out *out) {
+  if (!c || !data || !labels || !out || !desc || !out->patch || !out->sums || !out->status)
+    return fail(c, -1, "train_batch: missing arguments");
+  if (B <= 0 || B > 65535 || P < 8 || P > MPP_TRAIN_MAX_P || (P & 1)) return fail(c, -1, "train_batch: bad shape B=%d P=%d", B, P);
+  if (data->n_images <= 0 || !data->images || !data->img_off || !data->img_hw || !data->obj_start || !data->centers ||
+      !data->params)
+    return fail(c, -1, "train_batch: no resident dataset");
+  if (labels->kind == 0) {
+    if (!(labels->sigma_dil > 0.0) || !(labels->max_distance >= 0.0)) return fail(c, -1, "train_batch: bad PosNet options");
+  } else if (labels->kind == 1) {
+    if (labels->n_classes < 1 || labels->n_classes > MPP_NCLASS) return fail(c, -1, "train_batch: n_classes must be in 1..32");
+  } else {
+    return fail(c, -1, "train_batch: kind must be 0 (PosNet) or 1 (ShapeNet)");
+  }
+  if (flags & ~(MPP_AUG_GEOMETRIC | MPP_AUG_MEDIUM | MPP_AUG_STRONG | MPP_AUG_PERTURB)) return fail(c, -1, "train_batch: bad flags");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_train_batch(c->stream, *data, *labels, B, P, desc, flags, seed, epoch, batch, *out));
+  return 0;
+}
+extern "C" int mpp_posnet_loss(mpp_ctx *c, int B, int P, const float *out, const float *vec, const float *mask, const float *dil,
+                               const double *sums, int with_div, const float *w, const float *b, float *grad, double *res) {
+  if (!c || !out || !vec || !mask || !sums || !res || (with_div && (!dil || !w || !b)))
+    return fail(c, -1, "posnet_loss: missing arguments");
+  if (B <= 0 || B > 65535 || P < 3 || P > MPP_TRAIN_MAX_P) return fail(c, -1, "posnet_loss: bad shape B=%d P=%d", B, P);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_posnet_loss(c->stream, &c->train, B, P, out, vec, mask, dil, sums, with_div ? 1 : 0, w, b, grad, res));
+  return 0;
+}
+extern "C" int mpp_shapenet_loss(mpp_ctx *c, int B, int P, int n_classes, const float *l0, const float *l1, const float *l2,
+                                 const uint8_t *cls, const uint8_t *cover, const double *sums, float *g0, float *g1, float *g2,
+                                 double *res) {
+  if (!c || !l0 || !l1 || !l2 || !cls || !cover || !sums || !res || (!g0 != !g1) || (!g1 != !g2))
+    return fail(c, -1, "shapenet_loss: missing arguments");
+  if (B <= 0 || B > 65535 || P < 1 || P > MPP_TRAIN_MAX_P || n_classes < 1 || n_classes > MPP_NCLASS)
+    return fail(c, -1, "shapenet_loss: bad shape B=%d P=%d n_classes=%d", B, P, n_classes);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_shapenet_loss(c->stream, &c->train, B, P, n_classes, l0, l1, l2, cls, cover, sums, g0, g1, g2, res));
   return 0;
 }
 extern "C" int mpp_shapenet_epilogue(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *logits, float *marks) {

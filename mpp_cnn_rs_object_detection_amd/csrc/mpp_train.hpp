@@ -1,0 +1,29 @@
+// mpp_train.hpp -- training the U-Nets (csrc/mpp_train.hip): the batch builder (crop, augmentation, labels) and the two
+// fused losses with their gradients.  Host-side launchers; the C entries (mpp_train_batch, mpp_posnet_loss,
+// mpp_shapenet_loss) are thin wrappers in mpp_api.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/mpp_hip.h"
+
+// device workspace of the loss kernels, kept by the ctx between calls (grown, never shrunk)
+struct TrainWs {
+  double *part = nullptr;            // [workgroups][8] partial sums of one loss launch
+  size_t part_count = 0;
+  unsigned *done = nullptr;          // workgroups finished; the last one reduces the partials and resets it to 0
+};
+
+hipError_t mpp_train_ws_reserve(TrainWs *ws, size_t workgroups);
+void mpp_train_ws_free(TrainWs *ws);
+hipError_t mpp_launch_train_batch(hipStream_t st, const mpp_train_data &data, const mpp_train_labels &labels, int B, int P,
+                                  const int32_t *desc, int flags, uint32_t seed, uint32_t epoch, uint32_t batch,
+                                  const mpp_train_out &out);
+hipError_t mpp_launch_posnet_loss(hipStream_t st, TrainWs *ws, int B, int P, const float *out, const float *vec,
+                                  const float *mask, const float *dil, const double *sums, int with_div, const float *w,
+                                  const float *b, float *grad, double *res);
+hipError_t mpp_launch_shapenet_loss(hipStream_t st, TrainWs *ws, int B, int P, int n_classes, const float *l0,
+                                    const float *l1, const float *l2, const uint8_t *cls, const uint8_t *cover,
+                                    const double *sums, float *g0, float *g1, float *g2, double *res);

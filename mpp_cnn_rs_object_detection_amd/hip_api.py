@@ -27,7 +27,8 @@ ABI_SYMBOLS = [
     "mpp_count", "mpp_get_points_all", "mpp_pack_detections", "mpp_total_energy", "mpp_delta_batch", "mpp_delta_vectors", "mpp_papangelou", "mpp_merge_score", "mpp_naive_init", "mpp_set_schedule",
     "mpp_replay", "mpp_run", "mpp_set_chain_keys", "mpp_step_index", "mpp_last_kernel_ms", "mpp_posnet_epilogue",
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
-    "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_philox4x32", "mpp_abi_version",
+    "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
+    "mpp_abi_version",
 ]
 
 
@@ -54,6 +55,28 @@ class MappingsC(C.Structure):
 class KernelsC(C.Structure):
     _fields_ = [("p_kernel", C.c_double * NKERNEL), ("sigma_trans", C.c_double), ("sigma_transform", C.c_double),
                 ("max_delta", C.c_int32), ("_pad", C.c_int32), ("split_radius", C.c_double), ("split_sigma", C.c_double)]
+
+
+class TrainDataC(C.Structure):
+    """mpp_train_data: the resident training images and their object tables (device pointers)"""
+    _fields_ = [("images", C.c_void_p), ("img_off", C.c_void_p), ("img_hw", C.c_void_p), ("obj_start", C.c_void_p),
+                ("centers", C.c_void_p), ("params", C.c_void_p), ("n_images", C.c_int32), ("_pad", C.c_int32)]
+
+
+class TrainLabelsC(C.Structure):
+    """mpp_train_labels: kind 0 PosNet (uvec, max_distance, sigma_dil), 1 ShapeNet (n_classes, cyclic, lower bin edges)"""
+    _fields_ = [("kind", C.c_int32), ("uvec", C.c_int32), ("max_distance", C.c_double), ("sigma_dil", C.c_double),
+                ("n_classes", C.c_int32), ("cyclic", C.c_int32 * 3), ("edges", (C.c_double * NCLASS) * 3)]
+
+
+class TrainOutC(C.Structure):
+    """mpp_train_out: device pointers of the batch builder's outputs (None: not written)"""
+    _fields_ = [(k, C.c_void_p) for k in ("patch", "vec", "mask", "dil", "dist", "cls", "cover", "sums", "status")]
+
+
+#: mpp_train_batch flags (include/mpp_hip.h MPP_AUG_*) and its geometry
+AUG_GEOMETRIC, AUG_MEDIUM, AUG_STRONG, AUG_PERTURB = 1, 2, 4, 8
+TRAIN_BAND, TRAIN_MAX_OBJ = 16, 1024
 
 
 PROPOSAL_DTYPE = np.dtype([("kernel", "<i4"), ("target", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -142,6 +165,10 @@ def load_library(path: Optional[str] = None):
         "mpp_quad_iou": (i32, [vp, i32, vp, i32, vp, vp, i32]),
         "mpp_detect_centers": (i32, [vp, i32, i32, i32, vp, dbl, i32, dbl, i32, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "mpp_mark_classes": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
+        "mpp_train_batch": (i32, [vp, C.POINTER(TrainDataC), C.POINTER(TrainLabelsC), i32, i32, vp, i32, C.c_uint32, C.c_uint32,
+                                  C.c_uint32, C.POINTER(TrainOutC)]),
+        "mpp_posnet_loss": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+        "mpp_shapenet_loss": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mpp_philox4x32": (None, [vp, vp, vp]),
         "mpp_abi_version": (i32, []),
     }
@@ -629,6 +656,42 @@ class MppContext:
         h, wd, ld = views[0]
         self._check(self._L.mpp_shapenet_heads_win(self._h, H, W, ldh, ldw, _ptr(hid), _ptr(w), _ptr(b), int(wx0), int(wy0), h, wd,
                                                    _ptr(marks_win[0]), _ptr(marks_win[1]), _ptr(marks_win[2]), ld))
+
+    # -- training the U-Nets (device tensors; asynchronous on the ctx's stream) -----------------------------------------
+    def train_batch(self, data: TrainDataC, labels: TrainLabelsC, desc, P: int, flags: int, seed: int, epoch: int, batch: int,
+                    out: dict):
+        """``mpp_train_batch``: desc [B,3] int32 CUDA tensor (image, anchor row, anchor col); out: CUDA tensors by field name of
+        ``TrainOutC`` (patch, sums and status required)."""
+        import torch
+        if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 3 or not desc.is_contiguous() or not desc.is_cuda:
+            raise ValueError("desc must be a contiguous [B,3] int32 CUDA tensor")
+        B = int(desc.shape[0])
+        want = {"patch": (torch.float32, (B, 3, P, P)), "vec": (torch.float32, (B, 2, P, P)), "mask": (torch.float32, (B, P, P)),
+                "dil": (torch.float32, (B, P, P)), "dist": (torch.float32, (B, P, P)), "cls": (torch.uint8, (3, B, P, P)),
+                "cover": (torch.uint8, (B, P, P)), "sums": (torch.float64, (B, (P + TRAIN_BAND - 1) // TRAIN_BAND, 2)),
+                "status": (torch.int32, (1,))}
+        o = TrainOutC()
+        for k, t in out.items():
+            dt, shape = want[k]
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"train_batch: {k} must be a contiguous {dt} CUDA tensor of shape {shape}")
+            setattr(o, k, t.data_ptr())
+        self._check(self._L.mpp_train_batch(self._h, C.byref(data), C.byref(labels), B, int(P), _ptr(desc), int(flags),
+                                            int(seed) & 0xffffffff, int(epoch) & 0xffffffff, int(batch) & 0xffffffff, C.byref(o)))
+
+    def posnet_loss(self, out, vec, mask, dil, sums, res, grad=None, w=None, b=None):
+        """``mpp_posnet_loss``: with w and b (float32 CUDA scalars) the training form with the divergence classifier"""
+        B, P = int(out.shape[0]), int(out.shape[-1])
+        with_div = w is not None
+        self._check(self._L.mpp_posnet_loss(self._h, B, P, _ptr(out), _ptr(vec), _ptr(mask), _ptr(dil), _ptr(sums), int(with_div),
+                                            _ptr(w), _ptr(b), _ptr(grad), _ptr(res)))
+
+    def shapenet_loss(self, logits, cls, cover, sums, res, grads=None):
+        """``mpp_shapenet_loss``: logits three [B,n,P,P] float32 CUDA tensors; grads three of the same shape or None"""
+        B, nc, P = int(logits[0].shape[0]), int(logits[0].shape[1]), int(logits[0].shape[-1])
+        g = list(grads) if grads is not None else [None, None, None]
+        self._check(self._L.mpp_shapenet_loss(self._h, B, P, nc, _ptr(logits[0]), _ptr(logits[1]), _ptr(logits[2]), _ptr(cls),
+                                              _ptr(cover), _ptr(sums), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(res)))
 
     # -- evaluation --------------------------------------------------------------------------------
     def quad_iou(self, a, b) -> np.ndarray:

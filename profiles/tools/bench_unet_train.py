@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""U-Net training throughput at the shipped configs (B = 64, P = 128, hidden 32..256) on a synthetic dataset:
+
+* patches/s of whole training steps (batch build, forward, loss, backward, Adam), each timed window ending in a device sync;
+* one step split by device events: batch build, forward, loss, backward, Adam;
+* A/B in the same process: the same step with the losses written as plain torch ops (pos_loss.py / pixel_ce_loss.py).
+
+    python profiles/tools/bench_unet_train.py [--steps 20] [--warmup 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from mpp_cnn_rs_object_detection_amd import hip_api, shapes, synth, unet  # noqa: E402
+from mpp_cnn_rs_object_detection_amd import unet_training as ut  # noqa: E402
+
+B, P = 64, 128
+
+
+def torch_pos(out, lab, conv):
+    eps = 1e-5
+    s = torch.sigmoid(out[:, 2])
+    vec_loss = torch.mean(torch.square(out[:, :2] * torch.stack([s, s], 1) - lab["vec"]))
+    m, d = lab["mask"], lab["dil"]
+    beta = 1 - torch.sum(m) / m.numel()
+    mask_loss = torch.mean(-beta * m * torch.log(s + eps) - (1 - beta) * (1 - m) * torch.log(1 - s + eps))
+    div = torch.gradient(out[:, 0], dim=1)[0] + torch.gradient(out[:, 1], dim=2)[0]
+    q = torch.sigmoid(conv(torch.unsqueeze(div * s, 1)))[:, 0]
+    beta_d = 1 - torch.sum(d) / d.numel()
+    div_loss = torch.mean(-beta_d * d * torch.log(q + eps) - (1 - beta_d) * (1 - d) * torch.log(1 - q + eps))
+    return vec_loss + mask_loss + div_loss
+
+
+def torch_shape(logits, lab):
+    cover = lab["cover"].double()
+    cnt = cover.sum((1, 2), keepdim=True)
+    lm = torch.where(cnt > 0, cover / cnt.clamp(min=1), torch.zeros_like(cover))
+    loss = 0
+    for h in range(3):
+        ce = torch.nn.functional.cross_entropy(logits[h], lab["cls"][h].long(), reduction="none")
+        loss = loss + torch.mean(torch.sum(ce * lm, dim=(1, 2)))
+    return loss
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    imgs, cs, ps = [], [], []
+    for k in range(4):
+        img, xy, marks = synth.make_scene_image((512, 512), 900, seed=k)
+        imgs.append((img * 255).astype(np.uint8))
+        cs.append(xy)
+        ps.append(np.stack(shapes.sra_to_wla(marks[:, 0], marks[:, 1], marks[:, 2]), 1))
+    data = ut.ResidentSubset.from_arrays(imgs, cs, ps, 0)
+    mctx = hip_api.MppContext(0)
+    mctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    rng = np.random.default_rng(0)
+    desc = torch.tensor(np.stack([rng.integers(0, 4, B), rng.integers(0, 512, B), rng.integers(0, 512, B)], 1).astype(np.int32),
+                        device="cuda")
+    results = {}
+    for kind in ("posnet", "shapenet"):
+        cfg = ut.shipped_config(kind)
+        bld = ut.BatchBuilder(mctx, ut.labels_struct(cfg, kind), P, 0)
+        flags = ut.aug_flags(cfg, kind)
+        net = (unet.PosNet() if kind == "posnet" else unet.ShapeNet()).cuda().train()
+        conv = torch.nn.Conv2d(1, 1, 1).cuda()
+        opt = torch.optim.Adam(list(net.parameters()) + list(conv.parameters()), lr=1e-3)
+        for fused in (True, False):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+            split = np.zeros(5)
+
+            def step(i, timed):
+                if timed:
+                    ev[0].record()
+                lab = bld.build(data, desc, flags, 42, 0, i)
+                if timed:
+                    ev[1].record()
+                out = net(lab["patch"])
+                if timed:
+                    ev[2].record()
+                if kind == "posnet":
+                    loss = ut.posnet_loss(mctx, out, lab, conv)["loss"] if fused else torch_pos(out, lab, conv)
+                else:
+                    loss = ut.shapenet_loss(mctx, out, lab)["loss"] if fused else torch_shape(out, lab)
+                if timed:
+                    ev[3].record()
+                opt.zero_grad()
+                loss.backward()
+                if timed:
+                    ev[4].record()
+                opt.step()
+                if timed:
+                    ev[5].record()
+            for i in range(args.warmup):
+                step(i, False)
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for i in range(args.steps):
+                step(i, False)
+            t1.record()
+            torch.cuda.synchronize()
+            ms = t0.elapsed_time(t1) / args.steps
+            for i in range(5):
+                step(i, True)
+                torch.cuda.synchronize()
+                split += [ev[q].elapsed_time(ev[q + 1]) for q in range(5)]
+            split /= 5
+            name = f"{kind}_{'fused' if fused else 'torch_losses'}"
+            results[name] = {"ms_per_step": ms, "patches_per_s": B / ms * 1e3,
+                             "split_ms": dict(zip(["batch_build", "forward", "loss", "backward", "adam"], split.round(3).tolist()))}
+            print(json.dumps({name: results[name]}), flush=True)
+    bld.check()
+    mctx.close()
+
+
+if __name__ == "__main__":
+    main()
