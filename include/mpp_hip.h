@@ -396,7 +396,9 @@ enum {
   MPP_AUG_GEOMETRIC = 1,           /* D4: rotation by k*90 deg (p 0.5), then a vertical / horizontal / both flip (p 0.5) */
   MPP_AUG_MEDIUM = 2,              /* photometric part of data/augmentation.py:22-40 that is one formula per op */
   MPP_AUG_STRONG = 4,              /* ... of :43-72 */
-  MPP_AUG_PERTURB = 8              /* ShapeNet: class perturbation {0: 0.8, +1: 0.1, -1: 0.1} per object and mark */
+  MPP_AUG_PERTURB = 8,             /* ShapeNet: class perturbation {0: 0.8, +1: 0.1, -1: 0.1} per object and mark */
+  MPP_AUG_HISTMATCH = 16           /* histogram matching to a random image of the subset (p 0.5), blended with U(0.1, 0.75);
+                                      needs mpp_train_set_histograms */
 };
 /* One batch of B patches of P x P (P even, 8..MPP_TRAIN_MAX_P) from the resident images: desc [B][3] int32 = (image, anchor
  * row, anchor col) device array; the patch is the read at anchor - P/2 with zeros outside the image (utils/images.py:4-23),
@@ -419,6 +421,46 @@ int mpp_posnet_loss(mpp_ctx *ctx, int B, int P, const float *out, const float *v
 int mpp_shapenet_loss(mpp_ctx *ctx, int B, int P, int n_classes, const float *l0, const float *l1, const float *l2,
                       const uint8_t *cls, const uint8_t *cover, const double *sums, float *g0, float *g1, float *g2,
                       double *res);
+
+
+/* ---- histogram matching and error-density resampling (csrc/mpp_train.hip, csrc/mpp_resample.hip) ---------------------
+ * MPP_AUG_HISTMATCH is skimage's match_histograms per channel on the 8-bit values of the P x P crop (its zero padding
+ * included) against the full-resolution histogram of a template image of the same subset:
+ *   src_q = cumsum(bincount(s)) / s.size;  tmpl_q = cumsum(counts of the template's present values) / t.size;
+ *   lut = interp(src_q, tmpl_q, present values) in float64;  out = blend * lut[s] + (1 - blend) * s.
+ * It sits after the D4 element and before every other photometric op.  Its three draws are words 0..2 of Philox stream 0,
+ * index 5 of the patch: apply (u < 0.5), template = floor(u * n_images), blend = 0.1 + u * 0.65.
+ *
+ * mpp_image_histograms: hist [n_images][3][256] uint32 (device) of the resident images (each of fewer than 2^32 pixels,
+ * at most 65535 images), one launch on the ctx's stream after reading the image sizes back.
+ * mpp_train_set_histograms: hands that table (borrowed, device) to the ctx for the following mpp_train_batch calls with
+ * MPP_AUG_HISTMATCH; n_images must equal the data's (else mpp_train_batch returns -1); NULL takes it away. */
+int mpp_image_histograms(mpp_ctx *ctx, const mpp_train_data *data, uint32_t *hist);
+int mpp_train_set_histograms(mpp_ctx *ctx, const uint32_t *hist, int n_images);
+/* The error density of one training image (H x W) from a raw PosNet output: out [3][ldh][ldw] float32 is the forward of
+ * the crop whose pixel (0, 0) is image pixel (cx0, cy0); the cells of the core (x0, x1, y0, y1) -- image rows x0..x1-1,
+ * columns y0..y1-1; x0 and y0 multiples of 8, x1 (y1) a multiple of 8 or H (W) -- are written.  With
+ *   target = 1 where the nearest of the n centres [n][2] int32 (row, col; image coordinates) is within max_distance
+ *            (the `mask` label of mpp_train_batch; 0 without objects),
+ *   err = |target - sigmoid(out[2])| in float32,  cell = mean of err over the in-image pixels of an 8 x 8 block,
+ * dens [ceil(H/8)][ceil(W/8)] uint8 = min(255, floor(256 * cell)); *sum (uint64, device) grows by the sum of the cells
+ * written (zero it before the first core of an image); cell_out (NULL-able) the float32 means.  n is not limited.
+ * All device pointers, one launch on the ctx's stream (asynchronous). */
+int mpp_posnet_error_map(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *out, int cx0, int cy0, int x0, int x1,
+                         int y0, int y1, const int32_t *centers, int n, double max_distance, uint8_t *dens,
+                         unsigned long long *sum, float *cell_out);
+/* Integer prefix tables of the densities of n_images images (img_hw [n_images][2] int32 as in mpp_train_data), cell maps
+ * back to back: image i's [ceil(H/8)][ceil(W/8)] map starts cell_off[i] entries into dens / cellcum, its rows row_off[i]
+ * entries into rowcum (total_rows = row_off past the last image).  cellcum: inclusive prefix within each row (uint32);
+ * rowcum: inclusive prefix of the row totals (uint64), so the image's total is its last entry. */
+int mpp_density_prefix(mpp_ctx *ctx, int n_images, const int32_t *img_hw, const int64_t *cell_off, const int64_t *row_off,
+                       int64_t total_rows, const uint8_t *dens, uint32_t *cellcum, unsigned long long *rowcum);
+/* n anchors from those tables: rows [n][2] int32 = (image, plan row).  w = Philox4x32-10 words (1 << 32 | 0) with key
+ * (seed, epoch) and counter (plan row, 0, 3, 0); r = mulhi64(w, total); (I, J) the cell whose cumulative range holds r;
+ * anchors [n][2] int32 = (min(8 I, H), min(8 J, W)), or (-1, -1) for an image whose total is 0. */
+int mpp_density_anchors(mpp_ctx *ctx, int n_images, const int32_t *img_hw, const int64_t *cell_off, const int64_t *row_off,
+                        const uint32_t *cellcum, const unsigned long long *rowcum, int n, const int32_t *rows,
+                        uint32_t seed, uint32_t epoch, int32_t *anchors);
 
 void mpp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 int mpp_abi_version(void);

@@ -1613,9 +1613,67 @@ extern "C" int mpp_train_batch(mpp_ctx *c, const mpp_train_data *data, const mpp
   } else {
     return fail(c, -1, "train_batch: kind must be 0 (PosNet) or 1 (ShapeNet)");
   }
-  if (flags & ~(MPP_AUG_GEOMETRIC | MPP_AUG_MEDIUM | MPP_AUG_STRONG | MPP_AUG_PERTURB)) return fail(c, -1, "train_batch: bad flags");
+  if (flags & ~(MPP_AUG_GEOMETRIC | MPP_AUG_MEDIUM | MPP_AUG_STRONG | MPP_AUG_PERTURB | MPP_AUG_HISTMATCH))
+    return fail(c, -1, "train_batch: bad flags");
+  if ((flags & MPP_AUG_HISTMATCH) && (!c->train.hist || c->train.hist_images != data->n_images))
+    return fail(c, -1, "train_batch: MPP_AUG_HISTMATCH needs the histograms of the data's %d images (mpp_train_set_histograms)",
+                data->n_images);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, mpp_launch_train_batch(c->stream, *data, *labels, B, P, desc, flags, seed, epoch, batch, *out));
+  HIPCHK(c, mpp_launch_train_batch(c->stream, &c->train, *data, *labels, B, P, desc, flags, seed, epoch, batch, *out));
+  return 0;
+}
+// ---- histogram matching and error-density resampling (mpp_train.hip, mpp_resample.hip) ----------------------------------
+static bool no_dataset(const mpp_train_data *data) {
+  return !data || data->n_images <= 0 || !data->images || !data->img_off || !data->img_hw;
+}
+extern "C" int mpp_image_histograms(mpp_ctx *c, const mpp_train_data *data, uint32_t *hist) {
+  if (!c || no_dataset(data) || !hist) return fail(c, -1, "image_histograms: missing arguments");
+  if (data->n_images > 65535) return fail(c, -1, "image_histograms: at most 65535 images");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_image_histograms(c->stream, *data, hist));
+  return 0;
+}
+extern "C" int mpp_train_set_histograms(mpp_ctx *c, const uint32_t *hist, int n_images) {
+  if (!c || (hist && n_images <= 0)) return fail(c, -1, "train_set_histograms: bad arguments");
+  c->train.hist = hist;
+  c->train.hist_images = hist ? n_images : 0;
+  return 0;
+}
+extern "C" int mpp_posnet_error_map(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *out, int cx0, int cy0, int x0, int x1,
+                                    int y0, int y1, const int32_t *centers, int n, double max_distance, uint8_t *dens,
+                                    unsigned long long *sum, float *cell_out) {
+  if (!c || !out || !dens || !sum || n < 0 || (n > 0 && !centers)) return fail(c, -1, "posnet_error_map: missing arguments");
+  if (H <= 0 || W <= 0 || ldh <= 0 || ldw <= 0 || !(max_distance >= 0.0) || max_distance > 1024.0)
+    return fail(c, -1, "posnet_error_map: bad extent or max_distance");
+  if (x0 < 0 || y0 < 0 || x0 >= x1 || y0 >= y1 || x1 > H || y1 > W || (x0 & 7) || (y0 & 7) || ((x1 & 7) && x1 != H) ||
+      ((y1 & 7) && y1 != W))
+    return fail(c, -1, "posnet_error_map: the core (%d, %d, %d, %d) must lie in the %d x %d image on multiples of 8", x0, x1, y0,
+                y1, H, W);
+  if (cx0 < 0 || cy0 < 0 || cx0 > x0 || cy0 > y0 || x1 - cx0 > ldh || y1 - cy0 > ldw)
+    return fail(c, -1, "posnet_error_map: the core lies outside the %d x %d output at (%d, %d)", ldh, ldw, cx0, cy0);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_error_map(c->stream, H, W, ldh, ldw, out, cx0, cy0, x0, x1, y0, y1, centers, n, max_distance, dens, sum,
+                                 cell_out));
+  return 0;
+}
+extern "C" int mpp_density_prefix(mpp_ctx *c, int n_images, const int32_t *img_hw, const int64_t *cell_off, const int64_t *row_off,
+                                  int64_t total_rows, const uint8_t *dens, uint32_t *cellcum, unsigned long long *rowcum) {
+  if (!c || !img_hw || !cell_off || !row_off || !dens || !cellcum || !rowcum) return fail(c, -1, "density_prefix: missing arguments");
+  if (n_images <= 0 || total_rows < n_images || total_rows > 0x7fffffff)
+    return fail(c, -1, "density_prefix: bad counts (%d images, %lld rows)", n_images, (long long)total_rows);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_density_prefix(c->stream, n_images, img_hw, cell_off, row_off, total_rows, dens, cellcum, rowcum));
+  return 0;
+}
+extern "C" int mpp_density_anchors(mpp_ctx *c, int n_images, const int32_t *img_hw, const int64_t *cell_off, const int64_t *row_off,
+                                   const uint32_t *cellcum, const unsigned long long *rowcum, int n, const int32_t *rows,
+                                   uint32_t seed, uint32_t epoch, int32_t *anchors) {
+  if (!c || !img_hw || !cell_off || !row_off || !cellcum || !rowcum || n < 0 || (n > 0 && (!rows || !anchors)) || n_images <= 0)
+    return fail(c, -1, "density_anchors: bad arguments");
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_density_anchors(c->stream, n_images, img_hw, cell_off, row_off, cellcum, rowcum, n, rows, seed, epoch,
+                                       anchors));
   return 0;
 }
 extern "C" int mpp_posnet_loss(mpp_ctx *c, int B, int P, const float *out, const float *vec, const float *mask, const float *dil,

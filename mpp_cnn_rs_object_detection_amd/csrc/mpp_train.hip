@@ -6,12 +6,15 @@
 //    every thread labels its pixels against the LDS list: exact nearest centre for PosNet (ties to the lowest annotation
 //    index), the even-odd crossing test of skimage.draw.polygon for ShapeNet (the rule csrc/mpp_classics.hpp restates).
 //    It writes the band's label sums, so that the loss kernel knows both balancing betas before it writes a gradient.
+//  * k_hist_lut (MPP_AUG_HISTMATCH only), in front of it: one workgroup per patch builds the patch's histogram in LDS and
+//    the matching table of the patch's template image, lut [B][3][256] float32, which the band workgroups then apply.
 //  * k_posnet_loss / k_shapenet_loss: one workgroup per (patch, band); each writes the loss and dL/dout of its pixels and
 //    its partial sums, and the last workgroup to finish reduces the partials in a fixed order (the same inputs give the
 //    same bits).
 //
 // Random draws: Philox4x32-10, key (seed, epoch), counter (batch, patch, stream, index); stream 0: the patch's draws,
 // 1: class perturbation of an object (index: its row in the dataset's object table), 2: pixel noise (index: pixel).
+// Stream 0's indices: 0 D4, 1..4 the photometric ops, 5 histogram matching.
 #include <cmath>
 #include <cstdint>
 
@@ -80,14 +83,25 @@ struct PatchAug {
   int bc = 0; float alpha = 1.f, beta = 0.f;
   int color = 0; float shift[3] = {0.f, 0.f, 0.f};   // 1 RGB shift, 2 to gray
   int noise = 0; double sigma = 0.0;
+  int hm = 0, tmpl = 0; double blend = 0.0;          // histogram matching to image tmpl
 };
+
+// the three draws of histogram matching (HistogramMatching(blend_ratio (0.1, 0.75), p 0.5), data/augmentation.py:26-29)
+__device__ __forceinline__ void hist_draws(const Rng &g, int n_images, PatchAug &a) {
+  uint32_t d[4];
+  g.draw(0, 5, d);
+  a.hm = unif(d[0]) < 0.5;
+  a.tmpl = min(n_images - 1, (int)(unif(d[1]) * (double)n_images));
+  a.blend = 0.1 + unif(d[2]) * 0.65;
+}
 
 // albumentations' defaults (RandomRotate90, Flip, ChannelShuffle, ChannelDropout((1, 1), fill 0), RandomBrightnessContrast
 // (0.2, 0.2, brightness_by_max), RGBShift(20, 20, 20), ToGray, GaussNoise(var_limit (10, 50), mean 0, per channel)),
-// composed as data/augmentation.py:22-72 lays them out; CLAHE, histogram matching, shadow, fog, downscale and blur are not built
-__device__ PatchAug patch_draws(const Rng &g, int flags) {
+// composed as data/augmentation.py:22-72 lays them out; CLAHE, shadow, fog, downscale and blur are not built
+__device__ PatchAug patch_draws(const Rng &g, int flags, int n_images) {
   PatchAug a;
   uint32_t d[4];
+  if (flags & MPP_AUG_HISTMATCH) hist_draws(g, n_images, a);
   if (flags & MPP_AUG_GEOMETRIC) {
     g.draw(0, 0, d);
     a.rot = unif(d[0]) < 0.5 ? (int)(unif(d[1]) * 4.0) : 0;
@@ -171,9 +185,87 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
   return r;
 }
 
+// inclusive prefix of one uint32 per thread over the TB (= 256) threads, through buf
+__device__ __forceinline__ uint32_t scan256(uint32_t v, uint32_t *buf) {
+  buf[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 1; s < TB; s <<= 1) {
+    const uint32_t add = (int)threadIdx.x >= s ? buf[threadIdx.x - s] : 0u;
+    __syncthreads();
+    buf[threadIdx.x] += add;
+    __syncthreads();
+  }
+  const uint32_t r = buf[threadIdx.x];
+  __syncthreads();
+  return r;
+}
+
+// The matching table of every patch whose draw says "apply": thread v owns the 8-bit value v.  The patch's histogram is
+// that of its in-image pixels plus its zero padding (D4 does not change a histogram); the template's comes from hist.
+// lut[v] = np.interp(src_q[v], tmpl_q, tmpl_values) in float64, over the template's present values only.
+__global__ __launch_bounds__(TB) void k_hist_lut(mpp_train_data data, int P, const int32_t *desc, const uint32_t *hist,
+                                                 uint32_t seed, uint32_t epoch, uint32_t batch, float *lut) {
+  __shared__ uint32_t cnt[3][256];
+  __shared__ uint32_t buf[TB];
+  __shared__ uint32_t t_cnt[256];
+  __shared__ double t_q[256];
+  const int b = blockIdx.x, v = threadIdx.x;
+  const Rng g{seed, epoch, batch, (uint32_t)b};
+  PatchAug aug;
+  hist_draws(g, data.n_images, aug);
+  if (!aug.hm) return;
+  const int img = desc[3 * b];
+  const bool valid = img >= 0 && img < data.n_images;
+  const int tl_r = desc[3 * b + 1] - P / 2, tl_c = desc[3 * b + 2] - P / 2;
+  const int H = valid ? data.img_hw[2 * img] : 0, W = valid ? data.img_hw[2 * img + 1] : 0;
+  const uint8_t *im = valid ? data.images + data.img_off[img] : nullptr;
+  for (int ch = 0; ch < 3; ++ch) cnt[ch][v] = 0u;
+  __syncthreads();
+  // the rows and columns of the patch that lie in the image
+  const int ra = max(0, -tl_r), rb = min(P, H - tl_r), ca = max(0, -tl_c), cb = min(P, W - tl_c);
+  const int nr = max(0, rb - ra), nc = max(0, cb - ca);
+  for (int idx = threadIdx.x; idx < nr * nc; idx += TB) {
+    const int gr = tl_r + ra + idx / nc, gc = tl_c + ca + idx % nc;
+    const uint8_t *p = im + ((size_t)gr * W + gc) * 3;
+    atomicAdd(&cnt[0][p[0]], 1u);
+    atomicAdd(&cnt[1][p[1]], 1u);
+    atomicAdd(&cnt[2][p[2]], 1u);
+  }
+  __syncthreads();
+  const uint32_t pad = (uint32_t)(P * P - nr * nc);
+  const double s_size = (double)P * (double)P;
+  const double t_size = (double)data.img_hw[2 * aug.tmpl] * (double)data.img_hw[2 * aug.tmpl + 1];
+  for (int ch = 0; ch < 3; ++ch) {
+    const uint32_t s_cum = scan256(cnt[ch][v] + (v == 0 ? pad : 0u), buf);
+    const uint32_t tc = hist[((size_t)aug.tmpl * 3 + ch) * 256 + v];
+    const uint32_t t_cum = scan256(tc, buf);
+    t_cnt[v] = tc;
+    t_q[v] = (double)t_cum / t_size;
+    __syncthreads();
+    const double x = (double)s_cum / s_size;
+    // j: the last present value whose quantile is <= x; j2: the next present value
+    int first = -1, last = -1, j = -1, j2 = -1;
+    for (int k = 0; k < 256; ++k) {
+      if (!t_cnt[k]) continue;
+      if (first < 0) first = k;
+      last = k;
+      if (t_q[k] <= x) j = k;
+      else if (j2 < 0) j2 = k;
+    }
+    double r;
+    if (first < 0) r = (double)v;                            // (an image without pixels: nothing to match to)
+    else if (j < 0) r = (double)first;                       // x < xp[0]
+    else if (j == last || t_q[j] == x) r = (double)j;
+    else r = ((double)(j2 - j) / (t_q[j2] - t_q[j])) * (x - t_q[j]) + (double)j;
+    lut[((size_t)b * 3 + ch) * 256 + v] = (float)r;
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(TB) void k_train_batch(mpp_train_data data, mpp_train_labels lab, int B, int P, int nb,
                                                     const int32_t *desc, int flags, uint32_t seed, uint32_t epoch,
-                                                    uint32_t batch, mpp_train_out out) {
+                                                    uint32_t batch, const float *lut, mpp_train_out out) {
+  __shared__ float hm_lut[3][256];                 // the patch's matching table (MPP_AUG_HISTMATCH)
   __shared__ int o_idx[MAXO];              // the object's row in the dataset table
   __shared__ int16_t o_r[MAXO], o_c[MAXO];         // centre in the (transformed) patch
   __shared__ int16_t o_box[MAXO][4];               // rows r0..r1, columns c0..c1 of its polygon's pixels (ShapeNet)
@@ -184,7 +276,9 @@ __global__ __launch_bounds__(TB) void k_train_batch(mpp_train_data data, mpp_tra
 
   const int band = blockIdx.x, b = blockIdx.y;
   const Rng g{seed, epoch, batch, (uint32_t)b};
-  const PatchAug aug = patch_draws(g, flags);
+  const PatchAug aug = patch_draws(g, flags, data.n_images);
+  if (aug.hm)
+    for (int k = threadIdx.x; k < 3 * 256; k += TB) hm_lut[k >> 8][k & 255] = lut[(size_t)b * 768 + k];
   const int img = desc[3 * b];
   const bool valid = img >= 0 && img < data.n_images;
   const int tl_r = desc[3 * b + 1] - P / 2, tl_c = desc[3 * b + 2] - P / 2;
@@ -277,6 +371,9 @@ __global__ __launch_bounds__(TB) void k_train_batch(mpp_train_data data, mpp_tra
       const uint8_t *p = im + ((size_t)gr * W + gc) * 3;
       x[0] = (float)p[0]; x[1] = (float)p[1]; x[2] = (float)p[2];
     }
+    if (aug.hm)                                               // one rounding: the blend is formed in float64
+      for (int ch = 0; ch < 3; ++ch)
+        x[ch] = clip255((float)(aug.blend * (double)hm_lut[ch][(int)x[ch]] + (1.0 - aug.blend) * (double)x[ch]));
     if (flags & (MPP_AUG_MEDIUM | MPP_AUG_STRONG)) photometric(aug, g, i * P + j, x);
     for (int ch = 0; ch < 3; ++ch) out.patch[((size_t)b * 3 + ch) * PP + (size_t)i * P + j] = x[ch] / 255.0f;
 
@@ -565,16 +662,31 @@ hipError_t mpp_train_ws_reserve(TrainWs *ws, size_t workgroups) {
 void mpp_train_ws_free(TrainWs *ws) {
   if (ws->part) (void)hipFree(ws->part);
   if (ws->done) (void)hipFree(ws->done);
+  if (ws->lut) (void)hipFree(ws->lut);
   ws->part = nullptr;
   ws->done = nullptr;
+  ws->lut = nullptr;
   ws->part_count = 0;
+  ws->lut_patches = 0;
 }
 
-hipError_t mpp_launch_train_batch(hipStream_t st, const mpp_train_data &data, const mpp_train_labels &labels, int B, int P,
-                                  const int32_t *desc, int flags, uint32_t seed, uint32_t epoch, uint32_t batch,
+hipError_t mpp_launch_train_batch(hipStream_t st, TrainWs *ws, const mpp_train_data &data, const mpp_train_labels &labels,
+                                  int B, int P, const int32_t *desc, int flags, uint32_t seed, uint32_t epoch, uint32_t batch,
                                   const mpp_train_out &out) {
   const int nb = (P + BAND - 1) / BAND;
-  hipLaunchKernelGGL(k_train_batch, dim3(nb, B), dim3(TB), 0, st, data, labels, B, P, nb, desc, flags, seed, epoch, batch, out);
+  if (flags & MPP_AUG_HISTMATCH) {
+    if (ws->lut_patches < (size_t)B) {
+      if (ws->lut) (void)hipFree(ws->lut);
+      ws->lut = nullptr;
+      ws->lut_patches = 0;
+      hipError_t e = hipMalloc((void **)&ws->lut, (size_t)B * 768 * sizeof(float));
+      if (e != hipSuccess) return e;
+      ws->lut_patches = (size_t)B;
+    }
+    hipLaunchKernelGGL(k_hist_lut, dim3(B), dim3(TB), 0, st, data, P, desc, ws->hist, seed, epoch, batch, ws->lut);
+  }
+  hipLaunchKernelGGL(k_train_batch, dim3(nb, B), dim3(TB), 0, st, data, labels, B, P, nb, desc, flags, seed, epoch, batch,
+                     (const float *)ws->lut, out);
   return hipGetLastError();
 }
 

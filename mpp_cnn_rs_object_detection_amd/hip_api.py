@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "mpp_replay", "mpp_run", "mpp_set_chain_keys", "mpp_step_index", "mpp_last_kernel_ms", "mpp_posnet_epilogue",
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
     "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
+    "mpp_image_histograms", "mpp_train_set_histograms", "mpp_posnet_error_map", "mpp_density_prefix", "mpp_density_anchors",
     "mpp_abi_version",
 ]
 
@@ -75,7 +76,9 @@ class TrainOutC(C.Structure):
 
 
 #: mpp_train_batch flags (include/mpp_hip.h MPP_AUG_*) and its geometry
-AUG_GEOMETRIC, AUG_MEDIUM, AUG_STRONG, AUG_PERTURB = 1, 2, 4, 8
+AUG_GEOMETRIC, AUG_MEDIUM, AUG_STRONG, AUG_PERTURB, AUG_HISTMATCH = 1, 2, 4, 8, 16
+#: side of a density cell in pixels (mpp_posnet_error_map), the reference's rescale_fac 1/8
+DENSITY_CELL = 8
 TRAIN_BAND, TRAIN_MAX_OBJ = 16, 1024
 
 
@@ -170,6 +173,11 @@ def load_library(path: Optional[str] = None):
         "mpp_posnet_loss": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
         "mpp_shapenet_loss": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mpp_philox4x32": (None, [vp, vp, vp]),
+        "mpp_image_histograms": (i32, [vp, C.POINTER(TrainDataC), vp]),
+        "mpp_train_set_histograms": (i32, [vp, vp, i32]),
+        "mpp_posnet_error_map": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, dbl, vp, vp, vp]),
+        "mpp_density_prefix": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp]),
+        "mpp_density_anchors": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, C.c_uint32, vp]),
         "mpp_abi_version": (i32, []),
     }
     for name, (res, args) in protos.items():
@@ -692,6 +700,67 @@ class MppContext:
         g = list(grads) if grads is not None else [None, None, None]
         self._check(self._L.mpp_shapenet_loss(self._h, B, P, nc, _ptr(logits[0]), _ptr(logits[1]), _ptr(logits[2]), _ptr(cls),
                                               _ptr(cover), _ptr(sums), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(res)))
+
+    # -- histogram matching and error-density resampling (device tensors; asynchronous on the ctx's stream) ---------------
+    @staticmethod
+    def _dev(name: str, t, dtype, shape=None):
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError(f"{name} must be a contiguous {dtype} CUDA tensor" + (f" of shape {tuple(shape)}" if shape else ""))
+        return _ptr(t)
+
+    def image_histograms(self, data: TrainDataC, hist):
+        """``mpp_image_histograms``: hist [n_images,3,256] int32 CUDA tensor (the counts are unsigned)"""
+        import torch
+        self._check(self._L.mpp_image_histograms(self._h, C.byref(data), self._dev("hist", hist, torch.int32, (data.n_images, 3, 256))))
+
+    def train_set_histograms(self, hist):
+        """``mpp_train_set_histograms``: the table of ``image_histograms`` for the next ``train_batch`` calls (None: none);
+        the caller keeps the tensor alive"""
+        import torch
+        if hist is None:
+            self._check(self._L.mpp_train_set_histograms(self._h, None, 0))
+            return
+        if hist.dim() != 3 or tuple(hist.shape[1:]) != (3, 256):
+            raise ValueError("hist must be [n_images,3,256]")
+        self._check(self._L.mpp_train_set_histograms(self._h, self._dev("hist", hist, torch.int32), int(hist.shape[0])))
+
+    def posnet_error_map(self, out, shape, centers, max_distance: float, dens, total, cell=None, crop=(0, 0), core=None):
+        """``mpp_posnet_error_map``: out [3,ldh,ldw] float32 (the raw PosNet output of the crop whose pixel (0, 0) is image
+        pixel ``crop``), shape (H, W) of the image, centers [n,2] int32 (None or empty: no objects), dens
+        [ceil(H/8),ceil(W/8)] uint8, total [1] int64 (grows by the sum of the cells written), cell the float32 means or
+        None; core (x0, x1, y0, y1): the cells to write (default: the whole image)."""
+        import torch
+        H, W = int(shape[0]), int(shape[1])
+        ldh, ldw = _planar_shape(out, 3)
+        cells = (-(-H // DENSITY_CELL), -(-W // DENSITY_CELL))
+        x0, x1, y0, y1 = (0, H, 0, W) if core is None else (int(v) for v in core)
+        n = 0 if centers is None else int(centers.shape[0])
+        self._check(self._L.mpp_posnet_error_map(
+            self._h, H, W, ldh, ldw, _ptr(out), int(crop[0]), int(crop[1]), x0, x1, y0, y1,
+            self._dev("centers", centers, torch.int32) if n else None, n, float(max_distance),
+            self._dev("dens", dens, torch.uint8, cells), self._dev("total", total, torch.int64, (1,)),
+            None if cell is None else self._dev("cell", cell, torch.float32, cells)))
+
+    def density_prefix(self, img_hw, cell_off, row_off, total_rows: int, dens, cellcum, rowcum):
+        """``mpp_density_prefix``: img_hw [n,2] int32, cell_off / row_off [n] int64, dens uint8 and cellcum int32 (unsigned
+        counts) of the same length, rowcum [total_rows] int64"""
+        import torch
+        n = int(img_hw.shape[0])
+        self._check(self._L.mpp_density_prefix(
+            self._h, n, self._dev("img_hw", img_hw, torch.int32, (n, 2)), self._dev("cell_off", cell_off, torch.int64, (n,)),
+            self._dev("row_off", row_off, torch.int64, (n,)), int(total_rows), self._dev("dens", dens, torch.uint8),
+            self._dev("cellcum", cellcum, torch.int32, dens.shape), self._dev("rowcum", rowcum, torch.int64, (int(total_rows),))))
+
+    def density_anchors(self, img_hw, cell_off, row_off, cellcum, rowcum, rows, seed: int, epoch: int, anchors):
+        """``mpp_density_anchors``: rows [n,2] int32 (image, plan row) -> anchors [n,2] int32"""
+        import torch
+        n_images, n = int(img_hw.shape[0]), int(rows.shape[0])
+        self._check(self._L.mpp_density_anchors(
+            self._h, n_images, self._dev("img_hw", img_hw, torch.int32, (n_images, 2)),
+            self._dev("cell_off", cell_off, torch.int64, (n_images,)), self._dev("row_off", row_off, torch.int64, (n_images,)),
+            self._dev("cellcum", cellcum, torch.int32), self._dev("rowcum", rowcum, torch.int64),
+            n, self._dev("rows", rows, torch.int32, (n, 2)), int(seed) & 0xffffffff, int(epoch) & 0xffffffff,
+            self._dev("anchors", anchors, torch.int32, (n, 2))))
 
     # -- evaluation --------------------------------------------------------------------------------
     def quad_iou(self, a, b) -> np.ndarray:

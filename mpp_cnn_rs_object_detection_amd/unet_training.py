@@ -3,7 +3,11 @@
 * the ``train`` and ``val`` images of a dataset stay on the device (uint8 HWC) with one CSR table of objects per image;
 * a patch plan is a small ``(image, anchor row, anchor col)`` table drawn on the host with the recipe of the reference's
   ``data/patch_making.py:17-100`` and ``data/patch_samplers.py:39-200`` (uniform + object samplers), never rasterised;
-* ``mpp_train_batch`` (csrc/mpp_train.hip) builds a whole batch -- crop, augmentation, labels -- in one launch;
+* ``mpp_train_batch`` (csrc/mpp_train.hip) builds a whole batch -- crop, augmentation, labels -- in one launch (two with
+  histogram matching, whose tables a small kernel builds first from the per-image histograms of the resident subset);
+* PosNet's hard-example mining (``pos_net_model.py:234-269, 303-321``): every ``error_update_interval`` epochs each training
+  image is forwarded, ``mpp_posnet_error_map`` keeps ``|target mask - predicted mask|`` per 8 x 8 cell as a uint8 density, and
+  from then on half of the plan's anchors come from ``mpp_density_anchors`` (``ErrorDensities``);
 * ``mpp_posnet_loss`` / ``mpp_shapenet_loss`` compute the loss and its gradient in one launch each, wrapped as
   ``torch.autograd.Function``s; the convolutions and BatchNorm go through PyTorch-ROCm autograd;
 * the model directory, ``log.json``, checkpoints, ``model.pt`` and ``model_div_clf.pt`` follow ``utils/training.py:43-83``,
@@ -30,12 +34,13 @@ from torch import nn
 
 from . import hip_api, unet
 from .mappings import ValueMapping
-from .paths import fetch_data_paths, get_model_base_path
+from .paths import fetch_data_paths, get_dataset_base_path, get_model_base_path
 
 KINDS = ("posnet", "shapenet")
 CHECKPOINT_INTERVAL = 4          # Logger.log_model(checkpoint_interval=4) in both reference models
 POSNET_LR = 1e-3                 # pos_net_model.py:93 hard-codes it
 SEED = 42                        # np.random.default_rng(42), and the key of the device draws
+DENSITY_WEIGHT = 1 / 2           # d_sampler_weight of pos_net_model.py:319
 
 
 # ---- configuration ----------------------------------------------------------------------------------------------------------
@@ -101,16 +106,19 @@ def labels_struct(config: Dict, kind: str) -> hip_api.TrainLabelsC:
     return lab
 
 
-def aug_flags(config: Dict, kind: str) -> int:
+def aug_flags(config: Dict, kind: str, histograms: bool = False) -> int:
     """train-time flags of mpp_train_batch: D4 + photometric when ``augment_params`` is present (utils/training.py:102-106),
-    the class perturbation for ShapeNet (shape_net_model.py:87-92)"""
+    the class perturbation for ShapeNet (shape_net_model.py:87-92).  ``histograms``: the caller builds its batches from a
+    ``ResidentSubset`` through a ``BatchBuilder``, which hands the per-image histograms to the context; then, and only
+    then, ``hist_match_images`` sets MPP_AUG_HISTMATCH (data/augmentation.py:26-29).  The flag without that table is an
+    error of mpp_train_batch, so a caller that has not said so gets the flags of the ops that need no table."""
     flags = hip_api.AUG_PERTURB if kind == "shapenet" else 0
     aug = config.get("data_loader", {}).get("augment_params")
     if aug is not None:
         flags |= hip_api.AUG_GEOMETRIC
         flags |= hip_api.AUG_STRONG if aug.get("aug_level", "medium") == "strong" else hip_api.AUG_MEDIUM
-        if aug.get("hist_match_images"):
-            logging.warning("augment_params.hist_match_images: histogram matching is not built; the other ops run")
+        if histograms and aug.get("hist_match_images"):
+            flags |= hip_api.AUG_HISTMATCH
     return flags
 
 
@@ -160,6 +168,8 @@ class ResidentSubset:
         if not (len(paths["images"]) == len(paths["annotations"]) == len(paths["metadata"])):
             raise ValueError(f"{dataset}/{subset}: images, annotations and metadata differ in number")
         imgs, centers, params, n_obj = [], [], [], []
+        ids = [re.match(r"[^0-9]*([0-9]+).*.png", os.path.basename(pf)) for pf in paths["images"]]
+        self.ids = [m.group(1) if m else os.path.splitext(os.path.basename(pf))[0] for m, pf in zip(ids, paths["images"])]
         for pf, af, mf in zip(paths["images"], paths["annotations"], paths["metadata"]):
             with Image.open(pf) as im:
                 a = np.asarray(im)
@@ -178,6 +188,7 @@ class ResidentSubset:
     def from_arrays(cls, images: Sequence[np.ndarray], centers: Sequence, params: Sequence, device: int) -> "ResidentSubset":
         """uint8 [H,W,3] images with their (row, col) centres and (a, b, angle) parameters (tests, benchmarks)"""
         self = cls.__new__(cls)
+        self.ids = [f"{i:04}" for i in range(len(images))]
         self._upload(list(images), list(centers), list(params), [len(np.asarray(c).reshape(-1, 2)) for c in centers], device)
         return self
 
@@ -190,7 +201,10 @@ class ResidentSubset:
         self.shapes = np.array([a.shape[:2] for a in imgs], dtype=np.int64)
         self.n_objects = np.array(n_obj, dtype=np.int64)
         self.centers = centers
+        self.obj_start_host = starts
         off = np.cumsum([0] + [x.size for x in imgs])
+        self.img_off_host = off[:-1]
+        self._hist = None
         dev = torch.device("cuda", device)
         self.images = torch.from_numpy(np.concatenate([x.ravel() for x in imgs])).to(dev)
         self.img_off = torch.from_numpy(off[:-1].astype(np.int64)).to(dev)
@@ -207,10 +221,40 @@ class ResidentSubset:
         s.centers, s.params = self.obj_centers.data_ptr(), self.obj_params.data_ptr()
         self.struct = s
 
+    def histograms(self, mctx: hip_api.MppContext) -> torch.Tensor:
+        """[n_images,3,256] counts of the 8-bit values per image and channel, computed on the device at the first call"""
+        if self._hist is None:
+            self._hist = torch.empty((self.n_images, 3, 256), dtype=torch.int32, device=self.images.device)
+            mctx.image_histograms(self.struct, self._hist)
+        return self._hist
+
+    def image(self, i: int) -> torch.Tensor:
+        """image i as a [H,W,3] uint8 view of the resident buffer"""
+        H, W = (int(v) for v in self.shapes[i])
+        off = int(self.img_off_host[i])
+        return self.images[off:off + H * W * 3].view(H, W, 3)
+
+    def image_centers(self, i: int) -> Optional[torch.Tensor]:
+        """the [n,2] int32 centres of image i on the device (None: no objects)"""
+        s, e = int(self.obj_start_host[i]), int(self.obj_start_host[i + 1])
+        return self.obj_centers[s:e] if e > s else None
+
+
+def sampler_weights(unf_weight: float, obj_weight: float, with_density: bool = False) -> np.ndarray:
+    """MixedSampler's weights: [unf, obj] normalised; with the density sampler ``add_sampler(d, 1/2)``'s
+    [unf (1 - 1/2), obj (1 - 1/2), 1/2], normalised again (patch_samplers.py:172-179)"""
+    w = np.array([unf_weight, obj_weight], dtype=np.float64)
+    w = w / w.sum()
+    if with_density:
+        w = np.array([wi * (1 - DENSITY_WEIGHT) for wi in w] + [DENSITY_WEIGHT])
+        w = w / np.sum(w)
+    return w
+
 
 def sample_density_per_image(shapes: np.ndarray, n_objects: np.ndarray, n_patches: int, unf_weight: float,
-                             obj_weight: float) -> np.ndarray:
-    """MixedSampler([UniformSampler, ObjectSampler]).sample_density_per_image (patch_samplers.py:39-200)"""
+                             obj_weight: float, density_sums: Optional[np.ndarray] = None) -> np.ndarray:
+    """MixedSampler([UniformSampler, ObjectSampler]).sample_density_per_image (patch_samplers.py:39-200); with
+    ``density_sums`` (the per-image sums of the error densities, not all zero) the DensitySampler is the third sampler"""
     n_images = len(shapes)
     if n_images > n_patches:
         raise ValueError(f"{n_images} images but only {n_patches} patches (UniformSampler asserts n_images <= n_patches)")
@@ -220,26 +264,43 @@ def sample_density_per_image(shapes: np.ndarray, n_objects: np.ndarray, n_patche
         s = (count / np.sum(count)) * (n_patches - n_images) + 1
         dens.append(s / np.sum(s))
     w = np.array([unf_weight, obj_weight]) / np.sum(np.array([unf_weight, obj_weight]))
+    if density_sums is not None:
+        sums = np.asarray(density_sums, dtype=np.float64)
+        dens.append(sums / np.sum(sums))
+        w = sampler_weights(unf_weight, obj_weight, True)
     d = np.sum([wi * di for wi, di in zip(w, dens)], axis=0)
     return d / np.sum(d)
 
 
-def make_plan(rng: np.random.Generator, data: ResidentSubset, n_patches: int, pm: Dict) -> np.ndarray:
+def make_plan(rng: np.random.Generator, data: ResidentSubset, n_patches: int, pm: Dict, densities=None, epoch: int = 0,
+              return_samplers: bool = False):
     """[n, 3] int32 (image, anchor row, anchor col): rng.multinomial over the images, then per patch a sampler drawn by
-    weight -- uniform anchor, or an object centre + N(0, sigma) -- clipped to [0, shape] (_make_patches, _make_one_patch)."""
+    weight -- uniform anchor, or an object centre + N(0, sigma) -- clipped to [0, shape] (_make_patches, _make_one_patch).
+
+    ``densities`` (an ``ErrorDensities``, or anything with ``sums`` [n_images] and ``anchors(rows, seed, epoch)``) adds the
+    DensitySampler with weight 1/2: its rows get their anchors from ``mpp_density_anchors`` in one call, keyed by
+    (SEED, epoch) and the plan row; an image whose density sums to 0 gets a uniform anchor (patch_samplers.py:146-147).  If
+    every image sums to 0 (the reference would divide 0 by 0) the plan is made without it.  ``return_samplers``: also the
+    sampler of every row (0 uniform, 1 object, 2 density)."""
+    sums = None if densities is None else np.asarray(densities.sums, dtype=np.int64)
+    if sums is not None and sums.sum() == 0:
+        logging.warning("every error density sums to 0: this patch plan is made without the density sampler")
+        sums = None
     dens = sample_density_per_image(data.shapes, data.n_objects, pm["n_patches"], pm["unf_sampler_weight"],
-                                    pm["obj_sampler_weight"])
-    w = np.array([pm["unf_sampler_weight"], pm["obj_sampler_weight"]], dtype=np.float64)
-    w = w / w.sum()
+                                    pm["obj_sampler_weight"], sums)
+    w = sampler_weights(pm["unf_sampler_weight"], pm["obj_sampler_weight"], sums is not None)
     sigma = pm.get("obj_sampler_sigma") or 0
     per_image = rng.multinomial(n=n_patches, pvals=dens)
-    rows = []
+    rows, which_all, drawn = [], [], []
     for i, k in enumerate(per_image):
         shape = data.shapes[i]
         centers = data.centers[i]
         for _ in range(int(k)):
-            which = rng.choice(2, p=w)
-            if which == 1 and len(centers) > 0:
+            which = int(rng.choice(len(w), p=w))
+            if which == 2 and sums[i] > 0:
+                drawn.append((i, len(rows)))
+                anchor = (0, 0)                       # filled in below
+            elif which == 1 and len(centers) > 0:
                 anchor = rng.choice(centers, axis=0).astype(int)
                 if sigma != 0:
                     anchor = rng.normal(anchor, sigma).astype(int)
@@ -247,7 +308,143 @@ def make_plan(rng: np.random.Generator, data: ResidentSubset, n_patches: int, pm
             else:
                 anchor = rng.integers((0, 0), shape)
             rows.append((i, int(anchor[0]), int(anchor[1])))
-    return np.array(rows, dtype=np.int32).reshape(-1, 3)
+            which_all.append(which)
+    plan = np.array(rows, dtype=np.int32).reshape(-1, 3)
+    if drawn:
+        drawn = np.array(drawn, dtype=np.int32)
+        plan[drawn[:, 1], 1:] = densities.anchors(drawn, SEED, epoch)
+    return (plan, np.array(which_all, dtype=np.int64)) if return_samplers else plan
+
+
+def density_anchors_host(dens: np.ndarray, shape, words: np.ndarray) -> np.ndarray:
+    """What ``mpp_density_anchors`` computes for one image, restated with numpy: dens [ch,cw] uint8, words the 64-bit Philox
+    words of the rows -> [n,2] anchors (the tests compare the kernel with this)"""
+    d = np.asarray(dens, dtype=np.uint64)
+    rowcum = np.cumsum(d.sum(axis=1, dtype=np.uint64), dtype=np.uint64)
+    cellcum = np.cumsum(d, axis=1, dtype=np.uint64)
+    total = int(rowcum[-1])
+    out = np.zeros((len(words), 2), dtype=np.int64)
+    for k, w in enumerate(words):
+        r = (int(w) * total) >> 64
+        i = int(np.searchsorted(rowcum, np.uint64(r), side="right"))
+        rr = r - (int(rowcum[i - 1]) if i else 0)
+        j = int(np.searchsorted(cellcum[i], np.uint64(rr), side="right"))
+        out[k] = (min(hip_api.DENSITY_CELL * i, int(shape[0])), min(hip_api.DENSITY_CELL * j, int(shape[1])))
+    return out
+
+
+def density_words(rows, seed: int, epoch: int) -> np.ndarray:
+    """the 64-bit Philox word of each plan row: key (seed, epoch), counter (row, 0, 3, 0), words (1 << 32 | 0)"""
+    out = []
+    for r in rows:
+        o = hip_api.philox([int(r) & 0xffffffff, 0, 3, 0], [seed & 0xffffffff, epoch & 0xffffffff])
+        out.append((int(o[1]) << 32) | int(o[0]))
+    return np.array(out, dtype=np.uint64)
+
+
+class ErrorDensities:
+    """PosNet's error densities of the training images, resident on the device: per image a [ceil(H/8), ceil(W/8)] uint8 map
+    of ``|target mask - sigmoid(out[2])|`` (block means, 256 levels), their integer prefix tables and sums."""
+
+    def __init__(self, data: ResidentSubset, mctx: hip_api.MppContext, max_distance: float):
+        self.data, self.mctx, self.max_distance = data, mctx, float(max_distance)
+        dev = data.images.device
+        c = hip_api.DENSITY_CELL
+        self.cells = -(-data.shapes // c)
+        n_cells = self.cells[:, 0] * self.cells[:, 1]
+        self.cell_off_host = np.concatenate([[0], np.cumsum(n_cells)]).astype(np.int64)
+        self.row_off_host = np.concatenate([[0], np.cumsum(self.cells[:, 0])]).astype(np.int64)
+        self.cell_off = torch.from_numpy(self.cell_off_host[:-1].copy()).to(dev)
+        self.row_off = torch.from_numpy(self.row_off_host[:-1].copy()).to(dev)
+        self.dens = torch.zeros(int(self.cell_off_host[-1]), dtype=torch.uint8, device=dev)
+        self.cellcum = torch.zeros(int(self.cell_off_host[-1]), dtype=torch.int32, device=dev)
+        self.rowcum = torch.zeros(int(self.row_off_host[-1]), dtype=torch.int64, device=dev)
+        self.totals = torch.zeros(data.n_images, dtype=torch.int64, device=dev)
+        self.sums = np.zeros(data.n_images, dtype=np.int64)
+        self.ready = False
+
+    def map(self, i: int) -> torch.Tensor:
+        """the [ch,cw] uint8 density of image i (a view)"""
+        a, b = int(self.cell_off_host[i]), int(self.cell_off_host[i + 1])
+        return self.dens[a:b].view(int(self.cells[i, 0]), int(self.cells[i, 1]))
+
+    def add(self, i: int, out: torch.Tensor, crop=(0, 0), core=None, cell: Optional[torch.Tensor] = None):
+        """the cells of ``core`` (default: all) of image i from the raw PosNet output ``out`` [3,h,w] of the crop at ``crop``;
+        the first core of an image (x0 = y0 = 0) restarts its sum"""
+        if core is None or (core[0] == 0 and core[2] == 0):
+            self.totals[i:i + 1].zero_()
+        self.mctx.posnet_error_map(out, self.data.shapes[i], self.data.image_centers(i), self.max_distance, self.map(i),
+                                   self.totals[i:i + 1], cell=cell, crop=crop, core=core)
+
+    @torch.no_grad()
+    def update(self, model: nn.Module, max_pixels: Optional[int] = None):
+        """Forward every image (eval mode, float32; whole when it fits ``max_pixels`` and the device memory, else the crops of
+        ``unet.chunk_plan``) and remake the densities, their prefix tables and sums."""
+        was_training = model.training
+        model.eval()
+        depth = model.backbone.depth
+        plan_depth = max(depth, 3)                 # cores on multiples of 8: a cell never straddles two crops
+        dev = self.data.images.device
+
+        def forward(x):
+            padded, _ = unet.pad_before_infer(x, depth)
+            return model(padded.unsqueeze(0))[0].contiguous()
+
+        for i in range(self.data.n_images):
+            H, W = (int(v) for v in self.data.shapes[i])
+            x = self.data.image(i).permute(2, 0, 1).float() / 255
+            plan = None
+            if max_pixels is not None and unet.padded_pixels((H, W), depth) > max_pixels:
+                plan = unet.chunk_plan((H, W), max_pixels, plan_depth)
+            else:
+                out = None
+                try:
+                    out = forward(x)
+                except torch.cuda.OutOfMemoryError:
+                    pass            # (handled outside the except clause, as ScoreMapNets.infer does)
+                if out is None:
+                    torch.cuda.synchronize(dev)
+                    torch.cuda.empty_cache()
+                    budget = int(0.8 * torch.cuda.mem_get_info(dev)[0] / unet.FORWARD_BYTES_PER_PIXEL)
+                    plan = unet.chunk_plan((H, W), max(budget, 1), plan_depth)
+                    logging.warning(f"error densities: the {H} x {W} forward ran out of device memory; tiled under {budget} "
+                                    f"pixels per forward ({len(plan)} crops)")
+                else:
+                    self.add(i, out)
+            if plan is not None:
+                for core, (cx0, cx1, cy0, cy1) in plan:
+                    out = forward(x[:, cx0:cx1, cy0:cy1])
+                    self.add(i, out, crop=(cx0, cy0), core=core)
+                    del out
+        model.train(was_training)
+        self.finish()
+
+    def finish(self):
+        """prefix tables and host sums of the current maps"""
+        self.mctx.density_prefix(self.data.img_hw, self.cell_off, self.row_off, int(self.row_off_host[-1]), self.dens,
+                                 self.cellcum, self.rowcum)
+        self.sums = self.totals.cpu().numpy().astype(np.int64)
+        self.ready = True
+
+    def anchors(self, rows: np.ndarray, seed: int, epoch: int) -> np.ndarray:
+        """rows [n,2] (image, plan row) -> [n,2] anchors (``mpp_density_anchors``)"""
+        dev = self.dens.device
+        r = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2)).to(dev)
+        out = torch.empty_like(r)
+        self.mctx.density_anchors(self.data.img_hw, self.cell_off, self.row_off, self.cellcum, self.rowcum, r, seed, epoch, out)
+        return out.cpu().numpy()
+
+    def write_pngs(self, directory: str) -> List[str]:
+        """``<directory>/<id>.png``: the uint8 maps as gray images, one level per value (what compute_errors leaves behind)"""
+        from PIL import Image
+        os.makedirs(directory, exist_ok=True)
+        host = self.dens.cpu().numpy()
+        files = []
+        for i, name in enumerate(self.data.ids):
+            a, b = int(self.cell_off_host[i]), int(self.cell_off_host[i + 1])
+            files.append(os.path.join(directory, f"{name}.png"))
+            Image.fromarray(host[a:b].reshape(int(self.cells[i, 0]), int(self.cells[i, 1]))).save(files[-1])
+        return files
 
 
 # ---- the batch builder -----------------------------------------------------------------------------------------------------
@@ -286,6 +483,8 @@ class BatchBuilder:
         if fresh:
             out = {k: torch.empty_like(v) for k, v in out.items()}
         out["status"] = self.status
+        if flags & hip_api.AUG_HISTMATCH:
+            self.mctx.train_set_histograms(data.histograms(self.mctx))
         self.mctx.train_batch(data.struct, self.labels, desc, self.P, flags, seed, epoch, batch, out)
         return {k: v for k, v in out.items() if k != "status"}
 
@@ -409,10 +608,12 @@ def train_unet(config: Dict, kind: str, dataset: Optional[str] = None, device: i
     check_config(config, kind)
     if _world_size() > 1:
         raise RuntimeError("U-Net training runs on one GPU: start it without torchrun (or with --nproc-per-node 1)")
-    skipped = [k for k, v in (("data_loader.error_update_interval", config.get("data_loader", {}).get("error_update_interval")),
-                              ("trainer.figure_interval", config.get("trainer", {}).get("figure_interval"))) if v is not None]
-    if skipped:
-        logging.warning(f"not built, ignored: {', '.join(skipped)} (error-density resampling, figures)")
+    if config.get("trainer", {}).get("figure_interval") is not None:
+        logging.warning("not built, ignored: trainer.figure_interval (figures)")
+    error_interval = config.get("data_loader", {}).get("error_update_interval")
+    if error_interval is not None and kind == "shapenet":
+        logging.warning("data_loader.error_update_interval: ShapeNet has no error update (nor has the reference's); ignored")
+        error_interval = None
     save_path = startup(config, kind, overwrite, resume, model_base)
     dl, tr = config["data_loader"], config["trainer"]
     dataset = dataset or dl["dataset"]
@@ -450,7 +651,7 @@ def train_unet(config: Dict, kind: str, dataset: Optional[str] = None, device: i
     mctx = hip_api.MppContext(device)
     mctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     builder = BatchBuilder(mctx, labels_struct(config, kind), P, device)
-    flags_train = aug_flags(config, kind)
+    flags_train = aug_flags(config, kind, histograms=True)
     train_data = ResidentSubset(dataset, "train", device)
     val_data = ResidentSubset(dataset, "val", device)
     rng = np.random.default_rng(SEED)
@@ -458,6 +659,8 @@ def train_unet(config: Dict, kind: str, dataset: Optional[str] = None, device: i
     plan_train = torch.from_numpy(make_plan(rng, train_data, n_patches, pm)).to(dev)
     plan_val = torch.from_numpy(make_plan(rng, val_data, n_patches // 2, pm)).to(dev)
     update_interval = int(dl["dataset_update_interval"])
+    # the error densities persist between error updates; a resumed run has none until its next error epoch
+    densities = ErrorDensities(train_data, mctx, float(config["loss"]["max_distance"])) if error_interval is not None else None
 
     def run_epoch(epoch: int, train: bool) -> Dict[str, float]:
         plan, data = (plan_train, train_data) if train else (plan_val, val_data)
@@ -492,7 +695,13 @@ def train_unet(config: Dict, kind: str, dataset: Optional[str] = None, device: i
               " ".join(f"{k}: {v:.3f}" for k, v in val_m.items()), flush=True)
         log.update(epoch, {**{"train_" + k: v for k, v in train_m.items()}, **{"val_" + k: v for k, v in val_m.items()}}, model)
         if epoch % update_interval == 0 and epoch != 0:
-            plan_train = torch.from_numpy(make_plan(rng, train_data, n_patches, pm)).to(dev)
+            if densities is not None and epoch % int(error_interval) == 0:
+                densities.update(model)
+                densities.write_pngs(os.path.join(get_dataset_base_path(), "error_maps", dataset, "train",
+                                                  os.path.split(save_path)[1]))
+            plan = make_plan(rng, train_data, n_patches, pm, densities if densities is not None and densities.ready else None,
+                             epoch)
+            plan_train = torch.from_numpy(plan).to(dev)
 
     torch.save(model.state_dict(), os.path.join(save_path, "model.pt"))
     if div_clf is not None:

@@ -3,9 +3,12 @@
 
 * patches/s of whole training steps (batch build, forward, loss, backward, Adam), each timed window ending in a device sync;
 * one step split by device events: batch build, forward, loss, backward, Adam;
-* A/B in the same process: the same step with the losses written as plain torch ops (pos_loss.py / pixel_ce_loss.py).
+* A/B in the same process: the same step with the losses written as plain torch ops (pos_loss.py / pixel_ce_loss.py);
+* ``--no-histmatch``: the same steps without MPP_AUG_HISTMATCH (what the batch build cost before histogram matching);
+* ``--error-update``: one error update of PosNet on the same data (forward of every image + mpp_posnet_error_map, then the
+  prefix tables) and one patch plan of the shipped size with density rows (mpp_density_anchors), next to a training epoch.
 
-    python profiles/tools/bench_unet_train.py [--steps 20] [--warmup 5]
+    python profiles/tools/bench_unet_train.py [--steps 20] [--warmup 5] [--no-histmatch] [--error-update]
 """
 import argparse
 import json
@@ -51,6 +54,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-histmatch", action="store_true")
+    ap.add_argument("--error-update", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
     imgs, cs, ps = [], [], []
@@ -69,7 +74,7 @@ def main():
     for kind in ("posnet", "shapenet"):
         cfg = ut.shipped_config(kind)
         bld = ut.BatchBuilder(mctx, ut.labels_struct(cfg, kind), P, 0)
-        flags = ut.aug_flags(cfg, kind)
+        flags = ut.aug_flags(cfg, kind, histograms=not args.no_histmatch)
         net = (unet.PosNet() if kind == "posnet" else unet.ShapeNet()).cuda().train()
         conv = torch.nn.Conv2d(1, 1, 1).cuda()
         opt = torch.optim.Adam(list(net.parameters()) + list(conv.parameters()), lr=1e-3)
@@ -119,7 +124,55 @@ def main():
                              "split_ms": dict(zip(["batch_build", "forward", "loss", "backward", "adam"], split.round(3).tolist()))}
             print(json.dumps({name: results[name]}), flush=True)
     bld.check()
+    if args.error_update:
+        error_update(data, mctx, results["posnet_fused"]["ms_per_step"])
     mctx.close()
+
+
+def error_update(data, mctx, ms_per_step):
+    """seconds of one error update and milliseconds of the anchors of one plan, next to an epoch of the shipped config"""
+    import time
+    cfg = ut.shipped_config("posnet")
+    pm = cfg["data_loader"]["patch_maker_params"]
+    net = unet.PosNet().cuda()
+    ed = ut.ErrorDensities(data, mctx, cfg["loss"]["max_distance"])
+    ed.update(net)                                       # warm-up: the forward's algorithm search
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    ed.update(net)
+    torch.cuda.synchronize()
+    update_s = time.perf_counter() - t
+    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+    out = net(torch.zeros((1, 3, 512, 512), device="cuda"))[0].detach().contiguous()
+    e0.record()
+    for i in range(data.n_images):
+        ed.add(i, out)
+    e1.record()
+    ed.mctx.density_prefix(data.img_hw, ed.cell_off, ed.row_off, int(ed.row_off_host[-1]), ed.dens, ed.cellcum, ed.rowcum)
+    e2.record()
+    torch.cuda.synchronize()
+    kernel_ms, prefix_ms = e0.elapsed_time(e1), e1.elapsed_time(e2)
+    ed.update(net)
+    plan, which = ut.make_plan(np.random.default_rng(0), data, pm["n_patches"], pm, ed, epoch=16, return_samplers=True)
+    rows = np.stack([plan[which == 2, 0], np.nonzero(which == 2)[0]], 1).astype(np.int32)
+    r = torch.from_numpy(rows).cuda()
+    a = torch.empty_like(r)
+    args_ = (data.img_hw, ed.cell_off, ed.row_off, ed.cellcum, ed.rowcum, r, 42, 16, a)
+    mctx.density_anchors(*args_)
+    e0.record()
+    for _ in range(10):
+        mctx.density_anchors(*args_)
+    e1.record()
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    ut.make_plan(np.random.default_rng(0), data, pm["n_patches"], pm, ed, epoch=16)
+    plan_s = time.perf_counter() - t
+    steps = -(-pm["n_patches"] // B)
+    print(json.dumps({"error_update": {
+        "images": data.n_images, "update_s": round(update_s, 4), "error_kernel_ms_all_images": round(kernel_ms, 3),
+        "prefix_ms": round(prefix_ms, 3), "density_rows": int(len(rows)), "anchors_kernel_ms": round(e0.elapsed_time(e1) / 10, 4),
+        "make_plan_host_s": round(plan_s, 3), "epoch_s": round(steps * ms_per_step / 1e3, 2),
+        "share_of_16_epochs": round(update_s / (16 * steps * ms_per_step / 1e3), 6)}}), flush=True)
 
 
 if __name__ == "__main__":
