@@ -397,8 +397,10 @@ enum {
   MPP_AUG_MEDIUM = 2,              /* photometric part of data/augmentation.py:22-40 that is one formula per op */
   MPP_AUG_STRONG = 4,              /* ... of :43-72 */
   MPP_AUG_PERTURB = 8,             /* ShapeNet: class perturbation {0: 0.8, +1: 0.1, -1: 0.1} per object and mark */
-  MPP_AUG_HISTMATCH = 16           /* histogram matching to a random image of the subset (p 0.5), blended with U(0.1, 0.75);
+  MPP_AUG_HISTMATCH = 16,          /* histogram matching to a random image of the subset (p 0.5), blended with U(0.1, 0.75);
                                       needs mpp_train_set_histograms */
+  MPP_AUG_SPATIAL = 32             /* the ops of the recipe that need neighbours or the whole patch: shadow, fog, CLAHE,
+                                      downscale, median / box blur (below); needs P % 8 == 0 and 32 <= P <= 512 */
 };
 /* One batch of B patches of P x P (P even, 8..MPP_TRAIN_MAX_P) from the resident images: desc [B][3] int32 = (image, anchor
  * row, anchor col) device array; the patch is the read at anchor - P/2 with zeros outside the image (utils/images.py:4-23),
@@ -461,6 +463,39 @@ int mpp_density_prefix(mpp_ctx *ctx, int n_images, const int32_t *img_hw, const 
 int mpp_density_anchors(mpp_ctx *ctx, int n_images, const int32_t *img_hw, const int64_t *cell_off, const int64_t *row_off,
                         const uint32_t *cellcum, const unsigned long long *rowcum, int n, const int32_t *rows,
                         uint32_t seed, uint32_t epoch, int32_t *anchors);
+
+/* ---- the spatial ops of the augmentation recipe (csrc/mpp_train.hip, MPP_AUG_SPATIAL) ----------------------------------
+ * With the flag the image of a patch goes through the whole recipe of data/augmentation.py:21-71, in its order:
+ *   medium: D4, hist-match, OneOf[CLAHE | RGBShift], OneOf[Median3 | Blur3] (p 0.2), GaussNoise
+ *   strong: D4, hist-match, Shadow, Fog, OneOf[Shuffle | Dropout], BrightnessContrast, OneOf[CLAHE | RGBShift | ToGray],
+ *           Downscale(0.9), OneOf[Median3 | Blur3] (p 0.2), GaussNoise
+ * Labels do not move.  A patch whose draws pick none of the six ops is bit for bit the patch without the flag.  The ops are
+ * defined in DESIGN.md section 8; their patch draws are words of Philox stream 0, indices 6 and 7, their lists (shadow
+ * vertices, haze points) come from stream 3 (the table is in csrc/mpp_train.hip).
+ *
+ * mpp_train_aug_params writes what mpp_train_batch with the same (flags, seed, epoch, batch, B, P, n_images) draws for every
+ * patch: out [B] mpp_aug_record, device memory, one launch on the ctx's stream (asynchronous).  It reads no image. */
+#define MPP_AUG_MAX_HAZE 64        /* haze points of one patch (the fog loop gives at most 51 for P <= 512) */
+typedef struct mpp_aug_record {
+  int32_t rot, flip;               /* D4 */
+  int32_t chan_op, chan_arg;       /* 1 shuffle (permutation chan_arg of 6), 2 dropout (channel chan_arg) */
+  int32_t bc;                      /* brightness / contrast applies (alpha, beta) */
+  int32_t color;                   /* 1 RGB shift (shift), 2 to gray; 0 with clahe 1: CLAHE */
+  int32_t noise;                   /* Gauss noise applies (sigma) */
+  int32_t hm, tmpl;                /* histogram matching to image tmpl (blend) */
+  int32_t shadow, n_poly;          /* RandomShadow applies with n_poly (1 or 2) polygons of 5 vertices */
+  int32_t fog, n_haze;             /* RandomFog applies (fog_coef) with n_haze haze points */
+  int32_t clahe;                   /* CLAHE applies (clip) */
+  int32_t downscale;               /* Downscale(0.9) applies */
+  int32_t blur;                    /* 1 MedianBlur(3), 2 Blur(3) */
+  float alpha, beta, shift[3];
+  float _pad;
+  double sigma, blend, clip, fog_coef;
+  int16_t poly[2][5][2];           /* (x, y) = (column, row) of the shadow vertices, in the order drawn */
+  int16_t haze[MPP_AUG_MAX_HAZE][2];   /* (x, y) of the haze points, in the order drawn */
+} mpp_aug_record;
+int mpp_train_aug_params(mpp_ctx *ctx, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P, int n_images,
+                         mpp_aug_record *out);
 
 void mpp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 int mpp_abi_version(void);

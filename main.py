@@ -8,7 +8,8 @@ hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the 
 obb files), ``-p eval`` scores those.  ``-p train -m mpp`` learns the
 energy weights (manual / ordering / integral criterion) and calibrates; ``-p train -m posnet|shapenet`` trains the two
 U-Nets on one GPU (batches built and losses computed by HIP kernels, ``unet_training.train_unet``; with the shipped configs
-that includes histogram matching and, for PosNet, the error-density resampling of ``data_loader.error_update_interval``,
+that includes histogram matching, the whole ``strong`` augmentation recipe (shadow, fog, CLAHE, downscale and blur built as
+HIP kernels too) and, for PosNet, the error-density resampling of ``data_loader.error_update_interval``,
 whose maps land in ``<dataset base>/error_maps/<dataset>/train/<model_name>/``).  With ``torchrun --nproc-per-node N`` the images of the dataset are
 dealt to N GPUs (one gather of the results at the end; RCCL).
 """

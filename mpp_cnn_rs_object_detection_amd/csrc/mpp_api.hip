@@ -1613,13 +1613,28 @@ extern "C" int mpp_train_batch(mpp_ctx *c, const mpp_train_data *data, const mpp
   } else {
     return fail(c, -1, "train_batch: kind must be 0 (PosNet) or 1 (ShapeNet)");
   }
-  if (flags & ~(MPP_AUG_GEOMETRIC | MPP_AUG_MEDIUM | MPP_AUG_STRONG | MPP_AUG_PERTURB | MPP_AUG_HISTMATCH))
+  if (flags & ~(MPP_AUG_GEOMETRIC | MPP_AUG_MEDIUM | MPP_AUG_STRONG | MPP_AUG_PERTURB | MPP_AUG_HISTMATCH | MPP_AUG_SPATIAL))
     return fail(c, -1, "train_batch: bad flags");
+  if ((flags & MPP_AUG_SPATIAL) && (P % 8 || P < 32 || P > 512))
+    return fail(c, -1, "train_batch: MPP_AUG_SPATIAL needs P %% 8 == 0 and 32 <= P <= 512 (CLAHE's 8 x 8 tiles), not P=%d", P);
   if ((flags & MPP_AUG_HISTMATCH) && (!c->train.hist || c->train.hist_images != data->n_images))
     return fail(c, -1, "train_batch: MPP_AUG_HISTMATCH needs the histograms of the data's %d images (mpp_train_set_histograms)",
                 data->n_images);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, mpp_launch_train_batch(c->stream, &c->train, *data, *labels, B, P, desc, flags, seed, epoch, batch, *out));
+  return 0;
+}
+extern "C" int mpp_train_aug_params(mpp_ctx *c, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P,
+                                    int n_images, mpp_aug_record *out) {
+  if (!c || !out) return fail(c, -1, "train_aug_params: missing arguments");
+  if (B <= 0 || B > 65535 || P < 8 || P > MPP_TRAIN_MAX_P || (P & 1) || n_images <= 0)
+    return fail(c, -1, "train_aug_params: bad shape B=%d P=%d n_images=%d", B, P, n_images);
+  if (flags & ~(MPP_AUG_GEOMETRIC | MPP_AUG_MEDIUM | MPP_AUG_STRONG | MPP_AUG_PERTURB | MPP_AUG_HISTMATCH | MPP_AUG_SPATIAL))
+    return fail(c, -1, "train_aug_params: bad flags");
+  if ((flags & MPP_AUG_SPATIAL) && (P % 8 || P < 32 || P > 512))
+    return fail(c, -1, "train_aug_params: MPP_AUG_SPATIAL needs P %% 8 == 0 and 32 <= P <= 512, not P=%d", P);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, mpp_launch_aug_params(c->stream, flags, seed, epoch, batch, B, P, n_images, out));
   return 0;
 }
 // ---- histogram matching and error-density resampling (mpp_train.hip, mpp_resample.hip) ----------------------------------

@@ -8,13 +8,24 @@
 //    It writes the band's label sums, so that the loss kernel knows both balancing betas before it writes a gradient.
 //  * k_hist_lut (MPP_AUG_HISTMATCH only), in front of it: one workgroup per patch builds the patch's histogram in LDS and
 //    the matching table of the patch's template image, lut [B][3][256] float32, which the band workgroups then apply.
+//  * k_aug_spatial (MPP_AUG_SPATIAL only), between the two: one workgroup per patch whose draws pick at least one of the six
+//    ops that need neighbours or the whole patch (shadow, fog, CLAHE, downscale, median / box blur); the others leave at
+//    once.  It carries the image through the recipe up to the Gauss noise, stage by stage through a ping-pong pair of float32
+//    patch buffers in a workspace of the ctx, a workgroup barrier between stages; the CLAHE tile histograms / tables, the
+//    shadow vertices and the haze points live in LDS.  The band workgroups of k_train_batch then take the finished pixel of
+//    such a patch from the workspace and add the noise.
 //  * k_posnet_loss / k_shapenet_loss: one workgroup per (patch, band); each writes the loss and dL/dout of its pixels and
 //    its partial sums, and the last workgroup to finish reduces the partials in a fixed order (the same inputs give the
 //    same bits).
 //
 // Random draws: Philox4x32-10, key (seed, epoch), counter (batch, patch, stream, index); stream 0: the patch's draws,
 // 1: class perturbation of an object (index: its row in the dataset's object table), 2: pixel noise (index: pixel).
-// Stream 0's indices: 0 D4, 1..4 the photometric ops, 5 histogram matching.
+// 3: the lists of the spatial ops (index 0..9: shadow vertex v of polygon v / 5, words 0, 1 = x, y; index 16 + k: haze point
+// k, words 0, 1 = x, y).
+// Stream 0's indices: 0 D4, 1..4 the photometric ops, 5 histogram matching, 6 and 7 the spatial ops:
+//   6: word 0 shadow applies (u < 0.5), 1 two polygons (u < 0.5) else one, 2 fog applies (u < 0.5), 3 fog_coef = 0.3 + 0.7 u
+//   7: word 0 CLAHE's clip = 1 + 3 u, 1 downscale applies (u < 0.5), 2 the blur OneOf fires (u < 0.2), 3 median (u < 0.5) else box
+// (whether CLAHE applies is the colour OneOf's own draw, index 2 words 2 and 3, as before).
 #include <cmath>
 #include <cstdint>
 
@@ -23,7 +34,9 @@
 
 namespace {
 
-constexpr int TB = 256;                    // threads of every workgroup here
+constexpr int TB = 256;                    // threads of every workgroup here but k_aug_spatial's
+constexpr int TS = 1024;                   // threads of a k_aug_spatial workgroup (one patch)
+constexpr int MAXH = MPP_AUG_MAX_HAZE;
 constexpr int BAND = MPP_TRAIN_BAND;
 constexpr int MAXO = MPP_TRAIN_MAX_OBJ;
 constexpr double PI = 3.14159265358979311600;   // np.pi
@@ -84,6 +97,13 @@ struct PatchAug {
   int color = 0; float shift[3] = {0.f, 0.f, 0.f};   // 1 RGB shift, 2 to gray
   int noise = 0; double sigma = 0.0;
   int hm = 0, tmpl = 0; double blend = 0.0;          // histogram matching to image tmpl
+  // MPP_AUG_SPATIAL
+  int shadow = 0, n_poly = 0;                        // RandomShadow with n_poly polygons
+  int fog = 0; double fog_coef = 0.0;                // RandomFog
+  int clahe = 0; double clip = 0.0;                  // CLAHE (the colour OneOf's first member)
+  int down = 0;                                      // Downscale(0.9)
+  int blur = 0;                                      // 1 MedianBlur(3), 2 Blur(3)
+  __device__ bool spatial() const { return shadow | fog | clahe | down | blur; }
 };
 
 // the three draws of histogram matching (HistogramMatching(blend_ratio (0.1, 0.75), p 0.5), data/augmentation.py:26-29)
@@ -97,7 +117,8 @@ __device__ __forceinline__ void hist_draws(const Rng &g, int n_images, PatchAug 
 
 // albumentations' defaults (RandomRotate90, Flip, ChannelShuffle, ChannelDropout((1, 1), fill 0), RandomBrightnessContrast
 // (0.2, 0.2, brightness_by_max), RGBShift(20, 20, 20), ToGray, GaussNoise(var_limit (10, 50), mean 0, per channel)),
-// composed as data/augmentation.py:22-72 lays them out; CLAHE, shadow, fog, downscale and blur are not built
+// composed as data/augmentation.py:22-72 lays them out; with MPP_AUG_SPATIAL also RandomShadow(), RandomFog(), CLAHE(),
+// Downscale(0.9, 0.9, nearest), OneOf([MedianBlur(3), Blur(3)], p 0.2), as DESIGN.md section 8 defines them
 __device__ PatchAug patch_draws(const Rng &g, int flags, int n_images) {
   PatchAug a;
   uint32_t d[4];
@@ -120,17 +141,66 @@ __device__ PatchAug patch_draws(const Rng &g, int flags, int n_images) {
   a.beta = (float)((unif(d[1]) * 0.4 - 0.2) * 255.0);
   if (unif(d[2]) < 0.5) {                                  // OneOf([CLAHE(), RGBShift()] (+ ToGray(p=0.1) when strong))
     const double w = unif(d[3]) * (strong ? 1.1 : 1.0);
-    a.color = w < 0.5 ? 0 : (w < 1.0 ? 1 : 2);            // 0: CLAHE, not built
+    a.color = w < 0.5 ? 0 : (w < 1.0 ? 1 : 2);            // 0: CLAHE (applied with MPP_AUG_SPATIAL only)
+    a.clahe = (flags & MPP_AUG_SPATIAL) && a.color == 0;
   }
   g.draw(0, 3, d);
   for (int ch = 0; ch < 3; ++ch) a.shift[ch] = (float)(unif(d[ch]) * 40.0 - 20.0);
   a.noise = unif(d[3]) < 0.5;                              // GaussNoise()
   g.draw(0, 4, d);
   a.sigma = sqrt(10.0 + unif(d[0]) * 40.0);
+  if (!(flags & MPP_AUG_SPATIAL)) return a;
+  g.draw(0, 6, d);
+  if (strong) {
+    a.shadow = unif(d[0]) < 0.5;                           // RandomShadow(): shadow_roi (0, 0.5, 1, 1), 1..2 polygons of 5
+    a.n_poly = a.shadow ? 1 + (unif(d[1]) < 0.5 ? 1 : 0) : 0;
+    a.fog = unif(d[2]) < 0.5;                              // RandomFog(): fog_coef U(0.3, 1), alpha_coef 0.08
+    a.fog_coef = 0.3 + unif(d[3]) * 0.7;
+  }
+  g.draw(0, 7, d);
+  a.clip = 1.0 + unif(d[0]) * 3.0;                         // CLAHE(): clip_limit U(1, 4), tile grid 8 x 8
+  if (strong) a.down = unif(d[1]) < 0.5;                   // Downscale(0.9, 0.9)
+  if (unif(d[2]) < 0.2) a.blur = unif(d[3]) < 0.5 ? 1 : 2; // OneOf([MedianBlur(3), Blur(3)], p 0.2)
   return a;
 }
 
-__device__ void photometric(const PatchAug &a, const Rng &g, int pix, float x[3]) {
+// randint(lo, hi), both ends included, from one word
+__device__ __forceinline__ int rand_int(uint32_t w, int lo, int hi) {
+  return min(hi, lo + (int)(unif(w) * (double)(hi - lo + 1)));
+}
+// shadow vertex v (0..9; polygon v / 5): x in [0, P], y in [P/2, P]
+__device__ __forceinline__ void shadow_vertex(const Rng &g, int P, int v, int &x, int &y) {
+  uint32_t d[4];
+  g.draw(3, (uint32_t)v, d);
+  x = rand_int(d[0], 0, P);
+  y = rand_int(d[1], P / 2, P);
+}
+// The haze points of RandomFog as albumentations' loop lists them: rounds index = 1, 2, ... of (hw / 10) * index points in
+// the window [midx, P - midx - hw] x [midy, P - midy - hw], which grows by 3 hw / 2 a side per round until it has passed the
+// patch by hw on both axes.  Returns their number (the same for every k) and, for k below it, point k.  The count depends
+// on (P, hw) alone; over every P <= 512 that is a multiple of 8 and every hw in 1 .. P / 3 its maximum is 51 (P = 512,
+// hw = 170: rounds of 17 and 34), so MPP_AUG_MAX_HAZE = 64 cannot be reached; the loop stops there all the same.
+__device__ __forceinline__ int fog_hw(int P, double coef) { return max(1, (int)((double)(P / 3) * coef)); }
+__device__ int haze_point(const Rng &g, int P, double coef, int k, int &x, int &y) {
+  const int hw = fog_hw(P, coef), per = hw / 10, dec = 3 * hw * P / (2 * P);
+  int midx = P / 2 - 2 * hw, midy = P / 2 - hw, n = 0;
+  for (int index = 1; (midx > -hw || midy > -hw) && n < MAXH; ++index) {
+    const int m = min(per * index, MAXH - n);
+    if (k >= n && k < n + m) {
+      uint32_t d[4];
+      g.draw(3, (uint32_t)(16 + k), d);
+      x = rand_int(d[0], midx, P - midx - hw);
+      y = rand_int(d[1], midy, P - midy - hw);
+    }
+    n += m;
+    midx -= dec;
+    midy -= dec;
+  }
+  return n;
+}
+
+// the ops between fog and CLAHE / downscale: channel shuffle | dropout, brightness / contrast, RGB shift | to gray
+__device__ __forceinline__ void photometric_color(const PatchAug &a, float x[3]) {
   if (a.chan_op == 1) {
     const int perm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
     const float y0 = x[perm[a.chan_arg][0]], y1 = x[perm[a.chan_arg][1]], y2 = x[perm[a.chan_arg][2]];
@@ -146,6 +216,8 @@ __device__ void photometric(const PatchAug &a, const Rng &g, int pix, float x[3]
     const float y = clip255(0.299f * x[0] + 0.587f * x[1] + 0.114f * x[2]);
     x[0] = x[1] = x[2] = y;
   }
+}
+__device__ __forceinline__ void photometric_noise(const PatchAug &a, const Rng &g, int pix, float x[3]) {
   if (a.noise) {
     uint32_t d[4];
     g.draw(2, (uint32_t)pix, d);
@@ -154,6 +226,43 @@ __device__ void photometric(const PatchAug &a, const Rng &g, int pix, float x[3]
     const double z[3] = {r0 * cos(t0), r0 * sin(t0), r1 * cos(t1)};
     for (int ch = 0; ch < 3; ++ch) x[ch] = clip255((float)((double)x[ch] + a.sigma * z[ch]));
   }
+}
+__device__ __forceinline__ void photometric(const PatchAug &a, const Rng &g, int pix, float x[3]) {
+  photometric_color(a, x);
+  photometric_noise(a, g, pix, x);
+}
+
+// where a patch is read from: its image and the top-left corner of the crop
+struct PatchSrc {
+  bool valid;
+  int tl_r, tl_c, H, W;
+  const uint8_t *im;
+};
+__device__ __forceinline__ PatchSrc patch_src(const mpp_train_data &data, const int32_t *desc, int b, int P) {
+  PatchSrc s;
+  const int img = desc[3 * b];
+  s.valid = img >= 0 && img < data.n_images;
+  s.tl_r = desc[3 * b + 1] - P / 2;
+  s.tl_c = desc[3 * b + 2] - P / 2;
+  s.H = s.valid ? data.img_hw[2 * img] : 0;
+  s.W = s.valid ? data.img_hw[2 * img + 1] : 0;
+  s.im = s.valid ? data.images + data.img_off[img] : nullptr;
+  return s;
+}
+// pixel (i, j) of the patch after D4 and histogram matching: a read at tl + (source pixel), zeros outside the image
+__device__ __forceinline__ void source_pixel(const PatchSrc &s, const PatchAug &aug, int flags, int P, int i, int j,
+                                             const float (*hm_lut)[256], float x[3]) {
+  int si = i, sj = j;
+  if (flags & MPP_AUG_GEOMETRIC) d4_inv(aug.rot, aug.flip, P, si, sj);
+  const int gr = s.tl_r + si, gc = s.tl_c + sj;
+  x[0] = x[1] = x[2] = 0.f;
+  if (s.valid && gr >= 0 && gr < s.H && gc >= 0 && gc < s.W) {
+    const uint8_t *p = s.im + ((size_t)gr * s.W + gc) * 3;
+    x[0] = (float)p[0]; x[1] = (float)p[1]; x[2] = (float)p[2];
+  }
+  if (aug.hm)                                               // one rounding: the blend is formed in float64
+    for (int ch = 0; ch < 3; ++ch)
+      x[ch] = clip255((float)(aug.blend * (double)hm_lut[ch][(int)x[ch]] + (1.0 - aug.blend) * (double)x[ch]));
 }
 
 // exclusive block-wide prefix of one flag per thread (TB threads); returns the total
@@ -262,9 +371,337 @@ __global__ __launch_bounds__(TB) void k_hist_lut(mpp_train_data data, int P, con
   }
 }
 
+// ---- the spatial ops (MPP_AUG_SPATIAL) --------------------------------------------------------------------------------
+// The colour-space round trips run in float64 and round once to float32: a CLAHE bin is round(L* 255 / 100), and a float32
+// L* would flip bins that the float64 statement of the op does not.
+__device__ __forceinline__ double clip255d(double x) { return fmin(fmax(x, 0.0), 255.0); }
+
+// RandomShadow's pixel: RGB -> HLS (L = (max + min) / 2, hexcone H and S), L *= 0.5, HLS -> RGB
+__device__ void shadow_pixel(float x[3]) {
+  const double r = (double)x[0] / 255.0, g = (double)x[1] / 255.0, b = (double)x[2] / 255.0;
+  const double mx = fmax(r, fmax(g, b)), mn = fmin(r, fmin(g, b)), d = mx - mn;
+  const double L = (mx + mn) / 2;
+  const double L2 = L * 0.5;
+  if (d == 0.0) {
+    x[0] = x[1] = x[2] = (float)clip255d(L2 * 255.0);
+    return;
+  }
+  const double S = L < 0.5 ? d / (mx + mn) : d / (2.0 - mx - mn);
+  double h;
+  if (mx == r) h = (g - b) / d;
+  else if (mx == g) h = 2.0 + (b - r) / d;
+  else h = 4.0 + (r - g) / d;
+  h /= 6.0;
+  if (h < 0.0) h += 1.0;
+  const double q = L2 <= 0.5 ? L2 * (1.0 + S) : L2 + S - L2 * S, p = 2.0 * L2 - q;
+  const double off[3] = {1.0 / 3.0, 0.0, -1.0 / 3.0};
+  for (int ch = 0; ch < 3; ++ch) {
+    double t = h + off[ch];
+    if (t < 0.0) t += 1.0;
+    if (t >= 1.0) t -= 1.0;
+    double v;
+    if (t < 1.0 / 6.0) v = p + (q - p) * 6.0 * t;
+    else if (t < 0.5) v = q;
+    else if (t < 2.0 / 3.0) v = p + (q - p) * (2.0 / 3.0 - t) * 6.0;
+    else v = p;
+    x[ch] = (float)clip255d(v * 255.0);
+  }
+}
+
+// sRGB (gamma, D65) <-> CIE L*a*b* with OpenCV's float constants
+__device__ __forceinline__ double lab_f(double t) { return t > 0.008856 ? cbrt(t) : 7.787 * t + 16.0 / 116.0; }
+__device__ __forceinline__ double lab_finv(double f) { return f > 6.0 / 29.0 ? f * f * f : (f - 16.0 / 116.0) / 7.787; }
+__device__ void rgb_to_lab(const float x[3], double lab[3]) {
+  double lin[3];
+  for (int ch = 0; ch < 3; ++ch) {
+    const double c = (double)x[ch] / 255.0;
+    lin[ch] = c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4);
+  }
+  const double X = (0.412453 * lin[0] + 0.357580 * lin[1] + 0.180423 * lin[2]) / 0.950456;
+  const double Y = 0.212671 * lin[0] + 0.715160 * lin[1] + 0.072169 * lin[2];
+  const double Z = (0.019334 * lin[0] + 0.119193 * lin[1] + 0.950227 * lin[2]) / 1.088754;
+  const double fx = lab_f(X), fy = lab_f(Y), fz = lab_f(Z);
+  lab[0] = Y > 0.008856 ? 116.0 * fy - 16.0 : 903.3 * Y;
+  lab[1] = 500.0 * (fx - fy);
+  lab[2] = 200.0 * (fy - fz);
+}
+__device__ void lab_to_rgb(const double lab[3], float x[3]) {
+  const double fy = (lab[0] + 16.0) / 116.0;
+  const double Y = lab[0] > 903.3 * 0.008856 ? fy * fy * fy : lab[0] / 903.3;
+  const double fy2 = lab_f(Y);                                // (= fy above the knee)
+  const double X = lab_finv(lab[1] / 500.0 + fy2) * 0.950456, Z = lab_finv(fy2 - lab[2] / 200.0) * 1.088754;
+  const double lin[3] = {3.240479 * X - 1.537150 * Y - 0.498535 * Z, -0.969256 * X + 1.875991 * Y + 0.041556 * Z,
+                         0.055648 * X - 0.204043 * Y + 1.057311 * Z};
+  for (int ch = 0; ch < 3; ++ch) {
+    const double c = lin[ch] <= 0.0031308 ? 12.92 * lin[ch] : 1.055 * pow(lin[ch], 1.0 / 2.4) - 0.055;
+    x[ch] = (float)clip255d(c * 255.0);
+  }
+}
+// CLAHE's 8-bit lightness
+__device__ __forceinline__ int lab_l8(double L) { return min(255, max(0, (int)rint(L * 255.0 / 100.0))); }
+
+// side of fog's box mean, radius of its discs
+__device__ __forceinline__ int fog_hw2(int P, double coef) { return max((int)((double)(P / 3) * coef), 10); }
+// BORDER_REFLECT_101
+__device__ __forceinline__ int reflect101(int t, int n) { return t < 0 ? -t : (t >= n ? 2 * (n - 1) - t : t); }
+// Downscale(0.9), nearest both ways: the source of output index t
+__device__ __forceinline__ int down_src(int t, int P) {
+  const int d = (int)rint(0.9 * (double)P);
+  return min(P - 1, (int)floor((double)(t * d / P) / 0.9));
+}
+// how many stage outputs k_aug_spatial writes; the last one lies in buffer (n - 1) & 1
+__device__ __forceinline__ int spatial_final(const PatchAug &a, int P) {
+  const int n = 1 + ((a.fog && fog_hw2(P, a.fog_coef) / 10 > 1) ? 1 : 0) + a.clahe + a.down + (a.blur ? 1 : 0);
+  return (n - 1) & 1;
+}
+
+__device__ __forceinline__ void swap_ptr(float *&a, float *&b) {
+  float *t = a;
+  a = b;
+  b = t;
+}
+__device__ __forceinline__ void sort2(float &a, float &b) {
+  const float lo = fminf(a, b), hi = fmaxf(a, b);
+  a = lo;
+  b = hi;
+}
+
+// One workgroup per patch; ws [B][2][3][P][P] float32.  P % 8 == 0, 32 <= P <= 512 (checked by mpp_train_batch).
+__global__ __launch_bounds__(TS) void k_aug_spatial(mpp_train_data data, int P, const int32_t *desc, int flags, uint32_t seed,
+                                                    uint32_t epoch, uint32_t batch, const float *lut, float *ws) {
+  __shared__ uint32_t hist[64 * 256];              // CLAHE: the 8 x 8 tiles' histograms, then their tables in place
+  __shared__ float hm_lut[3][256];
+  __shared__ int16_t poly[2][5][2];
+  __shared__ int16_t haze[MAXH][2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const Rng g{seed, epoch, batch, (uint32_t)b};
+  const PatchAug aug = patch_draws(g, flags, data.n_images);
+  if (!aug.spatial()) return;
+  const PatchSrc src = patch_src(data, desc, b, P);
+  const int PP = P * P;
+  float *const base = ws + (size_t)b * 6 * PP;   // the two buffers; a stage reads in and writes out, then they swap
+  float *in = base + (size_t)3 * PP, *out = base;
+
+  if (aug.hm)
+    for (int k = tid; k < 3 * 256; k += TS) hm_lut[k >> 8][k & 255] = lut[(size_t)b * 768 + k];
+  if (aug.shadow && tid < 5 * aug.n_poly) {
+    int x, y;
+    shadow_vertex(g, P, tid, x, y);
+    poly[tid / 5][tid % 5][0] = (int16_t)x;
+    poly[tid / 5][tid % 5][1] = (int16_t)y;
+  }
+  int n_haze = 0;
+  if (aug.fog) {
+    int x = 0, y = 0;
+    n_haze = haze_point(g, P, aug.fog_coef, tid, x, y);
+    if (tid < n_haze) {
+      haze[tid][0] = (int16_t)x;
+      haze[tid][1] = (int16_t)y;
+    }
+  }
+  __syncthreads();
+
+  // stage 1: source, histogram matching, shadow, the fog's discs; without a box mean also the colour ops
+  const int hw2 = fog_hw2(P, aug.fog_coef), rad = hw2 / 2, box = aug.fog ? hw2 / 10 : 0;
+  const double fog_keep = 1.0 - 0.08 * aug.fog_coef;
+  for (int idx = tid; idx < PP; idx += TS) {
+    const int i = idx / P, j = idx % P;
+    float x[3];
+    source_pixel(src, aug, flags, P, i, j, hm_lut, x);
+    if (aug.shadow && 2 * i >= P) {
+      bool inside = false;
+      const double y = (double)i, xq = (double)j;
+      for (int m = 0; m < aug.n_poly; ++m) {
+        bool c = false;
+        int q = 4;
+        for (int e = 0; e < 5; ++e) {                // the even-odd rule of csrc/mpp_classics.hpp on the pixel centre
+          const double ye = poly[m][e][1], yq = poly[m][q][1], xe = poly[m][e][0], xj = poly[m][q][0];
+          if ((((ye <= y) && (y < yq)) || ((yq <= y) && (y < ye))) && (xq < (xj - xe) * (y - ye) / (yq - ye) + xe)) c = !c;
+          q = e;
+        }
+        inside = inside || c;
+      }
+      if (inside) shadow_pixel(x);
+    }
+    if (aug.fog) {
+      double f = 1.0;
+      for (int k = 0; k < n_haze; ++k) {
+        const int dx = j - (haze[k][0] + rad), dy = i - (haze[k][1] + rad);
+        if (dx * dx + dy * dy <= rad * rad) f = f * fog_keep;
+      }
+      if (f != 1.0)                                  // v <- 255 alpha + (1 - alpha) v, once per covering disc
+        for (int ch = 0; ch < 3; ++ch) x[ch] = (float)clip255d(255.0 - (255.0 - (double)x[ch]) * f);
+    }
+    if (box <= 1) photometric_color(aug, x);
+    for (int ch = 0; ch < 3; ++ch) out[ch * PP + idx] = x[ch];
+  }
+  swap_ptr(in, out);
+
+  // stage 2: the fog's box mean (side box, anchor box / 2, BORDER_REFLECT_101), then the colour ops
+  if (box > 1) {
+    __syncthreads();
+    const float inv = 1.0f / (float)(box * box);
+    for (int idx = tid; idx < PP; idx += TS) {
+      const int i = idx / P, j = idx % P;
+      float x[3] = {0.f, 0.f, 0.f};
+      for (int di = 0; di < box; ++di) {
+        const int row = reflect101(i + di - box / 2, P) * P;
+        for (int dj = 0; dj < box; ++dj) {
+          const int at = row + reflect101(j + dj - box / 2, P);
+          for (int ch = 0; ch < 3; ++ch) x[ch] += in[ch * PP + at];
+        }
+      }
+      for (int ch = 0; ch < 3; ++ch) x[ch] = clip255(x[ch] * inv);
+      photometric_color(aug, x);
+      for (int ch = 0; ch < 3; ++ch) out[ch * PP + idx] = x[ch];
+    }
+    swap_ptr(in, out);
+  }
+
+  // stage 3: CLAHE on the 8-bit lightness
+  if (aug.clahe) {
+    const int ts = P / 8, area = ts * ts;
+    for (int k = tid; k < 64 * 256; k += TS) hist[k] = 0u;
+    __syncthreads();
+    for (int idx = tid; idx < PP; idx += TS) {
+      const int i = idx / P, j = idx % P;
+      const float x[3] = {in[idx], in[PP + idx], in[2 * PP + idx]};
+      double lab[3];
+      rgb_to_lab(x, lab);
+      atomicAdd(&hist[((i / ts) * 8 + j / ts) * 256 + lab_l8(lab[0])], 1u);
+    }
+    __syncthreads();
+    // a wave per tile, lane l owns bins 4 l .. 4 l + 3: clip, spread the excess, cumulate, scale
+    const int lane = tid & 63;
+    const uint32_t limit = (uint32_t)max(1, (int)(aug.clip * (double)area / 256.0));
+    for (int tile = tid >> 6; tile < 64; tile += TS / 64) {
+      uint32_t *h = hist + tile * 256 + 4 * lane;
+      uint32_t v[4], excess = 0u;
+      for (int q = 0; q < 4; ++q) {
+        v[q] = h[q];
+        if (v[q] > limit) {
+          excess += v[q] - limit;
+          v[q] = limit;
+        }
+      }
+      for (int m = 1; m < 64; m <<= 1) excess += (uint32_t)__shfl_xor((int)excess, m);
+      const uint32_t each = excess / 256u, rest = excess % 256u, step = rest ? max(256u / rest, 1u) : 1u;
+      uint32_t sum = 0u;
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t bin = 4u * lane + q;
+        v[q] += each + ((rest && bin % step == 0u && bin / step < rest) ? 1u : 0u);
+        sum += v[q];
+      }
+      uint32_t incl = sum;
+      for (int m = 1; m < 64; m <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, m);
+        if (lane >= m) incl += up;
+      }
+      uint32_t cum = incl - sum;
+      for (int q = 0; q < 4; ++q) {
+        cum += v[q];
+        h[q] = (uint32_t)min(255, (int)rint((double)cum * 255.0 / (double)area));
+      }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < PP; idx += TS) {
+      const int i = idx / P, j = idx % P;
+      float x[3] = {in[idx], in[PP + idx], in[2 * PP + idx]};
+      double lab[3];
+      rgb_to_lab(x, lab);
+      const int l8 = lab_l8(lab[0]);
+      const double tyf = (double)i / (double)ts - 0.5, txf = (double)j / (double)ts - 0.5;
+      const int ty = (int)floor(tyf), tx = (int)floor(txf);
+      const double ya = tyf - (double)ty, xa = txf - (double)tx;
+      const int ty1 = max(ty, 0), ty2 = min(ty + 1, 7), tx1 = max(tx, 0), tx2 = min(tx + 1, 7);
+      const double l11 = hist[(ty1 * 8 + tx1) * 256 + l8], l12 = hist[(ty1 * 8 + tx2) * 256 + l8];
+      const double l21 = hist[(ty2 * 8 + tx1) * 256 + l8], l22 = hist[(ty2 * 8 + tx2) * 256 + l8];
+      const double res = (l11 * (1.0 - xa) + l12 * xa) * (1.0 - ya) + (l21 * (1.0 - xa) + l22 * xa) * ya;
+      lab[0] = res * 100.0 / 255.0;
+      lab_to_rgb(lab, x);
+      for (int ch = 0; ch < 3; ++ch) out[ch * PP + idx] = x[ch];
+    }
+    swap_ptr(in, out);
+  }
+
+  // stage 4: Downscale(0.9), a gather
+  if (aug.down) {
+    __syncthreads();
+    for (int idx = tid; idx < PP; idx += TS) {
+      const int at = down_src(idx / P, P) * P + down_src(idx % P, P);
+      for (int ch = 0; ch < 3; ++ch) out[ch * PP + idx] = in[ch * PP + at];
+    }
+    swap_ptr(in, out);
+  }
+
+  // stage 5: MedianBlur(3) (BORDER_REPLICATE) or Blur(3) (BORDER_REFLECT_101)
+  if (aug.blur) {
+    __syncthreads();
+    for (int idx = tid; idx < PP; idx += TS) {
+      const int i = idx / P, j = idx % P;
+      int rows[3], cols[3];
+      for (int d = 0; d < 3; ++d) {
+        rows[d] = (aug.blur == 1 ? min(max(i + d - 1, 0), P - 1) : reflect101(i + d - 1, P)) * P;
+        cols[d] = aug.blur == 1 ? min(max(j + d - 1, 0), P - 1) : reflect101(j + d - 1, P);
+      }
+      for (int ch = 0; ch < 3; ++ch) {
+        float v[9];
+        for (int d = 0; d < 9; ++d) v[d] = in[ch * PP + rows[d / 3] + cols[d % 3]];
+        float r;
+        if (aug.blur == 1) {                        // the median of nine by a 19-exchange network
+          sort2(v[1], v[2]); sort2(v[4], v[5]); sort2(v[7], v[8]); sort2(v[0], v[1]); sort2(v[3], v[4]); sort2(v[6], v[7]);
+          sort2(v[1], v[2]); sort2(v[4], v[5]); sort2(v[7], v[8]); sort2(v[0], v[3]); sort2(v[5], v[8]); sort2(v[4], v[7]);
+          sort2(v[3], v[6]); sort2(v[1], v[4]); sort2(v[2], v[5]); sort2(v[4], v[7]); sort2(v[4], v[2]); sort2(v[6], v[4]);
+          sort2(v[4], v[2]);
+          r = v[4];
+        } else {
+          float acc = 0.f;
+          for (int d = 0; d < 9; ++d) acc += v[d];
+          r = clip255(acc / 9.0f);
+        }
+        out[ch * PP + idx] = r;
+      }
+    }
+    swap_ptr(in, out);
+  }
+}
+
+// what patch_draws gives for every patch of a batch, for tests and tools (mpp_train_aug_params)
+static_assert(sizeof(mpp_aug_record) == 416, "mpp_aug_record: hip_api.AUG_RECORD_DTYPE restates this layout");
+__global__ void k_aug_params(int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P, int n_images,
+                             mpp_aug_record *out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const Rng g{seed, epoch, batch, (uint32_t)b};
+  const PatchAug a = patch_draws(g, flags, n_images);
+  mpp_aug_record &r = out[b];
+  r.rot = a.rot; r.flip = a.flip; r.chan_op = a.chan_op; r.chan_arg = a.chan_arg; r.bc = a.bc; r.color = a.color;
+  r.noise = a.noise; r.hm = a.hm; r.tmpl = a.tmpl; r.shadow = a.shadow; r.n_poly = a.n_poly; r.fog = a.fog; r.n_haze = 0;
+  r.clahe = a.clahe; r.downscale = a.down; r.blur = a.blur;
+  r.alpha = a.alpha; r.beta = a.beta;
+  for (int ch = 0; ch < 3; ++ch) r.shift[ch] = a.shift[ch];
+  r._pad = 0.f;
+  r.sigma = a.sigma; r.blend = a.blend; r.clip = a.clip; r.fog_coef = a.fog_coef;
+  for (int v = 0; v < 10; ++v) {
+    int x = 0, y = 0;
+    if (v < 5 * a.n_poly) shadow_vertex(g, P, v, x, y);
+    r.poly[v / 5][v % 5][0] = (int16_t)x;
+    r.poly[v / 5][v % 5][1] = (int16_t)y;
+  }
+  for (int k = 0; k < MAXH; ++k) {
+    int x = 0, y = 0;
+    const int n = a.fog ? haze_point(g, P, a.fog_coef, k, x, y) : 0;
+    if (k == 0) r.n_haze = n;
+    r.haze[k][0] = (int16_t)x;
+    r.haze[k][1] = (int16_t)y;
+  }
+}
+
+// SPAT: launched with MPP_AUG_SPATIAL; without it the kernel is compiled as it was before that flag existed
+template <bool SPAT>
 __global__ __launch_bounds__(TB) void k_train_batch(mpp_train_data data, mpp_train_labels lab, int B, int P, int nb,
                                                     const int32_t *desc, int flags, uint32_t seed, uint32_t epoch,
-                                                    uint32_t batch, const float *lut, mpp_train_out out) {
+                                                    uint32_t batch, const float *lut, const float *spat, mpp_train_out out) {
   __shared__ float hm_lut[3][256];                 // the patch's matching table (MPP_AUG_HISTMATCH)
   __shared__ int o_idx[MAXO];              // the object's row in the dataset table
   __shared__ int16_t o_r[MAXO], o_c[MAXO];         // centre in the (transformed) patch
@@ -277,13 +714,14 @@ __global__ __launch_bounds__(TB) void k_train_batch(mpp_train_data data, mpp_tra
   const int band = blockIdx.x, b = blockIdx.y;
   const Rng g{seed, epoch, batch, (uint32_t)b};
   const PatchAug aug = patch_draws(g, flags, data.n_images);
-  if (aug.hm)
+  // a patch with a spatial op: k_aug_spatial left its image, all but the noise, in the workspace
+  const float *fin = SPAT && aug.spatial() ? spat + ((size_t)b * 2 + spatial_final(aug, P)) * 3 * (size_t)P * P : nullptr;
+  if (aug.hm && !fin)
     for (int k = threadIdx.x; k < 3 * 256; k += TB) hm_lut[k >> 8][k & 255] = lut[(size_t)b * 768 + k];
+  const PatchSrc src = patch_src(data, desc, b, P);
   const int img = desc[3 * b];
-  const bool valid = img >= 0 && img < data.n_images;
-  const int tl_r = desc[3 * b + 1] - P / 2, tl_c = desc[3 * b + 2] - P / 2;
-  const int H = valid ? data.img_hw[2 * img] : 0, W = valid ? data.img_hw[2 * img + 1] : 0;
-  const uint8_t *im = valid ? data.images + data.img_off[img] : nullptr;
+  const bool valid = src.valid;
+  const int tl_r = src.tl_r, tl_c = src.tl_c;
 
   // the patch's objects, in annotation order
   int n = 0;
@@ -362,19 +800,14 @@ __global__ __launch_bounds__(TB) void k_train_batch(mpp_train_data data, mpp_tra
   for (int idx = threadIdx.x; idx < (r1 - r0) * P; idx += TB) {
     const int i = r0 + idx / P, j = idx % P;
     const size_t px = (size_t)b * PP + (size_t)i * P + j;
-    // the patch: a read at tl + (source pixel), zeros outside the image
-    int si = i, sj = j;
-    if (flags & MPP_AUG_GEOMETRIC) d4_inv(aug.rot, aug.flip, P, si, sj);
-    const int gr = tl_r + si, gc = tl_c + sj;
-    float x[3] = {0.f, 0.f, 0.f};
-    if (valid && gr >= 0 && gr < H && gc >= 0 && gc < W) {
-      const uint8_t *p = im + ((size_t)gr * W + gc) * 3;
-      x[0] = (float)p[0]; x[1] = (float)p[1]; x[2] = (float)p[2];
+    float x[3];
+    if (fin) {
+      for (int ch = 0; ch < 3; ++ch) x[ch] = fin[(size_t)ch * PP + (size_t)i * P + j];
+      photometric_noise(aug, g, i * P + j, x);
+    } else {
+      source_pixel(src, aug, flags, P, i, j, hm_lut, x);
+      if (flags & (MPP_AUG_MEDIUM | MPP_AUG_STRONG)) photometric(aug, g, i * P + j, x);
     }
-    if (aug.hm)                                               // one rounding: the blend is formed in float64
-      for (int ch = 0; ch < 3; ++ch)
-        x[ch] = clip255((float)(aug.blend * (double)hm_lut[ch][(int)x[ch]] + (1.0 - aug.blend) * (double)x[ch]));
-    if (flags & (MPP_AUG_MEDIUM | MPP_AUG_STRONG)) photometric(aug, g, i * P + j, x);
     for (int ch = 0; ch < 3; ++ch) out.patch[((size_t)b * 3 + ch) * PP + (size_t)i * P + j] = x[ch] / 255.0f;
 
     if (!shape) {
@@ -663,6 +1096,9 @@ void mpp_train_ws_free(TrainWs *ws) {
   if (ws->part) (void)hipFree(ws->part);
   if (ws->done) (void)hipFree(ws->done);
   if (ws->lut) (void)hipFree(ws->lut);
+  if (ws->spat) (void)hipFree(ws->spat);
+  ws->spat = nullptr;
+  ws->spat_floats = 0;
   ws->part = nullptr;
   ws->done = nullptr;
   ws->lut = nullptr;
@@ -685,8 +1121,31 @@ hipError_t mpp_launch_train_batch(hipStream_t st, TrainWs *ws, const mpp_train_d
     }
     hipLaunchKernelGGL(k_hist_lut, dim3(B), dim3(TB), 0, st, data, P, desc, ws->hist, seed, epoch, batch, ws->lut);
   }
-  hipLaunchKernelGGL(k_train_batch, dim3(nb, B), dim3(TB), 0, st, data, labels, B, P, nb, desc, flags, seed, epoch, batch,
-                     (const float *)ws->lut, out);
+  if (flags & MPP_AUG_SPATIAL) {
+    const size_t need = (size_t)B * 6 * P * P;              // a ping-pong pair of float32 patches per patch
+    if (ws->spat_floats < need) {
+      if (ws->spat) (void)hipFree(ws->spat);
+      ws->spat = nullptr;
+      ws->spat_floats = 0;
+      hipError_t e = hipMalloc((void **)&ws->spat, need * sizeof(float));
+      if (e != hipSuccess) return e;
+      ws->spat_floats = need;
+    }
+    hipLaunchKernelGGL(k_aug_spatial, dim3(B), dim3(TS), 0, st, data, P, desc, flags, seed, epoch, batch,
+                       (const float *)ws->lut, ws->spat);
+  }
+  if (flags & MPP_AUG_SPATIAL)
+    hipLaunchKernelGGL(k_train_batch<true>, dim3(nb, B), dim3(TB), 0, st, data, labels, B, P, nb, desc, flags, seed, epoch,
+                       batch, (const float *)ws->lut, (const float *)ws->spat, out);
+  else
+    hipLaunchKernelGGL(k_train_batch<false>, dim3(nb, B), dim3(TB), 0, st, data, labels, B, P, nb, desc, flags, seed, epoch,
+                       batch, (const float *)ws->lut, (const float *)nullptr, out);
+  return hipGetLastError();
+}
+
+hipError_t mpp_launch_aug_params(hipStream_t st, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P,
+                                 int n_images, mpp_aug_record *out) {
+  hipLaunchKernelGGL(k_aug_params, dim3((B + 63) / 64), dim3(64), 0, st, flags, seed, epoch, batch, B, P, n_images, out);
   return hipGetLastError();
 }
 

@@ -16,6 +16,8 @@ struct TrainWs {
   unsigned *done = nullptr;          // workgroups finished; the last one reduces the partials and resets it to 0
   float *lut = nullptr;              // [lut_patches][3][256] histogram-matching tables of one batch (MPP_AUG_HISTMATCH)
   size_t lut_patches = 0;
+  float *spat = nullptr;             // [B][2][3][P][P] the patch buffers of k_aug_spatial (MPP_AUG_SPATIAL)
+  size_t spat_floats = 0;
   const uint32_t *hist = nullptr;    // [hist_images][3][256] of the resident images, borrowed (mpp_train_set_histograms)
   int hist_images = 0;
 };
@@ -25,6 +27,8 @@ void mpp_train_ws_free(TrainWs *ws);
 hipError_t mpp_launch_train_batch(hipStream_t st, TrainWs *ws, const mpp_train_data &data, const mpp_train_labels &labels,
                                   int B, int P, const int32_t *desc, int flags, uint32_t seed, uint32_t epoch, uint32_t batch,
                                   const mpp_train_out &out);
+hipError_t mpp_launch_aug_params(hipStream_t st, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P,
+                                 int n_images, mpp_aug_record *out);
 
 // error-density resampling and the image histograms (csrc/mpp_resample.hip); the C entries in mpp_api.hip check the arguments
 hipError_t mpp_launch_image_histograms(hipStream_t st, const mpp_train_data &data, uint32_t *hist);

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
     "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
     "mpp_image_histograms", "mpp_train_set_histograms", "mpp_posnet_error_map", "mpp_density_prefix", "mpp_density_anchors",
-    "mpp_abi_version",
+    "mpp_train_aug_params", "mpp_abi_version",
 ]
 
 
@@ -77,6 +77,15 @@ class TrainOutC(C.Structure):
 
 #: mpp_train_batch flags (include/mpp_hip.h MPP_AUG_*) and its geometry
 AUG_GEOMETRIC, AUG_MEDIUM, AUG_STRONG, AUG_PERTURB, AUG_HISTMATCH = 1, 2, 4, 8, 16
+#: shadow, fog, CLAHE, downscale, median / box blur: the ops of the recipe that need neighbours or the whole patch
+AUG_SPATIAL = 32
+#: haze points of one patch (MPP_AUG_MAX_HAZE) and mpp_aug_record, what mpp_train_aug_params writes per patch
+AUG_MAX_HAZE = 64
+AUG_RECORD_DTYPE = np.dtype([(k, "<i4") for k in ("rot", "flip", "chan_op", "chan_arg", "bc", "color", "noise", "hm", "tmpl",
+                                                  "shadow", "n_poly", "fog", "n_haze", "clahe", "downscale", "blur")]
+                            + [("alpha", "<f4"), ("beta", "<f4"), ("shift", "<f4", (3,)), ("_pad", "<f4"),
+                               ("sigma", "<f8"), ("blend", "<f8"), ("clip", "<f8"), ("fog_coef", "<f8"),
+                               ("poly", "<i2", (2, 5, 2)), ("haze", "<i2", (AUG_MAX_HAZE, 2))], align=True)
 #: side of a density cell in pixels (mpp_posnet_error_map), the reference's rescale_fac 1/8
 DENSITY_CELL = 8
 TRAIN_BAND, TRAIN_MAX_OBJ = 16, 1024
@@ -175,6 +184,7 @@ def load_library(path: Optional[str] = None):
         "mpp_philox4x32": (None, [vp, vp, vp]),
         "mpp_image_histograms": (i32, [vp, C.POINTER(TrainDataC), vp]),
         "mpp_train_set_histograms": (i32, [vp, vp, i32]),
+        "mpp_train_aug_params": (i32, [vp, i32, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, i32, vp]),
         "mpp_posnet_error_map": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, dbl, vp, vp, vp]),
         "mpp_density_prefix": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp]),
         "mpp_density_anchors": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, C.c_uint32, vp]),
@@ -686,6 +696,17 @@ class MppContext:
             setattr(o, k, t.data_ptr())
         self._check(self._L.mpp_train_batch(self._h, C.byref(data), C.byref(labels), B, int(P), _ptr(desc), int(flags),
                                             int(seed) & 0xffffffff, int(epoch) & 0xffffffff, int(batch) & 0xffffffff, C.byref(o)))
+
+    def train_aug_params(self, flags: int, seed: int, epoch: int, batch: int, B: int, P: int, n_images: int) -> np.ndarray:
+        """``mpp_train_aug_params``: what ``train_batch`` with the same arguments draws for each of its B patches, as a
+        structured array of ``AUG_RECORD_DTYPE`` (synchronises the ctx's stream)"""
+        import torch
+        size = AUG_RECORD_DTYPE.itemsize
+        out = torch.zeros((int(B), size), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        self._check(self._L.mpp_train_aug_params(self._h, int(flags), int(seed) & 0xffffffff, int(epoch) & 0xffffffff,
+                                                 int(batch) & 0xffffffff, int(B), int(P), int(n_images), _ptr(out)))
+        self.synchronize()
+        return out.cpu().numpy().view(AUG_RECORD_DTYPE).reshape(int(B))
 
     def posnet_loss(self, out, vec, mask, dil, sums, res, grad=None, w=None, b=None):
         """``mpp_posnet_loss``: with w and b (float32 CUDA scalars) the training form with the divergence classifier"""

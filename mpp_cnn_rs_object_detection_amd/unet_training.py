@@ -4,7 +4,8 @@
 * a patch plan is a small ``(image, anchor row, anchor col)`` table drawn on the host with the recipe of the reference's
   ``data/patch_making.py:17-100`` and ``data/patch_samplers.py:39-200`` (uniform + object samplers), never rasterised;
 * ``mpp_train_batch`` (csrc/mpp_train.hip) builds a whole batch -- crop, augmentation, labels -- in one launch (two with
-  histogram matching, whose tables a small kernel builds first from the per-image histograms of the resident subset);
+  histogram matching, whose tables a small kernel builds first from the per-image histograms of the resident subset, and
+  one more for the patches that draw a spatial op of the recipe: shadow, fog, CLAHE, downscale, median / box blur);
 * PosNet's hard-example mining (``pos_net_model.py:234-269, 303-321``): every ``error_update_interval`` epochs each training
   image is forwarded, ``mpp_posnet_error_map`` keeps ``|target mask - predicted mask|`` per 8 x 8 cell as a uint8 density, and
   from then on half of the plan's anchors come from ``mpp_density_anchors`` (``ErrorDensities``);
@@ -106,12 +107,14 @@ def labels_struct(config: Dict, kind: str) -> hip_api.TrainLabelsC:
     return lab
 
 
-def aug_flags(config: Dict, kind: str, histograms: bool = False) -> int:
+def aug_flags(config: Dict, kind: str, histograms: bool = False, spatial: bool = False) -> int:
     """train-time flags of mpp_train_batch: D4 + photometric when ``augment_params`` is present (utils/training.py:102-106),
     the class perturbation for ShapeNet (shape_net_model.py:87-92).  ``histograms``: the caller builds its batches from a
     ``ResidentSubset`` through a ``BatchBuilder``, which hands the per-image histograms to the context; then, and only
     then, ``hist_match_images`` sets MPP_AUG_HISTMATCH (data/augmentation.py:26-29).  The flag without that table is an
-    error of mpp_train_batch, so a caller that has not said so gets the flags of the ops that need no table."""
+    error of mpp_train_batch, so a caller that has not said so gets the flags of the ops that need no table.
+    ``spatial``: with ``augment_params`` also MPP_AUG_SPATIAL, the ops of the recipe that are not one formula per pixel
+    (shadow, fog, CLAHE, downscale, median / box blur); it needs a patch size that is a multiple of 8 in 32..512."""
     flags = hip_api.AUG_PERTURB if kind == "shapenet" else 0
     aug = config.get("data_loader", {}).get("augment_params")
     if aug is not None:
@@ -119,7 +122,16 @@ def aug_flags(config: Dict, kind: str, histograms: bool = False) -> int:
         flags |= hip_api.AUG_STRONG if aug.get("aug_level", "medium") == "strong" else hip_api.AUG_MEDIUM
         if histograms and aug.get("hist_match_images"):
             flags |= hip_api.AUG_HISTMATCH
+        if spatial:
+            flags |= hip_api.AUG_SPATIAL
     return flags
+
+
+def aug_params(mctx: hip_api.MppContext, flags: int, seed: int, epoch: int, batch: int, B: int, P: int,
+               n_images: int) -> np.ndarray:
+    """What ``mpp_train_batch`` with the same key draws for each of the B patches of a batch: a structured array of
+    ``hip_api.AUG_RECORD_DTYPE`` (which ops apply, their parameters, the shadow vertices and the haze points)."""
+    return mctx.train_aug_params(flags, seed, epoch, batch, B, P, n_images)
 
 
 # ---- D4 of objects (host restatement of csrc/mpp_train.hip, used by the tests) ---------------------------------------------
@@ -651,7 +663,10 @@ def train_unet(config: Dict, kind: str, dataset: Optional[str] = None, device: i
     mctx = hip_api.MppContext(device)
     mctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
     builder = BatchBuilder(mctx, labels_struct(config, kind), P, device)
-    flags_train = aug_flags(config, kind, histograms=True)
+    flags_train = aug_flags(config, kind, histograms=True, spatial=True)
+    if flags_train & hip_api.AUG_SPATIAL and (P % 8 or not 32 <= P <= 512):
+        raise NotImplementedError(f"data_loader.patch_maker_params.patch_size = {P}: the augmentation recipe (CLAHE's 8 x 8 "
+                                  "tiles, the fog's haze list) is built for multiples of 8 in 32..512")
     train_data = ResidentSubset(dataset, "train", device)
     val_data = ResidentSubset(dataset, "val", device)
     rng = np.random.default_rng(SEED)

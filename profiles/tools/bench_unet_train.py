@@ -5,10 +5,12 @@
 * one step split by device events: batch build, forward, loss, backward, Adam;
 * A/B in the same process: the same step with the losses written as plain torch ops (pos_loss.py / pixel_ce_loss.py);
 * ``--no-histmatch``: the same steps without MPP_AUG_HISTMATCH (what the batch build cost before histogram matching);
+* ``--no-spatial``: the same steps without MPP_AUG_SPATIAL (what it cost before shadow, fog, CLAHE, downscale and blur);
+* ``--build-repeats N``: N more timings of the batch build alone (device events around 20 builds each), for its spread;
 * ``--error-update``: one error update of PosNet on the same data (forward of every image + mpp_posnet_error_map, then the
   prefix tables) and one patch plan of the shipped size with density rows (mpp_density_anchors), next to a training epoch.
 
-    python profiles/tools/bench_unet_train.py [--steps 20] [--warmup 5] [--no-histmatch] [--error-update]
+    python profiles/tools/bench_unet_train.py [--steps 20] [--warmup 5] [--no-histmatch] [--no-spatial] [--error-update]
 """
 import argparse
 import json
@@ -55,6 +57,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-histmatch", action="store_true")
+    ap.add_argument("--no-spatial", action="store_true")
+    ap.add_argument("--build-repeats", type=int, default=0)
     ap.add_argument("--error-update", action="store_true")
     args = ap.parse_args()
     torch.manual_seed(0)
@@ -74,7 +78,7 @@ def main():
     for kind in ("posnet", "shapenet"):
         cfg = ut.shipped_config(kind)
         bld = ut.BatchBuilder(mctx, ut.labels_struct(cfg, kind), P, 0)
-        flags = ut.aug_flags(cfg, kind, histograms=not args.no_histmatch)
+        flags = ut.aug_flags(cfg, kind, histograms=not args.no_histmatch, spatial=not args.no_spatial)
         net = (unet.PosNet() if kind == "posnet" else unet.ShapeNet()).cuda().train()
         conv = torch.nn.Conv2d(1, 1, 1).cuda()
         opt = torch.optim.Adam(list(net.parameters()) + list(conv.parameters()), lr=1e-3)
@@ -123,6 +127,20 @@ def main():
             results[name] = {"ms_per_step": ms, "patches_per_s": B / ms * 1e3,
                              "split_ms": dict(zip(["batch_build", "forward", "loss", "backward", "adam"], split.round(3).tolist()))}
             print(json.dumps({name: results[name]}), flush=True)
+        if args.build_repeats:
+            times = []
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for r in range(args.build_repeats + 1):                # (the first one warms up)
+                e0.record()
+                for i in range(20):
+                    bld.build(data, desc, flags, 42, 0, i)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1) / 20)
+            t = np.array(times[1:])
+            print(json.dumps({f"{kind}_batch_build_ms": {"flags": flags, "median": round(float(np.median(t)), 4),
+                                                         "min": round(float(t.min()), 4), "max": round(float(t.max()), 4),
+                                                         "repeats": len(t)}}), flush=True)
     bld.check()
     if args.error_update:
         error_update(data, mctx, results["posnet_fused"]["ms_per_step"])
