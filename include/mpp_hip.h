@@ -497,6 +497,24 @@ typedef struct mpp_aug_record {
 int mpp_train_aug_params(mpp_ctx *ctx, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P, int n_images,
                          mpp_aug_record *out);
 
+/* ---- dataset translation: the anti-aliased rescale (csrc/mpp_rescale.hip) ------------------------------------------------
+ * What data/translation/translate_DOTA.py:181 and translate_COWC.py:52 compute per image, skimage 0.18.1
+ * rescale(image / 255, scale, anti_aliasing=True, multichannel=True) followed by plt.imsave, as a generic separable
+ * resampler.  The caller folds the Gaussian blur (mirror boundary) and the bilinear interpolation of each axis into a table
+ * of (source index, weight) pairs per output row and per output column; then, in float64,
+ *   v[i][j][c]   = sum_t row_w[i][t] * ( sum_s col_w[j][s] * src[row_idx[i][t]][col_idx[j][s]][c] / 255 ),  t, s ascending
+ *   out[i][j][c] = (uint8)(255 * min(max(v, 0), 1))            -- truncation, as plt.imsave stores it
+ * src: uint8 [H][W][3], device, rows src_pitch bytes apart (>= 3 W); row_idx / row_w [oh][row_taps] and col_idx / col_w
+ * [ow][col_taps]: HOST arrays, read before the call returns, every index inside the image (checked); out: uint8
+ * [oh][ow][3], device, contiguous; out_f64 (NULL-able): v, float64 [oh][ow][3], device.  H * W * 3 may reach 2^31.
+ * The horizontally filtered rows are kept in a workspace of the ctx (grown on demand) for one band of output rows at a
+ * time; tables plus band stay within workspace_limit bytes (too small for one output row: an error), and neither out nor
+ * out_f64 depends on the bands.  Option rescale_bands: the bands of the last call.  Launches on the ctx's stream,
+ * asynchronous. */
+int mpp_rescale(mpp_ctx *ctx, const uint8_t *src, int H, int W, int64_t src_pitch, const int32_t *row_idx,
+                const double *row_w, int oh, int row_taps, const int32_t *col_idx, const double *col_w, int ow, int col_taps,
+                uint8_t *out, double *out_f64, int64_t workspace_limit);
+
 void mpp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 int mpp_abi_version(void);
 

@@ -12,6 +12,10 @@ that includes histogram matching, the whole ``strong`` augmentation recipe (shad
 HIP kernels too) and, for PosNet, the error-density resampling of ``data_loader.error_update_interval``,
 whose maps land in ``<dataset base>/error_maps/<dataset>/train/<model_name>/``).  With ``torchrun --nproc-per-node N`` the images of the dataset are
 dealt to N GPUs (one gather of the results at the end; RCCL).
+
+``-p translate_dota -c <config>`` / ``-p translate_cowc -c <config>`` (no ``-m``) turn a raw DOTA or COWC download into the
+dataset layout all of the above read (``dataset_translation``; the rescale to the target GSD is a HIP kernel; example configs
+in ``model_configs/translation/``).
 """
 import argparse
 import json
@@ -45,6 +49,12 @@ def main():
         config = json.load(f)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     overwrite_results = args.overwrite and args.procedure != "train"
+
+    if args.procedure in ("translate_dota", "translate_cowc"):
+        from mpp_cnn_rs_object_detection_amd import dataset_translation
+        getattr(dataset_translation, args.procedure)(config, device=local_rank)
+        print("done !")
+        return
 
     if args.procedure == "train" and args.model in ("posnet", "shapenet"):
         from mpp_cnn_rs_object_detection_amd.unet_training import train_unet

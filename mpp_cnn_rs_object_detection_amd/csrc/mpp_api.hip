@@ -12,6 +12,7 @@
 #include "mpp_prepass.hpp"
 #include "mpp_detect.hpp"
 #include "mpp_train.hpp"
+#include "mpp_rescale.hpp"
 
 extern "C" size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 extern "C" size_t mpp_chain_static_lds_bytes(int waves);
@@ -178,6 +179,7 @@ struct mpp_ctx {
   int g_cells = 0, g_cap = 0, grid_min_points = 256;
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
+  RescaleWs rescale;                 // workspace of mpp_rescale (mpp_rescale.hip)
 };
 
 static int fail(mpp_ctx *c, int code, const char *fmt, ...) {
@@ -294,6 +296,7 @@ extern "C" int mpp_destroy(mpp_ctx *c) {
   if (c->d_route_until) (void)hipFree(c->d_route_until);
   mpp_detect_free(&c->detect);
   mpp_train_ws_free(&c->train);
+  mpp_rescale_ws_free(&c->rescale);
   if (c->dp) (void)hipFree(c->dp);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -415,6 +418,8 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "prepass_queues")) return c->prepass_queues;
   if (!strcmp(name, "prepass_queues_used")) return c->prepass_queues_used;
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
+  if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
+  if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)
@@ -1636,6 +1641,15 @@ extern "C" int mpp_train_aug_params(mpp_ctx *c, int flags, uint32_t seed, uint32
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, mpp_launch_aug_params(c->stream, flags, seed, epoch, batch, B, P, n_images, out));
   return 0;
+}
+// ---- dataset translation: the anti-aliased rescale (mpp_rescale.hip) --------------------------------------------------------
+extern "C" int mpp_rescale(mpp_ctx *c, const uint8_t *src, int H, int W, int64_t src_pitch, const int32_t *row_idx,
+                           const double *row_w, int oh, int row_taps, const int32_t *col_idx, const double *col_w, int ow,
+                           int col_taps, uint8_t *out, double *out_f64, int64_t workspace_limit) {
+  if (!c) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  return mpp_rescale_run(c->stream, &c->rescale, src, H, W, src_pitch, row_idx, row_w, oh, row_taps, col_idx, col_w, ow, col_taps,
+                         out, out_f64, workspace_limit, &c->err);
 }
 // ---- histogram matching and error-density resampling (mpp_train.hip, mpp_resample.hip) ----------------------------------
 static bool no_dataset(const mpp_train_data *data) {

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
     "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
     "mpp_image_histograms", "mpp_train_set_histograms", "mpp_posnet_error_map", "mpp_density_prefix", "mpp_density_anchors",
-    "mpp_train_aug_params", "mpp_abi_version",
+    "mpp_train_aug_params", "mpp_rescale", "mpp_abi_version",
 ]
 
 
@@ -89,6 +89,8 @@ AUG_RECORD_DTYPE = np.dtype([(k, "<i4") for k in ("rot", "flip", "chan_op", "cha
 #: side of a density cell in pixels (mpp_posnet_error_map), the reference's rescale_fac 1/8
 DENSITY_CELL = 8
 TRAIN_BAND, TRAIN_MAX_OBJ = 16, 1024
+#: default workspace limit of MppContext.rescale in bytes: tables plus one band of horizontally filtered rows
+RESCALE_WORKSPACE = 512 << 20
 
 
 PROPOSAL_DTYPE = np.dtype([("kernel", "<i4"), ("target", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -188,6 +190,7 @@ def load_library(path: Optional[str] = None):
         "mpp_posnet_error_map": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, dbl, vp, vp, vp]),
         "mpp_density_prefix": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp]),
         "mpp_density_anchors": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, C.c_uint32, vp]),
+        "mpp_rescale": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i64]),
         "mpp_abi_version": (i32, []),
     }
     for name, (res, args) in protos.items():
@@ -782,6 +785,35 @@ class MppContext:
             self._dev("cellcum", cellcum, torch.int32), self._dev("rowcum", rowcum, torch.int64),
             n, self._dev("rows", rows, torch.int32, (n, 2)), int(seed) & 0xffffffff, int(epoch) & 0xffffffff,
             self._dev("anchors", anchors, torch.int32, (n, 2))))
+
+    # -- dataset translation (device tensors; asynchronous on the ctx's stream) ----------------------------------------
+    def rescale(self, src, tables, out=None, out_f64=None, workspace_limit: int = RESCALE_WORKSPACE):
+        """``mpp_rescale``: src [H,W,3] uint8 CUDA tensor whose pixels are contiguous (rows may be further apart: a slice of
+        a wider image); tables = (row_idx [oh,Tr] int32, row_w [oh,Tr] float64, col_idx [ow,Tc] int32, col_w [ow,Tc]
+        float64), numpy, as ``dataset_translation.rescale_tables`` builds them; out [oh,ow,3] uint8 (made if None), out_f64
+        the unquantised float64 values (True: made; a tensor: written).  Returns out, or (out, out_f64)."""
+        import torch
+        if not (_is_torch(src) and src.is_cuda and src.device.index == self.device and src.dtype == torch.uint8 and src.dim() == 3
+                and src.shape[2] == 3 and src.stride(2) == 1 and src.stride(1) == 3 and (src.shape[0] == 1 or src.stride(0) >= 3 * src.shape[1])):
+            raise ValueError(f"rescale: src must be a [H,W,3] uint8 tensor on GPU {self.device} with contiguous pixels")
+        H, W = int(src.shape[0]), int(src.shape[1])
+        ri, rw, ci, cw = tables
+        ri, ci = np.ascontiguousarray(ri, dtype=np.int32), np.ascontiguousarray(ci, dtype=np.int32)
+        rw, cw = np.ascontiguousarray(rw, dtype=np.float64), np.ascontiguousarray(cw, dtype=np.float64)
+        if ri.ndim != 2 or ci.ndim != 2 or ri.shape != rw.shape or ci.shape != cw.shape:
+            raise ValueError("rescale: tables must be (row_idx, row_w, col_idx, col_w) with [n_out, taps] each")
+        (oh, tr), (ow, tc) = ri.shape, ci.shape
+        if out is None:
+            out = torch.empty((oh, ow, 3), dtype=torch.uint8, device=src.device)
+        if out_f64 is True:
+            out_f64 = torch.empty((oh, ow, 3), dtype=torch.float64, device=src.device)
+        elif out_f64 is False:
+            out_f64 = None
+        self._check(self._L.mpp_rescale(self._h, _ptr(src), H, W, int(src.stride(0)) if H > 1 else 3 * W, _ptr(ri), _ptr(rw), oh, tr,
+                                        _ptr(ci), _ptr(cw), ow, tc, self._dev("out", out, torch.uint8, (oh, ow, 3)),
+                                        None if out_f64 is None else self._dev("out_f64", out_f64, torch.float64, (oh, ow, 3)),
+                                        int(workspace_limit)))
+        return out if out_f64 is None else (out, out_f64)
 
     # -- evaluation --------------------------------------------------------------------------------
     def quad_iou(self, a, b) -> np.ndarray:

@@ -66,6 +66,25 @@ def rect_to_poly(center: Union[Tuple[int, int], np.ndarray], short: float, long:
     return local @ rot.T + np.asarray(center)
 
 
+def polygon_to_abw(poly: np.ndarray) -> np.ndarray:
+    """(short side a, long side b, angle in [0, pi)) of quadrilaterals [..., 4, 2] -> [..., 3]: the sides are the means of
+    opposite edges, the angle is atan2(v[1], v[0]) % pi of the vector v that joins the midpoints of the two long edges
+    (reference ``rectangle.py:112-126``, for a whole annotation file at once)."""
+    p = np.asarray(poly, dtype=np.float64)
+    assert p.shape[-2:] == (4, 2)
+
+    def norm(v):
+        return np.sqrt(v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1])
+    n1 = (norm(p[..., 0, :] - p[..., 1, :]) + norm(p[..., 2, :] - p[..., 3, :])) / 2
+    n2 = (norm(p[..., 1, :] - p[..., 2, :]) + norm(p[..., 3, :] - p[..., 0, :])) / 2
+    first = n1 < n2
+    v1 = (p[..., 2, :] + p[..., 1, :]) / 2 - (p[..., 0, :] + p[..., 3, :]) / 2
+    v2 = (p[..., 1, :] + p[..., 0, :]) / 2 - (p[..., 3, :] + p[..., 2, :]) / 2
+    v = np.where(first[..., None], v1, v2)
+    angle = np.arctan2(v[..., 1], v[..., 0]) % np.pi
+    return np.stack((np.where(first, n1, n2), np.where(first, n2, n1), angle), axis=-1)
+
+
 def wla_to_sra(a, b, angle):
     return (a + b) / 2, a / b, angle
 
