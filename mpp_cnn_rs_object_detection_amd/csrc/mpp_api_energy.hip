@@ -1,0 +1,251 @@
+// mpp_api_energy.hip -- the from-scratch side of the C ABI (mpp_scratch.hip, mpp_maps.hip, mpp_gather.hip, mpp_metrics.hip):
+// total energy, deltas, Papangelou, merge + scoring, naive initialisation, packing of detections, rotated IoU.
+#include "mpp_ctx.hpp"
+
+// Build the candidate grid of `tile` when its configuration is large enough to pay for four small launches; returns
+// the two device arrays through start / items (nullptr, nullptr: the kernels scan the whole configuration).
+static int scratch_grid(mpp_ctx *c, int tile, int n, const int32_t **start, const int32_t **items) {
+  *start = *items = nullptr;
+  if (c->grid_min_points <= 0 || n < c->grid_min_points) return 0;
+  const int ncell = c->hp.nx * c->hp.ny;
+  if (ncell <= 0) return 0;
+  if (c->g_cells.reserve(c->stream, ((size_t)2 * ncell + 1) * sizeof(int32_t)) != hipSuccess ||
+      c->g_items.reserve(c->stream, (size_t)c->cap * sizeof(int32_t)) != hipSuccess) return -2;
+  int32_t *g_start = (int32_t *)c->g_cells.p;
+  *start = g_start; *items = (const int32_t *)c->g_items.p;
+  mpp_launch_grid_build(c->stream, c->dp, c->d_tiles, tile, n, ncell, g_start, g_start + ncell + 1, (int32_t *)c->g_items.p);
+  return 0;
+}
+
+extern "C" int mpp_pack_detections(mpp_ctx *c, int n, const int32_t *tile_ids, const int32_t *anchors, int capacity,
+                                   double *out_dev, int32_t *count) {
+  if (!c || !c->have_maps || n <= 0 || n > c->n_tiles || !tile_ids || !anchors || capacity < 0 || !out_dev)
+    return fail(c, -1, "bad pack_detections arguments");
+  int rc = push_state(c);
+  if (rc) return rc;
+  DevBuf<int32_t> d_meta;
+  HIPCHK(c, d_meta.alloc((size_t)3 * n));
+  hipError_t e = hipMemcpyAsync(d_meta, tile_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_meta + n, anchors, (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(out_dev, 0, ((size_t)capacity + 1) * 7 * sizeof(double), c->stream);
+  double total = 0.0;
+  if (e == hipSuccess) {
+    mpp_launch_pack_detections(c->stream, c->d_tiles, n, d_meta, d_meta + n, capacity, out_dev);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, out_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  if (count) *count = (int32_t)total;
+  if ((int)total > capacity)
+    return fail(c, -4, "%d detections exceed the gather buffer's capacity %d", (int)total, capacity);
+  return 0;
+}
+
+extern "C" int mpp_total_energy(mpp_ctx *c, int tile, double *energy, double *vectors) {
+  int rc = check_tile(c, tile);
+  if (rc) return rc;
+  if ((rc = push_state(c))) return rc;
+  int32_t n = 0;
+  if ((rc = mpp_count(c, tile, &n))) return rc;
+  double e = 0.0;
+  if (n > 0) {
+    int nt = c->hp.model.n_unit + c->hp.model.n_pair;
+    DevBuf<double> d_e, d_v;
+    HIPCHK(c, d_e.alloc((size_t)n));
+    if (vectors) HIPCHK(c, d_v.alloc((size_t)n * nt));
+    const int32_t *gs, *gi;
+    if (scratch_grid(c, tile, n, &gs, &gi)) return fail(c, -2, "no device memory for the candidate grid");
+    mpp_launch_point_energies(c->stream, c->dp, c->d_tiles, tile, n, d_e, d_v, gs, gi);
+    std::vector<double> he(n);
+    hipError_t e1 = hipMemcpyAsync(he.data(), d_e, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipSuccess;
+    if (vectors) e2 = hipMemcpyAsync(vectors, d_v, (size_t)n * nt * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e3 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e1); HIPCHK(c, e2); HIPCHK(c, e3);
+    for (int i = 0; i < n; ++i) e += he[i];                      // same order as the reference's np.sum over points
+  }
+  if (energy) *energy = e;
+  return 0;
+}
+
+// shared body of mpp_delta_batch (dE != NULL) and mpp_delta_vectors (before/after/mask != NULL)
+static int delta_cases(mpp_ctx *c, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
+                       const int32_t *add_off, const int32_t *add_xy, const double *add_marks, double *dE, int stride,
+                       double *before, double *after, unsigned char *mask) {
+  int rc = check_tile(c, tile);
+  if (rc) return rc;
+  if ((rc = push_state(c))) return rc;
+  if (n_cases <= 0) return 0;
+  int32_t n = 0;
+  if ((rc = mpp_count(c, tile, &n))) return rc;
+  const int n_rem = rem_off[n_cases], n_add = add_off[n_cases];
+  for (int i = 0; i < n_rem; ++i)
+    if (rem[i] < 0 || rem[i] >= n) return fail(c, -6, "removal of slot %d: no such point (n=%d)", rem[i], n);  // KeyError
+  for (int i = 0; i < n_add; ++i)
+    if (add_xy[2 * i] < 0 || add_xy[2 * i] >= c->H || add_xy[2 * i + 1] < 0 || add_xy[2 * i + 1] >= c->W)
+      return fail(c, -5, "added point %d is outside the tile", i);
+  const int nt = c->hp.model.n_unit + c->hp.model.n_pair;
+  if (!dE) {
+    for (int i = 0; i < n_cases; ++i)
+      if (n + (add_off[i + 1] - add_off[i]) > stride)
+        return fail(c, -1, "delta_vectors: stride %d < n + additions of case %d (%d)", stride, i, n + add_off[i + 1] - add_off[i]);
+  }
+  const int32_t *gs, *gi;
+  if (scratch_grid(c, tile, n, &gs, &gi)) return fail(c, -2, "no device memory for the candidate grid");
+  DevBuf<int32_t> d_ro, d_r, d_ao, d_axy;
+  DevBuf<double> d_am, d_out, d_b, d_a;
+  DevBuf<unsigned char> d_m;
+  const size_t rows = dE ? 0 : (size_t)n_cases * stride;
+  HIPCHK(c, d_ro.alloc((size_t)n_cases + 1)); HIPCHK(c, d_ao.alloc((size_t)n_cases + 1));
+  HIPCHK(c, d_r.alloc((size_t)n_rem)); HIPCHK(c, d_axy.alloc((size_t)2 * n_add));
+  HIPCHK(c, d_am.alloc((size_t)3 * n_add));
+  if (dE) HIPCHK(c, d_out.alloc((size_t)n_cases));
+  else { HIPCHK(c, d_b.alloc(rows * nt)); HIPCHK(c, d_a.alloc(rows * nt)); HIPCHK(c, d_m.alloc(rows)); }
+  hipError_t e = hipSuccess;
+  auto up = [&](void *dst, const void *src, size_t bytes) {
+    if (bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+  };
+  up(d_ro, rem_off, (n_cases + 1) * sizeof(int32_t)); up(d_ao, add_off, (n_cases + 1) * sizeof(int32_t));
+  up(d_r, rem, n_rem * sizeof(int32_t)); up(d_axy, add_xy, 2 * (size_t)n_add * sizeof(int32_t));
+  up(d_am, add_marks, 3 * (size_t)n_add * sizeof(double));
+  if (e == hipSuccess) {
+    if (dE) {
+      mpp_launch_delta_batch(c->stream, c->dp, c->d_tiles, tile, n_cases, d_ro, d_r, d_ao, d_axy, d_am, d_out, gs, gi);
+      e = hipMemcpyAsync(dE, d_out, n_cases * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    } else {
+      mpp_launch_delta_vectors(c->stream, c->dp, c->d_tiles, tile, n_cases, d_ro, d_r, d_ao, d_axy, d_am, stride, d_b, d_a, d_m, gs, gi);
+      e = hipMemcpyAsync(before, d_b, rows * nt * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(after, d_a, rows * nt * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(mask, d_m, rows, hipMemcpyDeviceToHost, c->stream);
+    }
+  }
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
+extern "C" int mpp_delta_batch(mpp_ctx *c, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
+                               const int32_t *add_off, const int32_t *add_xy, const double *add_marks, double *dE) {
+  if (!dE && n_cases > 0) return fail(c, -1, "delta_batch: dE is NULL");
+  return delta_cases(c, tile, n_cases, rem_off, rem, add_off, add_xy, add_marks, dE, 0, nullptr, nullptr, nullptr);
+}
+extern "C" int mpp_delta_vectors(mpp_ctx *c, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
+                                 const int32_t *add_off, const int32_t *add_xy, const double *add_marks, int stride,
+                                 double *before, double *after, unsigned char *mask) {
+  if (n_cases > 0 && (!before || !after || !mask || stride <= 0)) return fail(c, -1, "bad delta_vectors arguments");
+  return delta_cases(c, tile, n_cases, rem_off, rem, add_off, add_xy, add_marks, nullptr, stride, before, after, mask);
+}
+
+extern "C" int mpp_papangelou(mpp_ctx *c, int tile, double *dE) {
+  int32_t n = 0;
+  int rc = mpp_count(c, tile, &n);
+  if (rc) return rc;
+  if (n == 0) return 0;
+  std::vector<int32_t> ro(n + 1), r(n), ao(n + 1, 0);
+  for (int i = 0; i <= n; ++i) ro[i] = i;
+  for (int i = 0; i < n; ++i) r[i] = i;
+  int32_t dummy_xy[2] = {0, 0};
+  double dummy_m[3] = {0, 0, 0};
+  rc = mpp_delta_batch(c, tile, n, ro.data(), r.data(), ao.data(), dummy_xy, dummy_m, dE);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i) dE[i] = -dE[i];     // E(with u) - E(without u), energy_point_set.py:108-110
+  return 0;
+}
+
+// merge_patches(method='distance') for every tile of the ctx at once (data_loaders.py:122-161): each tile holds the
+// aggregated detections of one image on that image's score maps.  Papangelou of every point, the dedupe walk, the
+// removals (EPointsSet.remove order), Papangelou of the survivors -- four launches for the whole batch, one copy back.
+#define MPP_MERGE_MAX_POINTS 8192
+extern "C" int mpp_merge_score(mpp_ctx *c, double distance, int cap, int32_t *n_out, int32_t *xy, double *marks, double *dE,
+                               int32_t *n_removed) {
+  if (!c || !n_out || cap < 0 || !(distance >= 0)) return fail(c, -1, "bad merge_score arguments");
+  if (!c->have_maps || !c->have_model) return fail(c, -1, "mpp_set_maps / mpp_set_model have not been called");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = push_state(c);
+  if (rc) return rc;
+  const int T = c->n_tiles;
+  std::vector<int32_t> n0(T);
+  HIPCHK(c, hipMemcpyAsync(n0.data(), c->n, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int max_n = 0;
+  for (int t = 0; t < T; ++t) max_n = n0[t] > max_n ? n0[t] : max_n;
+  if (max_n > MPP_MERGE_MAX_POINTS || (size_t)((c->cap + 7) & ~7) * 17 > (size_t)MPP_DEDUPE_LDS_MAX)      // (the walk's working set lives in LDS)
+    return fail(c, -4, "merge_score: a tile holds %d points (the device walk takes at most %d): merge it on the host", max_n,
+                MPP_MERGE_MAX_POINTS);
+  const size_t TC = (size_t)T * c->cap;
+  DevBuf<double> d_dE, ts, tr, ta;
+  DevBuf<int32_t> work, slot_of, tx, ty, d_rem, gs, gc, gi;       // (gs, gc, gi: the candidate grids, where they pay)
+  hipError_t e = hipSuccess;
+  auto A = [&](auto &buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
+  A(d_dE, TC); A(ts, TC); A(tr, TC); A(ta, TC);
+  A(work, TC); A(slot_of, TC); A(tx, TC); A(ty, TC); A(d_rem, (size_t)T);
+  std::vector<int32_t> h_rem(T, 0);
+  if (e == hipSuccess && max_n > 0) {
+    const int dist2 = (int)floor(distance * distance + 1e-9);
+    // the from-scratch energies look their neighbours up in per-tile candidate grids, built on the device before each of
+    // the two scorings (the removals in between move points)
+    const int ncell = c->hp.nx * c->hp.ny;
+    if (ncell > 0 && max_n >= 64) { A(gs, (size_t)T * (ncell + 1)); A(gc, (size_t)T * ncell); A(gi, TC); }
+    const bool grid = gs && gc && gi && e == hipSuccess;
+    if (e == hipSuccess) {
+      if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, max_n, ncell, c->cap, gs, gc, gi);
+      mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, max_n, c->cap, d_dE, grid ? gs.p : nullptr, grid ? gi.p : nullptr, ncell + 1, c->cap);
+      mpp_launch_dedupe_tiles(c->stream, c->d_tiles, T, max_n, c->cap, d_dE, dist2, work, slot_of, tx, ty, ts, tr, ta, d_rem);
+      if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, max_n, ncell, c->cap, gs, gc, gi);
+      mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, max_n, c->cap, d_dE, grid ? gs.p : nullptr, grid ? gi.p : nullptr, ncell + 1, c->cap);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_rem.data(), d_rem, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  if (e == hipSuccess) rc = mpp_get_points_all(c, cap, n_out, xy, marks);
+  if (e == hipSuccess && rc == 0 && dE && cap > 0 && max_n > 0) {
+    const int m = max_n < cap ? max_n : cap;
+    std::vector<double> h((size_t)T * m);
+    e = hipMemcpy2D(h.data(), (size_t)m * 8, d_dE, (size_t)c->cap * 8, (size_t)m * 8, T, hipMemcpyDeviceToHost);
+    for (int t = 0; t < T && e == hipSuccess; ++t)
+      for (int i = 0; i < n_out[t] && i < m; ++i) dE[(size_t)t * cap + i] = h[(size_t)t * m + i];
+  }
+  if (n_removed) for (int t = 0; t < T; ++t) n_removed[t] = h_rem[t];
+  HIPCHK(c, e);
+  return rc;
+}
+
+extern "C" int mpp_naive_init(mpp_ctx *c, double threshold, double nms_distance) {
+  if (!c) return -1;
+  int rc = push_state(c);
+  if (rc) return rc;
+  const int cand_cap = c->H * c->W;
+  DevBuf<unsigned long long> cand;
+  HIPCHK(c, cand.alloc((size_t)c->n_tiles * cand_cap));
+  mpp_launch_naive_init(c->stream, c->dp, c->d_tiles, c->n_tiles, threshold, nms_distance, cand, cand_cap);
+  hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  std::vector<int32_t> herr(c->n_tiles);
+  HIPCHK(c, hipMemcpy(herr.data(), c->errd, c->n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int t = 0; t < c->n_tiles; ++t)
+    if (herr[t]) return fail(c, -10 - herr[t], "naive init, tile %d: %s", t, chain_error_text(herr[t]));
+  return 0;
+}
+
+extern "C" int mpp_quad_iou(mpp_ctx *c, int n, const double *a, int m, const double *b, double *out, int on_device) {
+  if (!c || n < 0 || m < 0 || ((long long)n * m > 0 && (!a || !b || !out))) return fail(c, -1, "bad quad_iou arguments");
+  if ((long long)n * m == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (on_device) {
+    mpp_launch_quad_iou(c->stream, n, a, m, b, out);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  DevBuf<double> da, db, dout;
+  const size_t sa = (size_t)n * 8 * sizeof(double), sb = (size_t)m * 8 * sizeof(double), so = (size_t)n * m * sizeof(double);
+  if (da.alloc((size_t)n * 8) != hipSuccess || db.alloc((size_t)m * 8) != hipSuccess || dout.alloc((size_t)n * m) != hipSuccess)
+    return fail(c, -2, "quad_iou: device allocation failed");
+  if (hipMemcpyAsync(da, a, sa, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(db, b, sb, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(c, -2, "quad_iou: upload failed");
+  mpp_launch_quad_iou(c->stream, n, da, m, db, dout);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, dout, so, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, -2, "quad_iou: kernel or download failed");
+  return 0;
+}

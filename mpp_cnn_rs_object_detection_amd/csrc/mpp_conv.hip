@@ -17,6 +17,7 @@
 //     NHWC rows of 128 B.
 // HBM traffic: one read of the input (x 1.29 for the halo) and one write of the output; 72 FLOP per byte: MFMA-bound.
 #include "mpp_device.hpp"
+#include "mpp_launch.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

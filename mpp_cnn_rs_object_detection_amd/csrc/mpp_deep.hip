@@ -24,6 +24,7 @@
 
 #include "mpp_chain.hpp"
 #include "mpp_prepass.hpp"
+#include "mpp_launch.hpp"
 
 #define DEEP_NMAX_LIMIT 256      // most steps of one round (deeper rounds commit no more: the first conflict ends them)
 #define DEEP_CLIST 192         // candidate neighbours a wave collects before it evaluates them (>= 64: one cell's entries fit)

@@ -1,6 +1,6 @@
 // mpp_detect.hpp -- the CNN-only baseline's detection step (csrc/mpp_detect.hip): threshold + exact greedy distance NMS
 // over a whole score map, and the argmax mark classes at a list of pixels.  Host-side driver; the C entries
-// (mpp_detect_centers, mpp_mark_classes) are thin wrappers in mpp_api.hip.
+// (mpp_detect_centers, mpp_mark_classes) are thin wrappers in mpp_api_nets.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -8,6 +8,7 @@
 // (tile id, x, y, size, ratio, angle, 0 = room for a score).  HBM-bound and tiny (a few hundred 56-byte records per
 // tile); one workgroup per tile, the record offset of a tile is the sum of the counts of the tiles before it.
 #include "mpp_device.hpp"
+#include "mpp_launch.hpp"
 
 #define GATHER_RECORD 7
 

@@ -9,6 +9,7 @@
 //    the read (64 consecutive pixels of one channel) and the write (64 pixels x 32 classes = 8 KiB
 //    contiguous) are fully coalesced (shape_net_model.py:139-141 + data_loaders.py:54).
 #include "mpp_device.hpp"
+#include "mpp_launch.hpp"
 
 // ---- birth CDF ---------------------------------------------------------------------------------
 // (all tiles of a context in one launch: blockIdx.y / blockIdx.x / blockIdx.z = tile)

@@ -5,6 +5,7 @@
 // un-vendored clone, README.md:22-30).  One lane per (detection, ground-truth) pair; the clipper is the
 // Sutherland-Hodgman device function of the sampler's overlap prior.
 #include "mpp_device.hpp"
+#include "mpp_launch.hpp"
 
 // quad q[8] = x1 y1 .. x4 y4 -> counter-clockwise corner arrays, |area| returned
 __device__ __forceinline__ double load_ccw(const double *q, double *x, double *y) {

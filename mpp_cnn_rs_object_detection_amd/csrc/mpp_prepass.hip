@@ -12,6 +12,7 @@
 // (draw_head_q), or, for a birth, its ordinal in the records.
 #include "mpp_chain.hpp"
 #include "mpp_prepass.hpp"
+#include "mpp_launch.hpp"
 
 // the Philox key of chain `tile`, formed as the chain kernels form it (mpp_deep.hip, mpp_chain_body.inc)
 __device__ __forceinline__ void pre_key(const TileRef &t, unsigned long long seed, uint32_t chain0, int tile, uint32_t *k0,

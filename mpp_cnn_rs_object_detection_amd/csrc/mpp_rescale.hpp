@@ -1,5 +1,5 @@
 // mpp_rescale.hpp -- the anti-aliased rescale of dataset translation (csrc/mpp_rescale.hip): a separable resampler driven by
-// two host-built tap tables.  Host-side launcher; the C entry (mpp_rescale) is a thin wrapper in mpp_api.hip.
+// two host-built tap tables.  Host-side launcher; the C entry (mpp_rescale) is a thin wrapper in mpp_api_nets.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,6 +3,7 @@
 
 #include "mpp_chain.hpp"
 #include "mpp_split_merge.hpp"
+#include "mpp_launch.hpp"
 
 // WAVES waves per chain.  LPW == 0: one speculative step per wave, the wave's lanes cooperate on it.
 // LPW > 0 ("lane mode"): lanes 0..LPW-1 of every wave each evaluate their own step.  SPEC steps per round.

@@ -1,10 +1,11 @@
 // mpp_sampler_hbm.hip -- the one-wave-per-step chain with its state in device memory, for the chains that outgrow a
-// CU's LDS (see run_chain in mpp_api.hip for the routing, mpp_chain.hpp: carve_hbm for the layout and wave_lds_fence for
+// CU's LDS (see run_chain in mpp_api_chain.hip for the routing, mpp_chain.hpp: carve_hbm for the layout and wave_lds_fence for
 // the memory ordering).  Same body as mpp_chain_kernel (mpp_chain_body.inc), same Philox stream, same arithmetic: the
 // chain is the one an unlimited LDS would have run.
 #define MPP_STATE_HBM 1
 #include "mpp_chain.hpp"
 #include "mpp_split_merge.hpp"
+#include "mpp_launch.hpp"
 
 // WAVES 1 or 8 (one wave per step), generic pair loops (FAST = false); DIAG: traced runs and tape replay; SM: the split /
 // merge kernels and the classic image energies.  ws: the workspace, chain blockIdx.x at ws + blockIdx.x * ws_stride.

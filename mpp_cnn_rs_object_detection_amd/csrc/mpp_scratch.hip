@@ -12,6 +12,7 @@
 // the launch (PointsSet.get_potential_neighbors, point_set.py:111-145; the reductions are max / min, so the visiting
 // order does not change a bit of the result).
 #include "mpp_device.hpp"
+#include "mpp_launch.hpp"
 
 struct Grid {                 // CSR over the P->nx x P->ny cells of the tile: items[start[c] .. start[c+1]) = slots in cell c
   const int32_t *start;       // nullptr: no grid, scan all points
@@ -455,7 +456,7 @@ extern "C" void mpp_launch_dedupe_tiles(hipStream_t st, const TileRef *tiles, in
   hipLaunchKernelGGL(k_has_neighbour, dim3((max_n + WAVE - 1) / WAVE, n_tiles), dim3(64), 0, st, tiles, cap, dist2, work);
   const size_t lds = (size_t)((cap + 7) & ~7) * 17;          // flags + (index, position, score) of the flagged points
   static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void *)k_dedupe_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr_set = true; }
+  if (!attr_set) { (void)hipFuncSetAttribute((const void *)k_dedupe_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, MPP_DEDUPE_LDS_MAX); attr_set = true; }
   hipLaunchKernelGGL(k_dedupe_tiles, dim3(n_tiles), dim3(64), lds, st, tiles, cap, dE, dist2, (const int32_t *)work, slot_of, tx, ty,
                      ts, tr, ta, n_removed);
 }

@@ -294,7 +294,7 @@ __device__ inline void sm_step(const Chain &c, Rec &r, int ri, int n, double T, 
     Rect a0, a1;
     sm_split_rects(P, p0, r.aux0, r.aux1, r.as, r.ar, r.aa, &a0, &a1);
     {                         // room in the two target cells?  checked before anything changes, so that a chain that
-      int ci, cj;             // stops here can be continued with a larger cell capacity (mpp_api.hip: run_chain)
+      int ci, cj;             // stops here can be continued with a larger cell capacity (mpp_api_chain.hip: run_chain)
       const int cp = cell_index(c, p0.x, p0.y, &ci, &cj), c0 = cell_index(c, a0.x, a0.y, &ci, &cj),
                 c1 = cell_index(c, a1.x, a1.y, &ci, &cj);
       const int need0 = c0 != cp ? 1 : 0, need1 = 1 + (c1 == c0 ? need0 : 0);

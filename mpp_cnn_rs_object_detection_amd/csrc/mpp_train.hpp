@@ -1,6 +1,6 @@
 // mpp_train.hpp -- training the U-Nets (csrc/mpp_train.hip): the batch builder (crop, augmentation, labels) and the two
 // fused losses with their gradients.  Host-side launchers; the C entries (mpp_train_batch, mpp_posnet_loss,
-// mpp_shapenet_loss) are thin wrappers in mpp_api.hip.
+// mpp_shapenet_loss) are thin wrappers in mpp_api_nets.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,7 +30,7 @@ hipError_t mpp_launch_train_batch(hipStream_t st, TrainWs *ws, const mpp_train_d
 hipError_t mpp_launch_aug_params(hipStream_t st, int flags, uint32_t seed, uint32_t epoch, uint32_t batch, int B, int P,
                                  int n_images, mpp_aug_record *out);
 
-// error-density resampling and the image histograms (csrc/mpp_resample.hip); the C entries in mpp_api.hip check the arguments
+// error-density resampling and the image histograms (csrc/mpp_resample.hip); the C entries in mpp_api_nets.hip check the arguments
 hipError_t mpp_launch_image_histograms(hipStream_t st, const mpp_train_data &data, uint32_t *hist);
 hipError_t mpp_launch_error_map(hipStream_t st, int H, int W, int ldh, int ldw, const float *out, int cx0, int cy0, int x0,
                                 int x1, int y0, int y1, const int32_t *centers, int n, double max_distance, uint8_t *dens,
