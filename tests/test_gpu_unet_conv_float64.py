@@ -1,0 +1,241 @@
+"""The three hand-written kernels of the float32 score-map forward (csrc/mpp_conv.hip: ``k_conv3x3_c32``, ``k_conv3x3_stem``,
+``k_shapenet_heads`` and its window copy) against the float64 references and derived bounds of tests/unet_conv_ref.py, at
+the smallest shapes at which each mechanism of the kernels exists: the launcher's minimum, one tile, one past a tile, and
+one shape at which every workgroup of the persistent convolution runs two or three tiles and some waves of the heads run
+their loop twice (both asserted from the device's compute-unit count, not assumed).  Every output buffer the binding lets
+the caller provide is filled with NaN first: a store that never happens fails the comparison.  What must be exact (a
+repeated call, a source whose weights are zero, a pixel's independence of the tile, stage and workgroup that computed it,
+the window form of the heads) is compared bit for bit.  tests/test_unet_conv_ref_host.py pins the references and shows
+that the bounds are neither too tight for float32 nor loose enough to pass a wrong kernel."""
+import pytest
+import torch
+
+import unet_conv_ref as R
+from mpp_cnn_rs_object_detection_amd import hip_api
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -7.25
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = hip_api.MppContext(0)
+    c.set_stream(torch.cuda.current_stream().cuda_stream)
+    yield c
+    c.close()
+
+
+def nhwc(t):
+    """[1,C,H,W] on the device over NHWC memory (explicitly: with H or W of 1 torch calls any strides channels-last)"""
+    return t.cuda().permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def nan_map(H, W):
+    return torch.full((1, H, W, 32), float("nan"), device="cuda").permute(0, 3, 1, 2)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def dev(v):
+    return v.cuda() if torch.is_tensor(v) else v
+
+
+def run_c32(ctx, x, wp, kw):
+    """conv3x3_c32 of x [1, 32 or 64, H, W] (CPU or device) into a NaN-filled map"""
+    x0 = nhwc(x[:, :32])
+    x1 = nhwc(x[:, 32:]) if x.shape[1] == 64 else None
+    H, W = x.shape[2:]
+    out = nan_map(H, W)
+    got = ctx.conv3x3_c32(x0, wp, x1=x1, out=out, **{k: dev(v) for k, v in kw.items()})
+    torch.cuda.synchronize()
+    assert got.data_ptr() == out.data_ptr()
+    return got
+
+
+def cu_count():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+# ---- conv3x3_c32 against float64 ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(R.C32_VARIANTS))
+@pytest.mark.parametrize("H,W", R.C32_SHAPES)
+@pytest.mark.parametrize("cin", [32, 64])
+def test_conv3x3_c32_is_within_the_float32_bound_of_float64(ctx, cin, H, W, variant):
+    if (H, W) == R.C32_BIG:
+        # a condition, not an assumption: some workgroup runs at least three tiles and the shares are uneven
+        tx, ty = R.c32_tiles(H, W)
+        grid = R.c32_grid(tx * ty, cu_count())
+        assert tx * ty >= 2 * grid + 1, f"{tx * ty} tiles on {grid} workgroups ({cu_count()} compute units): no third tile"
+    inp, ref, bound = R.c32_case(cin, H, W, variant)
+    got = run_c32(ctx, inp[0], R.pack_c32(inp[1]).cuda(), R.c32_kwargs(inp, variant)).cpu()
+    assert got.shape == ref.shape
+    r = R.worst_ratio(got, ref, bound)
+    print(f"conv3x3_c32 C_in={cin} {H}x{W} {variant}: max err / bound = {r:.4f}")
+    over = int(((got.double() - ref).abs() <= bound).logical_not().sum())
+    assert over == 0, f"{over} of {ref.numel()} outputs over the bound (or never stored), worst err / bound {r:.3g}"
+
+
+@pytest.mark.parametrize("H,W", [(1, 5), (5, 1), (1, 1)])
+def test_conv_launchers_refuse_an_image_too_small_to_reflect(ctx, H, W):
+    g = torch.Generator().manual_seed(0)
+    wp = R.pack_c32(torch.randn((32, 32, 3, 3), generator=g)).cuda()
+    with pytest.raises(hip_api.MppError):
+        ctx.conv3x3_c32(nhwc(torch.randn((1, 32, H, W), generator=g)), wp, out=nan_map(H, W))
+    ws = R.pack_stem(torch.randn((32, 3, 3, 3), generator=g)).cuda()
+    with pytest.raises(hip_api.MppError):
+        ctx.conv3x3_stem(nhwc(torch.rand((1, 3, H, W), generator=g)), ws, torch.ones(32, device="cuda"), torch.zeros(32, device="cuda"))
+    torch.cuda.synchronize()
+
+
+# ---- conv3x3_c32: what must be exact ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", params=[32, 64])
+def big(request, ctx):
+    """the persistent shape with the in-load affine and the epilogue: inputs, packed weights, arguments, the kernel's output"""
+    cin = request.param
+    inp = R.c32_inputs(cin, *R.C32_BIG)
+    kw = R.c32_kwargs(inp, "affine+epilogue")
+    wp = R.pack_c32(inp[1]).cuda()
+    return cin, inp, wp, kw, run_c32(ctx, inp[0], wp, kw)
+
+
+def test_conv3x3_c32_repeats_bit_for_bit(ctx, big):
+    cin, inp, wp, kw, first = big
+    for _ in range(2):
+        again = run_c32(ctx, inp[0], wp, kw)
+        assert torch.equal(bits(again), bits(first))
+
+
+def test_a_source_with_zero_weights_leaves_the_chain_of_the_other_unchanged(ctx):
+    """acc + x * 0 = acc exactly: the 64-channel call with one source's weights zeroed is the 32-channel call on the other,
+    whichever stage of a tile the live source is (the in-load affine belongs to the first source only)."""
+    x, w, isc, ish, osc, osh = R.c32_inputs(64, *R.C32_BIG)
+    epi = dict(out_scale=osc, out_shift=osh, relu=True)
+    aff = dict(in_scale=isc, in_shift=ish, **epi)
+    none = dict(in_scale=None, in_shift=None, **epi)
+    w0, w1 = w.clone(), w.clone()
+    w0[:, :32], w1[:, 32:] = 0.0, 0.0
+    for kw in (aff, none):                                                # second source dead
+        got = run_c32(ctx, x, R.pack_c32(w1).cuda(), kw)
+        want = run_c32(ctx, x[:, :32], R.pack_c32(w[:, :32]).cuda(), kw)
+        assert not bool(torch.isnan(want).any()) and torch.equal(bits(got), bits(want))
+    got = run_c32(ctx, x, R.pack_c32(w0).cuda(), none)                    # first source dead
+    want = run_c32(ctx, x[:, 32:], R.pack_c32(w[:, 32:]).cuda(), none)
+    assert not bool(torch.isnan(want).any()) and torch.equal(bits(got), bits(want))
+
+
+def interior_windows(H, W, cus):
+    """Windows (r0, r1, c0, c1) of the persistent shape chosen from the launcher's split on this device: one that starts
+    inside the third tile of a workgroup that has three, and one full-width band over a tile-row wrap that falls inside a
+    workgroup's range (its later tile starts the new row)."""
+    tx, ty = R.c32_tiles(H, W)
+    ranges = R.c32_ranges(tx * ty, R.c32_grid(tx * ty, cus))
+    wins = {}
+    for a, b in ranges:
+        if b - a >= 3 and "third tile" not in wins and 0 < (a + 2) // tx < ty - 2 and 0 < (a + 2) % tx < tx - 2:
+            r, c = (a + 2) // tx * R.CV_ROWS + 3, (a + 2) % tx * R.CV_COLS + 5
+            wins["third tile"] = (r, r + 14, c, c + 100)                   # into the next tile row and the next two tiles
+        wrap = [t for t in range(a + 1, b) if t % tx == 0]
+        if wrap and "row wrap" not in wins and 0 < wrap[0] // tx < ty - 1:
+            r = wrap[0] // tx * R.CV_ROWS
+            wins["row wrap"] = (r - 5, r + 6, 0, W)
+    return wins
+
+
+def check_crop_property(run, x, full, wins):
+    """``run(x)`` on the window cropped out with a one-pixel margin equals ``full`` on the window, bit for bit (a side of
+    the window that is a side of the image needs no margin: the reflection is the image's own there)"""
+    H, W = x.shape[2:]
+    for name, (r0, r1, c0, c1) in wins.items():
+        a0, a1, b0, b1 = max(r0 - 1, 0), min(r1 + 1, H), max(c0 - 1, 0), min(c1 + 1, W)
+        got = run(x[:, :, a0:a1, b0:b1])[:, :, r0 - a0:r1 - a0, c0 - b0:c1 - b0]
+        want = full[:, :, r0:r1, c0:c1]
+        assert got.shape == want.shape and not bool(torch.isnan(want).any())
+        assert torch.equal(bits(got), bits(want)), name
+
+
+def test_a_pixel_does_not_depend_on_the_tile_stage_or_workgroup_that_computed_it(ctx, big):
+    cin, inp, wp, kw, full = big
+    H, W = R.C32_BIG
+    wins = interior_windows(H, W, cu_count())
+    assert set(wins) == {"third tile", "row wrap"}, f"no such workgroup on {cu_count()} compute units: {sorted(wins)}"
+    check_crop_property(lambda x: run_c32(ctx, x, wp, kw), inp[0], full, wins)
+
+
+# ---- the stem -----------------------------------------------------------------------------------------------------------------------
+def run_stem(ctx, x, wp, sc, sh):
+    H, W = x.shape[2:]
+    xd = nhwc(x)
+    # (the binding allocates the output itself; a NaN block of its size released just before makes it likely, not certain,
+    # that the output starts as NaN)
+    junk = nan_map(H, W)
+    del junk
+    got = ctx.conv3x3_stem(xd, wp, sc, sh)
+    torch.cuda.synchronize()
+    return got
+
+
+@pytest.mark.parametrize("H,W", R.STEM_SHAPES)
+def test_stem_is_within_the_float32_bound_of_float64_repeats_and_crops(ctx, H, W):
+    (x, w, sc, sh), ref, bound = R.stem_case(H, W)
+    wp, scd, shd = R.pack_stem(w).cuda(), sc.cuda(), sh.cuda()
+    got = run_stem(ctx, x, wp, scd, shd)
+    assert got.shape == ref.shape and got.is_contiguous(memory_format=torch.channels_last)
+    r = R.worst_ratio(got.cpu(), ref, bound)
+    print(f"stem {H}x{W}: max err / bound = {r:.4f}")
+    over = int(((got.cpu().double() - ref).abs() <= bound).logical_not().sum())
+    assert over == 0, f"{over} of {ref.numel()} outputs over the bound, worst err / bound {r:.3g}"
+    assert torch.equal(bits(run_stem(ctx, x, wp, scd, shd)), bits(got))
+    # windows that straddle the 16 x 16 tiles, where the image has room for them
+    wins = {}
+    if H >= 17 and W >= 33:
+        wins["corner of four tiles"] = (13, min(19, H), 14, min(37, W))
+    if H >= 300:
+        wins["interior"] = (150, 185, 395, 460)
+        wins["last rows"] = (H - 20, H, 0, W)
+    check_crop_property(lambda t: run_stem(ctx, t, wp, scd, shd), x, got, wins)
+
+
+# ---- the heads ---------------------------------------------------------------------------------------------------------------------
+def run_heads(ctx, h, w, b, H, W):
+    marks = [torch.full((H, W, 32), float("nan"), device="cuda") for _ in range(3)]
+    ctx.shapenet_heads(h, w, b, H, W, marks)
+    torch.cuda.synchronize()
+    return torch.stack(marks)
+
+
+@pytest.mark.parametrize("H,W,ldh,ldw", R.HEADS_SHAPES)
+def test_heads_are_within_the_float32_bound_of_float64_and_repeat(ctx, H, W, ldh, ldw):
+    if (H, W, ldh, ldw) == R.HEADS_SHAPES[-1]:
+        # more groups than the capped grid has waves: some waves run the loop body twice on their LDS tile
+        assert R.heads_groups(H, W) > 4 * R.HEADS_MAX_GRID
+    (h, w, b), _, p, bound = R.heads_case(H, W, ldh, ldw)
+    hd, wd, bd = nhwc(h), w.cuda(), b.cuda()
+    got = run_heads(ctx, hd, wd, bd, H, W)
+    r = R.worst_ratio(got.cpu(), p, bound)
+    print(f"heads {H}x{W} of {ldh}x{ldw}: max err / bound = {r:.4f}")
+    over = int(((got.cpu().double() - p).abs() <= bound).logical_not().sum())
+    assert over == 0, f"{over} of {p.numel()} probabilities over the bound (or never stored), worst err / bound {r:.3g}"
+    assert float((got.sum(-1) - 1.0).abs().max()) <= 1e-5
+    assert torch.equal(bits(run_heads(ctx, hd, wd, bd, H, W)), bits(got))
+
+
+@pytest.mark.parametrize("wx0,wy0,wh,ww", [(7, 0, 320, 801), (5, 9, 300, 700), (330, 800, 1, 1)])
+def test_heads_window_form_equals_the_full_form_and_stays_inside_its_window(ctx, wx0, wy0, wh, ww):
+    H, W, ldh, ldw = R.HEADS_SHAPES[-1]
+    if ww == W:
+        assert R.heads_groups(wh, ww) > 4 * R.HEADS_MAX_GRID              # the window's own loop runs twice as well
+    (h, w, b), _, _, _ = R.heads_case(H, W, ldh, ldw)
+    hd, wd, bd = nhwc(h), w.cuda(), b.cuda()
+    full = run_heads(ctx, hd, wd, bd, H, W)
+    ox, oy = 3, 5
+    dests = [torch.full((wh + 7, ww + 11, 32), SENTINEL, device="cuda") for _ in range(3)]
+    ctx.shapenet_heads_win(hd, wd, bd, H, W, wx0, wy0, [t[ox:ox + wh, oy:oy + ww] for t in dests])
+    torch.cuda.synchronize()
+    for k, t in enumerate(dests):
+        assert torch.equal(bits(t[ox:ox + wh, oy:oy + ww]), bits(full[k, wx0:wx0 + wh, wy0:wy0 + ww])), k
+        t = t.clone()
+        t[ox:ox + wh, oy:oy + ww] = SENTINEL
+        assert bool((t == SENTINEL).all()), (k, "written outside the window")
