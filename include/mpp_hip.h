@@ -245,9 +245,9 @@ int mpp_last_kernel_ms(mpp_ctx *ctx, double *ms);
 
 /* score-map epilogue of the two U-Nets (position_net/pos_net_model.py:186-200,338-346,
  * torch_div.py:8-43; shape_net/shape_net_model.py:139-141): all device pointers.
- * pos_out: [3][ldh][ldw] (vec0, vec1, mask logit; the network's padded output, of which the top-left
- * H x W region is used) -> det [H][W];
- * logits: [32][ldh][ldw] of one mark head -> marks [H][W][32], softmax over the 32 classes. */
+ * pos_out: [3][ldh][ldw] (vec0, vec1, mask logit; the padded output, whose top-left H x W region is used) -> det [H][W];
+ * logits: [32][ldh][ldw] of one mark head -> marks [H][W][32] (16-byte aligned), softmax over the 32 classes.
+ * Each is its window form (mpp_*_win below) with the window equal to the crop and a dense destination. */
 int mpp_posnet_epilogue(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *pos_out, double div_w,
                         double div_b, float *det);
 int mpp_shapenet_epilogue(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *logits, float *marks);
@@ -260,7 +260,8 @@ int mpp_affine_relu(mpp_ctx *ctx, void *x, int planes, int C, int64_t hw, int el
 
 /* The two epilogues above on channels-last network outputs: pos_out [ldh][ldw][3], logits [ldh][ldw][32], elements
  * float32 (elem_bytes 4) or bfloat16 (2), device pointers; same arithmetic and outputs (det [H][W], marks [H][W][32]
- * float32).  A pixel's 32 logits are contiguous here, so the softmax is one coalesced pass with no transpose. */
+ * float32).  A pixel's 32 logits are contiguous here, so the softmax is one coalesced pass with no transpose.
+ * Each is its window form (mpp_*_nhwc_win below) with the window equal to the crop and a dense destination. */
 int mpp_posnet_epilogue_nhwc(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
                              double div_b, float *det);
 int mpp_shapenet_epilogue_nhwc(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, float *marks);
@@ -296,16 +297,15 @@ int mpp_conv3x3_stem(mpp_ctx *ctx, const float *x, int H, int W, const float *wp
  * shape_net_model.py's inference softmax): h [ldh][ldw][32] float32 channels-last (the backbone's output) ->
  * marks_* [H][W][32] = softmax_c(sum_i w[k][c][i] * h[i] + b[k][c]), k = size, ratio, angle; w [3][32 classes][32 in],
  * b [3][32].  Replaces three library convolutions + bias adds + mpp_shapenet_epilogue_nhwc (same values up to float32
- * summation order).  All device pointers, 16-byte aligned; the ctx's stream. */
+ * summation order).  All device pointers, 16-byte aligned; the ctx's stream.
+ * It is mpp_shapenet_heads_win below with the window equal to the crop and a dense destination. */
 int mpp_shapenet_heads(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b,
                        float *marks_size, float *marks_ratio, float *marks_angle);
 
-/* Window forms of the five epilogues above, for a forward that walks a large image in crops: the crop's network output
- * as above, its extent H x W (which decides where the divergence is one-sided, exactly as in the full-crop call), and a
- * window of wh x ww pixels at (wx0, wy0) in crop coordinates.  Only the window's pixels are computed; det / marks point to
- * the window's first pixel in a larger map whose rows are ld_det / ld_marks pixels apart (marks: 32 floats per pixel).
- * Per pixel the result is bit for bit the full-crop call's; nothing outside the window is written.  A window outside the
- * crop or a pitch smaller than ww: -1 and a message. */
+/* The general (window) forms of the five epilogues above, one kernel each, for a forward that walks a large image in crops:
+ * H x W is the crop's extent (it decides where the divergence is one-sided), (wx0, wy0, wh x ww) the window in crop coordinates;
+ * det / marks point to the window's first pixel in a map whose rows are ld_det / ld_marks pixels apart.  A pixel's result does not
+ * depend on the window, bit for bit; nothing outside it is written.  A window outside the crop or ld < ww: -1 and a message. */
 int mpp_posnet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
                             int wx0, int wy0, int wh, int ww, float *det, int ld_det);
 int mpp_shapenet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0, int wh, int ww,

@@ -207,101 +207,21 @@ extern "C" int mpp_launch_conv3x3_c32(hipStream_t st, const float *x0, const flo
 
 // ---- ShapeNet's three 1x1 heads + bias + softmax in one pass (model_parts/shape_net.py:12-46: three Conv2d(32, 32, 1x1);
 // the softmax of shape_net_model.py's inference) ----------------------------------------------------------------------
-// h [ldh][ldw][32] float32 (the backbone's last activation, channels-last) -> marks[k] [H][W][32] for k = size, ratio, angle.
+// h [ldh][ldw][32] float32 (the backbone's last activation, channels-last) -> for k = size, ratio, angle the window
+// (wx0, wy0, wh x ww) of the crop's mark map (the tiled forward: unet.py, chunk_plan; the whole crop is the window (0, 0, H x W)),
+// stored at m0 / m1 / m2 (the window's first pixel of each full-image map) with a row pitch of ld_dst pixels.
 // Separately (library 1x1 convolution, its bias add, the softmax epilogue) the three heads move 38 GB on a 4096 x 4096
 // image; fused they read h once and write the three mark maps: 8.6 GB.
-// A wave takes 32 consecutive pixels of an image row: their 32 x 32 activations go through LDS (pixel stride 33, as above)
+// A wave takes 32 consecutive pixels of a window row: their 32 x 32 activations go through LDS (pixel stride 33, as above)
 // into B fragments; A fragments are the head's weights (kept in registers); D[class][pixel] puts 16 classes of one pixel
 // in a lane and the other 16 in lane ^ 32, so the softmax is 16 in-lane steps and one exchange.
+// An MFMA output column depends on its own pixel only, so a pixel's marks are the same bit for bit whichever window and
+// group it falls in.
 #define HD_PIX 33
-__global__ __launch_bounds__(256) void k_shapenet_heads(const float *__restrict__ h, int H, int W, int ldw, const float *__restrict__ wh,
+__global__ __launch_bounds__(256) void k_shapenet_heads(const float *__restrict__ h, int ldw, const float *__restrict__ wh,
                                                         const float *__restrict__ bh, float *__restrict__ m0, float *__restrict__ m1,
-                                                        float *__restrict__ m2, int groups_per_row, int n_groups) {
-  __shared__ float tiles[4][32 * HD_PIX];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = lane & 31, kh = lane >> 5;
-  float *tile = tiles[wave];
-  // weights of the three heads as A fragments: step s covers channels 2s, 2s + 1; this lane: class n, channel 2s + kh
-  float wa[3][16], bias[3][16];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int s = 0; s < 16; ++s) wa[k][s] = wh[(k * 32 + n) * 32 + 2 * s + kh];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) bias[k][r] = bh[k * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh];
-  }
-  const int n_waves = (int)gridDim.x * 4;
-  for (int g = (int)blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
-    const int gx = g / groups_per_row, gy0 = (g - gx * groups_per_row) * 32;
-    const int nv = min(32, W - gy0);
-    const float *src = h + ((size_t)gx * ldw + gy0) * 32;
-    float4 v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = lane + 64 * i, p = idx >> 3;
-      v[i] = p < nv ? *(const float4 *)(src + (size_t)idx * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = lane + 64 * i;
-      float *d = tile + (idx >> 3) * HD_PIX + 4 * (idx & 7);
-      d[0] = v[i].x; d[1] = v[i].y; d[2] = v[i].z; d[3] = v[i].w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float bf[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) bf[s] = tile[n * HD_PIX + 2 * s + kh];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();                 // (the next group's stores to the tile come after these reads)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = bias[k][r];
-#pragma unroll
-      for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[k][s], bf[s], acc, 0, 0, 0);
-      float mx = acc[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, acc[r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      float e[16], sum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { e[r] = expf(acc[r] - mx); sum += e[r]; }
-      sum += __shfl_xor(sum, 32, 64);
-      if (n < nv) {
-        float *dst = (k == 0 ? m0 : (k == 1 ? m1 : m2)) + ((size_t)gx * W + gy0 + n) * 32 + 4 * kh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *(float4 *)(dst + 8 * q) = make_float4(e[4 * q] / sum, e[4 * q + 1] / sum, e[4 * q + 2] / sum, e[4 * q + 3] / sum);
-      }
-    }
-  }
-}
-
-extern "C" int mpp_launch_shapenet_heads(hipStream_t st, const float *h, int H, int W, int ldw, const float *wh, const float *bh,
-                                         float *m0, float *m1, float *m2) {
-  if (H < 1 || W < 1 || ldw < W) return -1;
-  if (((uintptr_t)h & 15) || ((uintptr_t)m0 & 15) || ((uintptr_t)m1 & 15) || ((uintptr_t)m2 & 15)) return -2;
-  const int gpr = (W + 31) / 32;
-  const long long n_groups = (long long)gpr * H;
-  if (n_groups > 0x7fffffffLL) return -1;
-  int grid = (int)((n_groups + 3) / 4);
-  if (grid > 2048) grid = 2048;                       // eight workgroups per CU, each wave strides over the groups
-  hipLaunchKernelGGL(k_shapenet_heads, dim3(grid), dim3(256), 0, st, h, H, W, ldw, wh, bh, m0, m1, m2, gpr, (int)n_groups);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// The window form (the tiled forward: unet.py, chunk_plan): the window (wx0, wy0, wh x ww) of the crop, groups of 32 pixels of a
-// window row, stored at m0 / m1 / m2 (the window's first pixel of each full-image map) with a row pitch of ld_dst pixels.  An
-// MFMA output column depends on its own pixel only and the arithmetic is the kernel's above, so a pixel's marks are bit for
-// bit those of the full-crop kernel whichever group it falls in.  (A copy rather than a shared body: the kernel above keeps
-// its code.)
-__global__ __launch_bounds__(256) void k_shapenet_heads_win(const float *__restrict__ h, int ldw, const float *__restrict__ wh,
-                                                            const float *__restrict__ bh, float *__restrict__ m0, float *__restrict__ m1,
-                                                            float *__restrict__ m2, int groups_per_row, int n_groups, int wx0, int wy0,
-                                                            int ww, int ld_dst) {
+                                                        float *__restrict__ m2, int groups_per_row, int n_groups, int wx0, int wy0,
+                                                        int ww, int ld_dst) {
   __shared__ float tiles[4][32 * HD_PIX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 31, kh = lane >> 5;
@@ -365,15 +285,15 @@ __global__ __launch_bounds__(256) void k_shapenet_heads_win(const float *__restr
   }
 }
 
-extern "C" int mpp_launch_shapenet_heads_win(hipStream_t st, const float *h, int ldw, const float *wh, const float *bh, int wx0, int wy0,
-                                             int wh_, int ww, float *m0, float *m1, float *m2, int ld_dst) {
+extern "C" int mpp_launch_shapenet_heads(hipStream_t st, const float *h, int ldw, const float *wh, const float *bh, int wx0, int wy0,
+                                         int wh_, int ww, float *m0, float *m1, float *m2, int ld_dst) {
   if (((uintptr_t)h & 15) || ((uintptr_t)m0 & 15) || ((uintptr_t)m1 & 15) || ((uintptr_t)m2 & 15)) return -2;
   const int gpr = (ww + 31) / 32;
   const long long n_groups = (long long)gpr * wh_;
   if (n_groups > 0x7fffffffLL) return -1;
   int grid = (int)((n_groups + 3) / 4);
-  if (grid > 2048) grid = 2048;
-  hipLaunchKernelGGL(k_shapenet_heads_win, dim3(grid), dim3(256), 0, st, h, ldw, wh, bh, m0, m1, m2, gpr, (int)n_groups, wx0, wy0, ww,
+  if (grid > 2048) grid = 2048;                       // eight workgroups per CU, each wave strides over the groups
+  hipLaunchKernelGGL(k_shapenet_heads, dim3(grid), dim3(256), 0, st, h, ldw, wh, bh, m0, m1, m2, gpr, (int)n_groups, wx0, wy0, ww,
                      ld_dst);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }

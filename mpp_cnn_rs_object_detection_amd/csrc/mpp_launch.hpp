@@ -52,17 +52,12 @@ void mpp_launch_grid_build(hipStream_t st, const DevParams *P, const TileRef *ti
                            int32_t *cursor, int32_t *items);
 int mpp_launch_affine_relu(hipStream_t st, void *x, int planes, int C, size_t hw, int elem_bytes, const float *scale,
                            const float *shift);
-int mpp_launch_posnet_epilogue_nhwc(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w, float b,
-                                    float *det);
-int mpp_launch_shapenet_epilogue_nhwc(hipStream_t st, const void *logits, int elem_bytes, int H, int W, int ldw, float *marks);
 int mpp_launch_nhwc_glue(hipStream_t st, const void *x0, const void *x1, void *y, int H, int W, int C0, int C1, int pad, int pool,
                          int in_bytes, int out_bytes, const float *scale, const float *shift);
 int mpp_launch_conv3x3_c32(hipStream_t st, const float *x0, const float *x1, int H, int W, const float *wp, const float *in_scale,
                            const float *in_shift, const float *out_scale, const float *out_shift, int relu, float *y);
 int mpp_launch_conv3x3_stem(hipStream_t st, const float *x, int H, int W, const float *wp, const float *scale, const float *shift,
                             float *y);
-int mpp_launch_shapenet_heads(hipStream_t st, const float *h, int H, int W, int ldw, const float *wh, const float *bh, float *m0,
-                              float *m1, float *m2);
 void mpp_launch_quad_iou(hipStream_t st, int n, const double *a, int m, const double *b, double *out);
 void mpp_launch_pack_detections(hipStream_t st, const TileRef *tiles, int n_tiles, const int32_t *tile_ids,
                                 const int32_t *anchors, int capacity, double *out);
@@ -76,16 +71,15 @@ void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W,
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);
 void mpp_launch_naive_init(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, double threshold,
                            double nms_dist, unsigned long long *cand, int cand_cap);
-void mpp_launch_posnet_epilogue(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b, float *det);
-void mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits, int H, int W, int ldh, int ldw, float *marks);
-void mpp_launch_posnet_epilogue_win(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b, int wx0,
-                                    int wy0, int wh, int ww, float *dst, int ld_dst);
-int mpp_launch_shapenet_epilogue_win(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
-                                     float *dst, int ld_dst);
-int mpp_launch_posnet_epilogue_nhwc_win(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w, float b,
-                                        int wx0, int wy0, int wh, int ww, float *dst, int ld_dst);
-int mpp_launch_shapenet_epilogue_nhwc_win(hipStream_t st, const void *logits, int elem_bytes, int ldw, int wx0, int wy0, int wh,
-                                          int ww, float *dst, int ld_dst);
-int mpp_launch_shapenet_heads_win(hipStream_t st, const float *h, int ldw, const float *wh, const float *bh, int wx0, int wy0,
-                                  int wh_, int ww, float *m0, float *m1, float *m2, int ld_dst);
+// the U-Net epilogues: the window (wx0, wy0, wh x ww) of an H x W crop into dst, row pitch ld_dst pixels (mpp_maps.hip, mpp_conv.hip)
+void mpp_launch_posnet_epilogue(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b, int wx0,
+                                int wy0, int wh, int ww, float *dst, int ld_dst);
+int mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
+                                 float *dst, int ld_dst);
+int mpp_launch_posnet_epilogue_nhwc(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w, float b,
+                                    int wx0, int wy0, int wh, int ww, float *dst, int ld_dst);
+int mpp_launch_shapenet_epilogue_nhwc(hipStream_t st, const void *logits, int elem_bytes, int ldw, int wx0, int wy0, int wh,
+                                      int ww, float *dst, int ld_dst);
+int mpp_launch_shapenet_heads(hipStream_t st, const float *h, int ldw, const float *wh, const float *bh, int wx0, int wy0,
+                              int wh_, int ww, float *m0, float *m1, float *m2, int ld_dst);
 }

@@ -134,6 +134,11 @@ extern "C" void mpp_launch_naive_init(hipStream_t st, const DevParams *P, const 
 // out: [3][ldh][ldw] float32 (vec0 = d/d row component, vec1 = d/d col component, mask logit);
 // det[x][y] = sigmoid(w * (d vec0/dx + d vec1/dy) * sigmoid(mask) + b), central differences inside,
 // one-sided at the borders of the H x W region (torch.gradient semantics).
+// Both epilogues take a window (wx0, wy0, wh x ww) of the crop's H x W extent (the tiled forward: unet.py, chunk_plan; the
+// whole crop is the window (0, 0, H x W)): H x W still decides where the differences are one-sided; the window's pixels go to
+// dst (the window's first pixel in a full-image map) with a row pitch of ld_dst pixels.  Per pixel the arithmetic and its order
+// do not depend on the window (the build forms no FMA: -ffp-contract=off), so a window is the whole-crop map restricted to it
+// bit for bit; nothing outside it is written.
 __device__ __forceinline__ float posnet_pixel(const float *v0, const float *v1, const float *mk, int x, int y, int H,
                                               int W, int ldw, float w, float b) {
   float g0, g1;
@@ -151,94 +156,8 @@ __device__ __forceinline__ float posnet_pixel(const float *v0, const float *v1, 
 }
 // each thread produces 4 consecutive pixels of a row: 16-byte loads of the rows above/below, of the row
 // itself (plus its two neighbours) and of the mask, one 16-byte store
-__global__ __launch_bounds__(256) void k_posnet_epilogue(const float *out, int H, int W, int ldh, int ldw, float w,
-                                                         float b, float *det, int vec_ok) {
-  const int y4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, x = blockIdx.y;
-  if (y4 >= W || x >= H) return;
-  const size_t plane = (size_t)ldh * ldw;
-  const float *v0 = out, *v1 = out + plane, *mk = out + 2 * plane;
-  if (vec_ok && x > 0 && x < H - 1 && y4 > 0 && y4 + 4 < W) {
-    const float4 up = *(const float4 *)(v0 + (size_t)(x - 1) * ldw + y4), dn = *(const float4 *)(v0 + (size_t)(x + 1) * ldw + y4);
-    const float4 c = *(const float4 *)(v1 + (size_t)x * ldw + y4), m4 = *(const float4 *)(mk + (size_t)x * ldw + y4);
-    const float left = v1[(size_t)x * ldw + y4 - 1], right = v1[(size_t)x * ldw + y4 + 4];
-    const float g0[4] = {(dn.x - up.x) / 2.0f, (dn.y - up.y) / 2.0f, (dn.z - up.z) / 2.0f, (dn.w - up.w) / 2.0f};
-    const float g1[4] = {(c.y - left) / 2.0f, (c.z - c.x) / 2.0f, (c.w - c.y) / 2.0f, (right - c.z) / 2.0f};
-    const float mm[4] = {m4.x, m4.y, m4.z, m4.w};
-    float r[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float mask = 1.0f / (1.0f + expf(-mm[i]));
-      float score = w * ((g0[i] + g1[i]) * mask) + b;
-      r[i] = 1.0f / (1.0f + expf(-score));
-    }
-    *(float4 *)(det + (size_t)x * W + y4) = make_float4(r[0], r[1], r[2], r[3]);
-  } else {
-    for (int y = y4; y < min(y4 + 4, W); ++y) det[(size_t)x * W + y] = posnet_pixel(v0, v1, mk, x, y, H, W, ldw, w, b);
-  }
-}
-extern "C" void mpp_launch_posnet_epilogue(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w,
-                                           float b, float *det) {
-  int vec_ok = (ldw % 4 == 0) && (W % 4 == 0) && (((uintptr_t)out & 15) == 0) && (((uintptr_t)det & 15) == 0) &&
-               (((size_t)ldh * ldw) % 4 == 0);
-  hipLaunchKernelGGL(k_posnet_epilogue, dim3((W + 1023) / 1024, H), dim3(256), 0, st, out, H, W, ldh, ldw, w, b, det,
-                     vec_ok);
-}
-
-// ---- ShapeNet epilogue --------------------------------------------------------------------------------
-// logits: [32][ldh][ldw] -> marks [H][W][32] = softmax over classes.  One block = 64 pixels of a row:
-// 16-byte loads (4 pixels of one channel per lane), transpose through LDS, 2 x 16-byte stores per lane
-// (one pixel's 32 classes = 128 contiguous bytes from 4 lanes).
-__global__ __launch_bounds__(256) void k_shapenet_epilogue(const float *logits, int H, int W, int ldh, int ldw,
-                                                           float *marks, int vec_ok) {
-  __shared__ float tile[MPP_NCLASS][WAVE + 1];
-  const int x = blockIdx.y, y0 = blockIdx.x * WAVE;
-  const size_t plane = (size_t)ldh * ldw;
-  if (vec_ok && y0 + WAVE <= W) {
-    const int px4 = (threadIdx.x & 15) * 4, ch0 = threadIdx.x >> 4;      // 16 lanes cover the 64 pixels of a channel
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int ch = ch0 + 16 * h;
-      const float4 v = *(const float4 *)(logits + ch * plane + (size_t)x * ldw + y0 + px4);
-      tile[ch][px4] = v.x; tile[ch][px4 + 1] = v.y; tile[ch][px4 + 2] = v.z; tile[ch][px4 + 3] = v.w;
-    }
-  } else {
-    const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    for (int ch = grp; ch < MPP_NCLASS; ch += 4) {
-      int y = y0 + lane;
-      tile[ch][lane] = y < W ? logits[ch * plane + (size_t)x * ldw + y] : 0.f;
-    }
-  }
-  __syncthreads();
-  // pixel p = threadIdx.x / 4 handles 8 classes: threads of one pixel sit in one wave -> shuffles
-  const int p = threadIdx.x >> 2, q = threadIdx.x & 3;
-  float v[8], m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = tile[q * 8 + i][p]; m = fmaxf(m, v[i]); }
-  m = fmaxf(m, __shfl_xor(m, 1, WAVE)); m = fmaxf(m, __shfl_xor(m, 2, WAVE));
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = expf(v[i] - m); s += v[i]; }
-  s += __shfl_xor(s, 1, WAVE); s += __shfl_xor(s, 2, WAVE);
-  if (y0 + p < W) {
-    float4 *dst = (float4 *)(marks + ((size_t)x * W + y0 + p) * MPP_NCLASS + q * 8);
-    dst[0] = make_float4(v[0] / s, v[1] / s, v[2] / s, v[3] / s);
-    dst[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
-  }
-}
-extern "C" void mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits, int H, int W, int ldh, int ldw,
-                                             float *marks) {
-  int vec_ok = (ldw % 4 == 0) && (((uintptr_t)logits & 15) == 0) && (((size_t)ldh * ldw) % 4 == 0);
-  hipLaunchKernelGGL(k_shapenet_epilogue, dim3((W + WAVE - 1) / WAVE, H), dim3(256), 0, st, logits, H, W, ldh, ldw,
-                     marks, vec_ok);
-}
-
-// ---- window forms of the two epilogues (the tiled forward: unet.py, chunk_plan) ----------------------------------------
-// A crop's epilogue restricted to the window (wx0, wy0, wh x ww) of its H x W extent: H x W still decides where the
-// differences are one-sided; the window's pixels go to dst (the window's first pixel in a full-image map) with a row pitch
-// of ld_dst pixels.  Per pixel the arithmetic, in its order, of the full-crop kernel above (the build forms no FMA:
-// -ffp-contract=off), so a window is the full-crop map restricted to it bit for bit; nothing outside it is written.
-__global__ __launch_bounds__(256) void k_posnet_epilogue_win(const float *out, int H, int W, int ldh, int ldw, float w, float b,
-                                                             int wx0, int wy0, int wh, int ww, float *dst, int ld_dst, int vec_ok) {
+__global__ __launch_bounds__(256) void k_posnet_epilogue(const float *out, int H, int W, int ldh, int ldw, float w, float b,
+                                                         int wx0, int wy0, int wh, int ww, float *dst, int ld_dst, int vec_ok) {
   const int j4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, r = blockIdx.y;
   if (j4 >= ww || r >= wh) return;
   const int x = wx0 + r, y4 = wy0 + j4;
@@ -264,16 +183,21 @@ __global__ __launch_bounds__(256) void k_posnet_epilogue_win(const float *out, i
     for (int j = j4; j < min(j4 + 4, ww); ++j) drow[j] = posnet_pixel(v0, v1, mk, x, wy0 + j, H, W, ldw, w, b);
   }
 }
-extern "C" void mpp_launch_posnet_epilogue_win(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b,
-                                               int wx0, int wy0, int wh, int ww, float *dst, int ld_dst) {
+extern "C" void mpp_launch_posnet_epilogue(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b,
+                                           int wx0, int wy0, int wh, int ww, float *dst, int ld_dst) {
   // (a det window can start at any pixel: float4 stores only where the destination rows are 16-byte aligned)
   int vec_ok = (ldw % 4 == 0) && (wy0 % 4 == 0) && (ld_dst % 4 == 0) && (((uintptr_t)out & 15) == 0) &&
                (((uintptr_t)dst & 15) == 0) && (((size_t)ldh * ldw) % 4 == 0);
-  hipLaunchKernelGGL(k_posnet_epilogue_win, dim3((ww + 1023) / 1024, wh), dim3(256), 0, st, out, H, W, ldh, ldw, w, b, wx0, wy0,
+  hipLaunchKernelGGL(k_posnet_epilogue, dim3((ww + 1023) / 1024, wh), dim3(256), 0, st, out, H, W, ldh, ldw, w, b, wx0, wy0,
                      wh, ww, dst, ld_dst, vec_ok);
 }
-__global__ __launch_bounds__(256) void k_shapenet_epilogue_win(const float *logits, int ldh, int ldw, int wx0, int wy0, int ww,
-                                                               float *dst, int ld_dst, int vec_ok) {
+
+// ---- ShapeNet epilogue --------------------------------------------------------------------------------
+// logits: [32][ldh][ldw] -> the window's marks [wh][ww][32] = softmax over classes.  One block = 64 pixels of a window row:
+// 16-byte loads (4 pixels of one channel per lane), transpose through LDS, 2 x 16-byte stores per lane
+// (one pixel's 32 classes = 128 contiguous bytes from 4 lanes).
+__global__ __launch_bounds__(256) void k_shapenet_epilogue(const float *logits, int ldh, int ldw, int wx0, int wy0, int ww,
+                                                           float *dst, int ld_dst, int vec_ok) {
   __shared__ float tile[MPP_NCLASS][WAVE + 1];
   const int r = blockIdx.y, j0 = blockIdx.x * WAVE, x = wx0 + r, y0 = wy0 + j0;
   const size_t plane = (size_t)ldh * ldw;
@@ -305,11 +229,11 @@ __global__ __launch_bounds__(256) void k_shapenet_epilogue_win(const float *logi
     d[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
   }
 }
-extern "C" int mpp_launch_shapenet_epilogue_win(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
-                                                float *dst, int ld_dst) {
+extern "C" int mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
+                                            float *dst, int ld_dst) {
   if ((uintptr_t)dst & 15) return -2;                  // (a pixel's 32 classes are 128 bytes: every window row is aligned)
   int vec_ok = (ldw % 4 == 0) && (wy0 % 4 == 0) && (((uintptr_t)logits & 15) == 0) && (((size_t)ldh * ldw) % 4 == 0);
-  hipLaunchKernelGGL(k_shapenet_epilogue_win, dim3((ww + WAVE - 1) / WAVE, wh), dim3(256), 0, st, logits, ldh, ldw, wx0, wy0, ww,
+  hipLaunchKernelGGL(k_shapenet_epilogue, dim3((ww + WAVE - 1) / WAVE, wh), dim3(256), 0, st, logits, ldh, ldw, wx0, wy0, ww,
                      dst, ld_dst, vec_ok);
   return 0;
 }
@@ -504,81 +428,13 @@ extern "C" int mpp_launch_nhwc_glue(hipStream_t st, const void *x0, const void *
 // Same arithmetic, in the same order, as k_posnet_epilogue / k_shapenet_epilogue; only the addressing differs:
 // out [ldh][ldw][3] and logits [ldh][ldw][32].  A pixel's 32 logits are contiguous, so the softmax needs no transpose:
 // 4 lanes per pixel, 8 classes each (one or two 16-byte loads), two 16-byte stores.
+// The window (wx0, wy0, wh x ww) of the H x W crop goes to dst with a row pitch of ld_dst pixels, as above.
 template <int EB> __device__ __forceinline__ float ld_elem(const void *p, size_t i) {
   return EB == 4 ? ((const float *)p)[i] : bf16_to_f32(((const unsigned short *)p)[i]);
 }
 template <int EB>
-__global__ __launch_bounds__(256) void k_posnet_epilogue_nhwc(const void *out, int H, int W, int ldw, float w, float b, float *det) {
-  const int y = blockIdx.x * blockDim.x + threadIdx.x, x = blockIdx.y;
-  if (y >= W || x >= H) return;
-  auto at = [&](int i, int j, int ch) -> float { return ld_elem<EB>(out, ((size_t)i * ldw + j) * 3 + ch); };
-  float g0, g1;
-  if (H == 1) g0 = 0.f;
-  else if (x == 0) g0 = at(1, y, 0) - at(0, y, 0);
-  else if (x == H - 1) g0 = at(x, y, 0) - at(x - 1, y, 0);
-  else g0 = (at(x + 1, y, 0) - at(x - 1, y, 0)) / 2.0f;
-  if (W == 1) g1 = 0.f;
-  else if (y == 0) g1 = at(x, 1, 1) - at(x, 0, 1);
-  else if (y == W - 1) g1 = at(x, y, 1) - at(x, y - 1, 1);
-  else g1 = (at(x, y + 1, 1) - at(x, y - 1, 1)) / 2.0f;
-  float mask = 1.0f / (1.0f + expf(-at(x, y, 2)));
-  float score = w * ((g0 + g1) * mask) + b;
-  det[(size_t)x * W + y] = 1.0f / (1.0f + expf(-score));
-}
-template <int EB>
-__global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc(const void *logits, int H, int W, int ldw, float *marks) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t pix = t >> 2;
-  const int q = (int)(t & 3);
-  const bool live = pix < (size_t)H * W;           // the 4 lanes of a pixel are live together; dead lanes still shuffle
-  const int x = live ? (int)(pix / (size_t)W) : 0, y = live ? (int)(pix % (size_t)W) : 0;
-  const size_t src = ((size_t)x * ldw + y) * MPP_NCLASS + q * 8;
-  float v[8], m = -INFINITY;
-  if (EB == 4) {
-    const float4 a = *(const float4 *)((const float *)logits + src), c = *(const float4 *)((const float *)logits + src + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
-  } else {
-    const uint4 a = *(const uint4 *)((const unsigned short *)logits + src);
-    const unsigned int wd[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[2 * k] = bf16_to_f32((unsigned short)(wd[k] & 0xffffu)); v[2 * k + 1] = bf16_to_f32((unsigned short)(wd[k] >> 16)); }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) m = fmaxf(m, v[i]);
-  m = fmaxf(m, __shfl_xor(m, 1, WAVE)); m = fmaxf(m, __shfl_xor(m, 2, WAVE));
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = expf(v[i] - m); s += v[i]; }
-  s += __shfl_xor(s, 1, WAVE); s += __shfl_xor(s, 2, WAVE);
-  if (live) {
-    float4 *dst = (float4 *)(marks + pix * MPP_NCLASS + q * 8);
-    dst[0] = make_float4(v[0] / s, v[1] / s, v[2] / s, v[3] / s);
-    dst[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
-  }
-}
-extern "C" int mpp_launch_posnet_epilogue_nhwc(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w,
-                                               float b, float *det) {
-  const dim3 grid((W + 255) / 256, H);
-  if (elem_bytes == 4) hipLaunchKernelGGL(k_posnet_epilogue_nhwc<4>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, det);
-  else if (elem_bytes == 2) hipLaunchKernelGGL(k_posnet_epilogue_nhwc<2>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, det);
-  else return -1;
-  return 0;
-}
-extern "C" int mpp_launch_shapenet_epilogue_nhwc(hipStream_t st, const void *logits, int elem_bytes, int H, int W, int ldw,
-                                                 float *marks) {
-  if (((uintptr_t)logits & 15) || ((uintptr_t)marks & 15)) return -2;
-  const size_t threads = (size_t)H * W * 4;
-  const unsigned grid = (unsigned)((threads + 255) / 256);
-  if (elem_bytes == 4) hipLaunchKernelGGL(k_shapenet_epilogue_nhwc<4>, dim3(grid), dim3(256), 0, st, logits, H, W, ldw, marks);
-  else if (elem_bytes == 2) hipLaunchKernelGGL(k_shapenet_epilogue_nhwc<2>, dim3(grid), dim3(256), 0, st, logits, H, W, ldw, marks);
-  else return -1;
-  return 0;
-}
-
-// window forms (see k_posnet_epilogue_win): the window (wx0, wy0, wh x ww) of the H x W crop into dst, row pitch ld_dst pixels
-template <int EB>
-__global__ __launch_bounds__(256) void k_posnet_epilogue_nhwc_win(const void *out, int H, int W, int ldw, float w, float b, int wx0,
-                                                                  int wy0, int wh, int ww, float *dst, int ld_dst) {
+__global__ __launch_bounds__(256) void k_posnet_epilogue_nhwc(const void *out, int H, int W, int ldw, float w, float b, int wx0,
+                                                              int wy0, int wh, int ww, float *dst, int ld_dst) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
   if (j >= ww || r >= wh) return;
   const int x = wx0 + r, y = wy0 + j;
@@ -597,8 +453,8 @@ __global__ __launch_bounds__(256) void k_posnet_epilogue_nhwc_win(const void *ou
   dst[(size_t)r * ld_dst + j] = 1.0f / (1.0f + expf(-score));
 }
 template <int EB>
-__global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc_win(const void *logits, int ldw, int wx0, int wy0, int wh, int ww,
-                                                                    float *dst, int ld_dst) {
+__global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc(const void *logits, int ldw, int wx0, int wy0, int wh, int ww,
+                                                                float *dst, int ld_dst) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t pix = t >> 2;
   const int q = (int)(t & 3);
@@ -628,24 +484,24 @@ __global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc_win(const void *
     d[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
   }
 }
-extern "C" int mpp_launch_posnet_epilogue_nhwc_win(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w,
-                                                   float b, int wx0, int wy0, int wh, int ww, float *dst, int ld_dst) {
+extern "C" int mpp_launch_posnet_epilogue_nhwc(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w,
+                                               float b, int wx0, int wy0, int wh, int ww, float *dst, int ld_dst) {
   const dim3 grid((ww + 255) / 256, wh);
   if (elem_bytes == 4)
-    hipLaunchKernelGGL(k_posnet_epilogue_nhwc_win<4>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, wx0, wy0, wh, ww, dst, ld_dst);
+    hipLaunchKernelGGL(k_posnet_epilogue_nhwc<4>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, wx0, wy0, wh, ww, dst, ld_dst);
   else if (elem_bytes == 2)
-    hipLaunchKernelGGL(k_posnet_epilogue_nhwc_win<2>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, wx0, wy0, wh, ww, dst, ld_dst);
+    hipLaunchKernelGGL(k_posnet_epilogue_nhwc<2>, grid, dim3(256), 0, st, out, H, W, ldw, w, b, wx0, wy0, wh, ww, dst, ld_dst);
   else return -1;
   return 0;
 }
-extern "C" int mpp_launch_shapenet_epilogue_nhwc_win(hipStream_t st, const void *logits, int elem_bytes, int ldw, int wx0, int wy0,
-                                                     int wh, int ww, float *dst, int ld_dst) {
+extern "C" int mpp_launch_shapenet_epilogue_nhwc(hipStream_t st, const void *logits, int elem_bytes, int ldw, int wx0, int wy0,
+                                                 int wh, int ww, float *dst, int ld_dst) {
   if (((uintptr_t)logits & 15) || ((uintptr_t)dst & 15)) return -2;
   const unsigned grid = (unsigned)(((size_t)wh * ww * 4 + 255) / 256);
   if (elem_bytes == 4)
-    hipLaunchKernelGGL(k_shapenet_epilogue_nhwc_win<4>, dim3(grid), dim3(256), 0, st, logits, ldw, wx0, wy0, wh, ww, dst, ld_dst);
+    hipLaunchKernelGGL(k_shapenet_epilogue_nhwc<4>, dim3(grid), dim3(256), 0, st, logits, ldw, wx0, wy0, wh, ww, dst, ld_dst);
   else if (elem_bytes == 2)
-    hipLaunchKernelGGL(k_shapenet_epilogue_nhwc_win<2>, dim3(grid), dim3(256), 0, st, logits, ldw, wx0, wy0, wh, ww, dst, ld_dst);
+    hipLaunchKernelGGL(k_shapenet_epilogue_nhwc<2>, dim3(grid), dim3(256), 0, st, logits, ldw, wx0, wy0, wh, ww, dst, ld_dst);
   else return -1;
   return 0;
 }

@@ -454,6 +454,11 @@ class ScoreMapNets:
         self._keep = None
         return det, marks
 
+    def _whole_window(self, H: int, W: int):
+        """``win`` of a whole-crop forward: new H x W maps as the window at (0, 0), through the same kernels as a tile"""
+        det = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        return 0, 0, det, [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
+
     def _forward(self, img: Tensor, win=None) -> Tuple[Tensor, List[Tensor]]:
         """Both nets and their epilogues on the whole of img [3,H,W]; ``win`` = (wx0, wy0, det, marks): only that window of
         the maps, written into the given views (det [h,w], marks 3 x [h,w,32]) instead of new maps."""
@@ -464,19 +469,12 @@ class ScoreMapNets:
         big = padded.shape[1] * padded.shape[2] >= self.min_fused_pixels
         if self.layout == "nhwc" and self.fused and big and padded.shape[1] >= 16 and padded.shape[2] >= 16:
             xi = padded.permute(1, 2, 0).contiguous().unsqueeze(0).permute(0, 3, 1, 2)      # [1,3,H,W] over NHWC memory
-            if win is None:
-                det = torch.empty((H, W), dtype=torch.float32, device=self.device)
-                marks = [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
-            else:
-                wx0, wy0, det, marks = win
+            wx0, wy0, det, marks = win or self._whole_window(H, W)
             cur = torch.cuda.current_stream(self.device)
 
             def pos_part():
                 pos_out = self._cl(self._head(self.pos.final_layer, self._backbone_nhwc(self.pos.backbone, xi)))
-                if win is None:
-                    self.ctx.posnet_epilogue_nhwc(pos_out, H, W, self.div_w, self.div_b, det)
-                else:
-                    self.ctx.posnet_epilogue_nhwc_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
+                self.ctx.posnet_epilogue_nhwc_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
                 return pos_out
 
             def shp_part():
@@ -486,17 +484,11 @@ class ScoreMapNets:
                     # the three 1x1 heads, their biases and the softmax in ONE pass over h (csrc/mpp_conv.hip): 8.6 GB of
                     # traffic on a 4096 x 4096 image instead of 38 GB
                     h = self._cl(h)
-                    if win is None:
-                        self.ctx.shapenet_heads(h, heads[0], heads[1], H, W, marks)
-                    else:
-                        self.ctx.shapenet_heads_win(h, heads[0], heads[1], H, W, wx0, wy0, marks)
+                    self.ctx.shapenet_heads_win(h, heads[0], heads[1], H, W, wx0, wy0, marks)
                     return h
                 logits = [self._cl(self._head(fl[0], h)) for fl in self.shp.final_layers]
                 for k in range(3):
-                    if win is None:
-                        self.ctx.shapenet_epilogue_nhwc(logits[k], H, W, marks[k])
-                    else:
-                        self.ctx.shapenet_epilogue_nhwc_win(logits[k], H, W, wx0, wy0, marks[k])
+                    self.ctx.shapenet_epilogue_nhwc_win(logits[k], H, W, wx0, wy0, marks[k])
                 return logits
 
             if self.two_streams:
@@ -556,19 +548,10 @@ class ScoreMapNets:
     def _epilogues(self, pos_out: Tensor, logits: List[Tensor], H: int, W: int, win=None) -> Tuple[Tensor, List[Tensor]]:
         pos_out = pos_out[0].float().contiguous()
         logits = [t[0].float().contiguous() for t in logits]
-        if win is None:
-            det = torch.empty((H, W), dtype=torch.float32, device=self.device)
-            marks = [torch.empty((H, W, 32), dtype=torch.float32, device=self.device) for _ in range(3)]
-        else:
-            wx0, wy0, det, marks = win
+        wx0, wy0, det, marks = win or self._whole_window(H, W)
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        if win is None:
-            self.ctx.posnet_epilogue(pos_out, H, W, self.div_w, self.div_b, det)
-            for k in range(3):
-                self.ctx.shapenet_epilogue(logits[k], H, W, marks[k])
-        else:
-            self.ctx.posnet_epilogue_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
-            for k in range(3):
-                self.ctx.shapenet_epilogue_win(logits[k], H, W, wx0, wy0, marks[k])
+        self.ctx.posnet_epilogue_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
+        for k in range(3):
+            self.ctx.shapenet_epilogue_win(logits[k], H, W, wx0, wy0, marks[k])
         self._keep = (pos_out, logits)        # alive until the kernels on this stream have consumed them
         return det, marks

@@ -1,11 +1,11 @@
 """The three hand-written kernels of the float32 score-map forward (csrc/mpp_conv.hip: ``k_conv3x3_c32``, ``k_conv3x3_stem``,
-``k_shapenet_heads`` and its window copy) against the float64 references and derived bounds of tests/unet_conv_ref.py, at
+``k_shapenet_heads``) against the float64 references and derived bounds of tests/unet_conv_ref.py, at
 the smallest shapes at which each mechanism of the kernels exists: the launcher's minimum, one tile, one past a tile, and
 one shape at which every workgroup of the persistent convolution runs two or three tiles and some waves of the heads run
 their loop twice (both asserted from the device's compute-unit count, not assumed).  Every output buffer the binding lets
 the caller provide is filled with NaN first: a store that never happens fails the comparison.  What must be exact (a
 repeated call, a source whose weights are zero, a pixel's independence of the tile, stage and workgroup that computed it,
-the window form of the heads) is compared bit for bit.  tests/test_unet_conv_ref_host.py pins the references and shows
+windows of the heads against their whole-crop window) is compared bit for bit.  tests/test_unet_conv_ref_host.py pins the references and shows
 that the bounds are neither too tight for float32 nor loose enough to pass a wrong kernel."""
 import pytest
 import torch

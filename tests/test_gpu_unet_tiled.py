@@ -113,6 +113,22 @@ def test_window_epilogues_equal_the_full_crop_epilogue_bit_for_bit(modules, H, W
         ctx.shapenet_epilogue_win(logits, H, W, 0, 0, torch.zeros((H, W, 16, 2), device="cuda"))
 
 
+def test_the_full_shapenet_epilogue_refuses_marks_off_a_16_byte_boundary():
+    """The full form runs the window kernel, whose float4 stores need aligned marks: a map 4 bytes into its storage is refused
+    before any launch.  2 x 69: one full 64-pixel block (the 16-byte loads) plus a 5-pixel tail (the scalar loads)."""
+    ctx = hip_api.MppContext(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    H, W = 2, 69
+    logits = torch.randn((32, 8, 72), generator=torch.Generator().manual_seed(69)).cuda()
+    store = torch.full((H * W * 32 + 1,), SENTINEL, device="cuda")
+    marks = store[1:].view(H, W, 32)
+    assert marks.is_contiguous() and marks.data_ptr() % 16 == 4
+    with pytest.raises(hip_api.MppError, match="aligned"):
+        ctx.shapenet_epilogue(logits, H, W, marks)
+    torch.cuda.synchronize()
+    assert bool((store == SENTINEL).all())
+
+
 # ---- 2.-3. tiled forward ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("path,dtype", [("fused", torch.float32), ("module", torch.float32), ("fused", torch.bfloat16),
                                         ("module", torch.bfloat16)])

@@ -1,5 +1,5 @@
-"""Float64 references of the three kernels of csrc/mpp_conv.hip (``k_conv3x3_c32``, ``k_conv3x3_stem``, ``k_shapenet_heads``
-and its window copy) with an error bound per output that is derived from the float32 format, not measured.  Plain torch
+"""Float64 references of the three kernels of csrc/mpp_conv.hip (``k_conv3x3_c32``, ``k_conv3x3_stem``, ``k_shapenet_heads``,
+whose full form is its whole-crop window) with an error bound per output that is derived from the float32 format, not measured.  Plain torch
 on the CPU; nothing of the library is imported.  tests/test_unet_conv_ref_host.py shows that the bounds hold for a
 float32 stand-in and that wrong kernels break them; tests/test_gpu_unet_conv_float64.py holds the kernels to them.
 
@@ -13,7 +13,7 @@ import torch.nn.functional as F
 U = 2.0 ** -24
 FLT_MIN = 2.0 ** -126
 
-#: grid cap of mpp_launch_shapenet_heads / _win (workgroups of four waves, one group of 32 pixels per wave and iteration)
+#: grid cap of mpp_launch_shapenet_heads (workgroups of four waves, one group of 32 pixels per wave and iteration)
 HEADS_MAX_GRID = 2048
 #: output tile of a k_conv3x3_c32 workgroup
 CV_ROWS, CV_COLS = 8, 64
