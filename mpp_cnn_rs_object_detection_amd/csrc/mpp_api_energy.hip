@@ -173,6 +173,7 @@ extern "C" int mpp_merge_score(mpp_ctx *c, double distance, int cap, int32_t *n_
   if (max_n > MPP_MERGE_MAX_POINTS || (size_t)((c->cap + 7) & ~7) * 17 > (size_t)MPP_DEDUPE_LDS_MAX)      // (the walk's working set lives in LDS)
     return fail(c, -4, "merge_score: a tile holds %d points (the device walk takes at most %d): merge it on the host", max_n,
                 MPP_MERGE_MAX_POINTS);
+  // (the walk carries a position as two 16-bit halves; mpp_set_maps is the guard: it takes no side above 65535)
   const size_t TC = (size_t)T * c->cap;
   DevBuf<double> d_dE, ts, tr, ta;
   DevBuf<int32_t> work, slot_of, tx, ty, d_rem, gs, gc, gi;       // (gs, gc, gi: the candidate grids, where they pay)
@@ -182,7 +183,8 @@ extern "C" int mpp_merge_score(mpp_ctx *c, double distance, int cap, int32_t *n_
   A(work, TC); A(slot_of, TC); A(tx, TC); A(ty, TC); A(d_rem, (size_t)T);
   std::vector<int32_t> h_rem(T, 0);
   if (e == hipSuccess && max_n > 0) {
-    const int dist2 = (int)floor(distance * distance + 1e-9);
+    // (64 bits: 65535^2 + 65535^2 does not fit an int; beyond that every pair of points is within the distance)
+    const long long dist2 = (long long)floor(fmin(distance * distance + 1e-9, 1e10));
     // the from-scratch energies look their neighbours up in per-tile candidate grids, built on the device before each of
     // the two scorings (the removals in between move points)
     const int ncell = c->hp.nx * c->hp.ny;

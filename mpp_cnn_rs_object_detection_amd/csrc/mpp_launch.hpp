@@ -39,7 +39,7 @@ void mpp_launch_papangelou_tiles(hipStream_t st, const DevParams *P, const TileR
                                  double *dE, const int32_t *grid_start, const int32_t *grid_items, int sstride, int istride);
 void mpp_launch_grid_build_all(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int ncell,
                                int cap, int32_t *start, int32_t *cursor, int32_t *items);
-void mpp_launch_dedupe_tiles(hipStream_t st, const TileRef *tiles, int n_tiles, int max_n, int cap, const double *dE, int dist2,
+void mpp_launch_dedupe_tiles(hipStream_t st, const TileRef *tiles, int n_tiles, int max_n, int cap, const double *dE, long long dist2,
                              int32_t *work, int32_t *slot_of, int32_t *tx, int32_t *ty, double *ts, double *tr, double *ta,
                              int32_t *n_removed);
 void mpp_launch_remap_table(hipStream_t st, const float *m, size_t n, double coef, double icpt, double *out);

@@ -312,7 +312,9 @@ __device__ __forceinline__ int wave_min_i(int v) {
 }
 // flags[tile][i] = point i has another point within the distance (the others are their own best and never removed: the walk
 // below only visits the flagged ones -- 5 % of the points of a 5 000-point image).  One lane per point.
-__global__ __launch_bounds__(64) void k_has_neighbour(const TileRef *tiles, int cap, int dist2, int32_t *flags) {
+// (squared distances in 64 bits, here and in the walk: two points 46341 or more pixels apart on a wide support overflow an
+// int, wrap to a negative number and would pass for neighbours)
+__global__ __launch_bounds__(64) void k_has_neighbour(const TileRef *tiles, int cap, long long dist2, int32_t *flags) {
   const int tile = blockIdx.y, i = blockIdx.x * WAVE + threadIdx.x;
   TileRef t = tiles[tile];
   const int n = *t.n;
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(64) void k_has_neighbour(const TileRef *tiles, int 
   int f = 0;
   for (int j = 0; j < n; ++j) {
     const int dx = t.px[j] - xi, dy = t.py[j] - yi;
-    f |= (j != i && dx * dx + dy * dy <= dist2) ? 1 : 0;
+    f |= (j != i && (long long)dx * dx + (long long)dy * dy <= dist2) ? 1 : 0;
   }
   flags[(size_t)tile * cap + i] = f;
 }
@@ -332,7 +334,7 @@ __global__ __launch_bounds__(64) void k_has_neighbour(const TileRef *tiles, int 
 // non-finite best score: numpy's argmax (a NaN first, else the first infinity).  Then the removals in index order, each
 // moving the last point into the hole (EPointsSet.remove), which fixes the order of the survivors.  One wave per tile.
 // work: [T][cap] the neighbour flags of k_has_neighbour; slot_of, tx .. ta: [T][cap] scratch for the removals (permutation, then copies of the configuration).
-__global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int cap, const double *dE, int dist2, const int32_t *work,
+__global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int cap, const double *dE, long long dist2, const int32_t *work,
                                                      int32_t *slot_of, int32_t *tx, int32_t *ty, double *ts, double *tr,
                                                      double *ta, int32_t *n_removed) {
   const int tile = blockIdx.x, lane = threadIdx.x;
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int c
     const unsigned long long m = __ballot(f);
     if (f) {
       const int pos = nl + __popcll(m & below);
-      fj[pos] = j; fxy[pos] = (t.px[j] & 0xffff) | (t.py[j] << 16); fsc[pos] = exp(-d[j]);
+      fj[pos] = j; fxy[pos] = (int32_t)((uint32_t)(t.px[j] & 0xffff) | ((uint32_t)t.py[j] << 16)); fsc[pos] = exp(-d[j]);
     }
     nl += __popcll(m);
   }
@@ -375,7 +377,7 @@ __global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int c
     for (int lj = lane; lj < nl; lj += WAVE) {
       const int j = fj[lj], xy = fxy[lj];
       const int dx = (xy & 0xffff) - xi, dy = ((xy >> 16) & 0xffff) - yi;
-      if (alive[j] && dx * dx + dy * dy <= dist2) {
+      if (alive[j] && (long long)dx * dx + (long long)dy * dy <= dist2) {
         const double sc = fsc[lj];
         ++cnt;
         if (sc != sc) first_nan = j < first_nan ? j : first_nan;
@@ -394,7 +396,7 @@ __global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int c
       for (int lj = lane; lj < nl; lj += WAVE) {
         const int j = fj[lj], xy = fxy[lj];
         const int dx = (xy & 0xffff) - xi, dy = ((xy >> 16) & 0xffff) - yi;
-        if (alive[j] && dx * dx + dy * dy <= dist2) {
+        if (alive[j] && (long long)dx * dx + (long long)dy * dy <= dist2) {
           const double sc = fsc[lj];
           if (finite ? sc >= thr : sc == top) best = j < best ? j : best;
         }
@@ -404,7 +406,7 @@ __global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int c
     for (int lj = lane; lj < nl; lj += WAVE) {
       const int j = fj[lj], xy = fxy[lj];
       const int dx = (xy & 0xffff) - xi, dy = ((xy >> 16) & 0xffff) - yi;
-      if (j != best && alive[j] && dx * dx + dy * dy <= dist2) alive[j] = 0;
+      if (j != best && alive[j] && (long long)dx * dx + (long long)dy * dy <= dist2) alive[j] = 0;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -415,7 +417,7 @@ __global__ __launch_bounds__(64) void k_dedupe_tiles(const TileRef *tiles, int c
   for (int j = lane; j < n; j += WAVE) {
     sl[j] = j;
     ts[(size_t)tile * cap + j] = t.ps[j]; tr[(size_t)tile * cap + j] = t.pr[j]; ta[(size_t)tile * cap + j] = t.pa[j];
-    ty[(size_t)tile * cap + j] = (t.px[j] & 0xffff) | (t.py[j] << 16);
+    ty[(size_t)tile * cap + j] = (int32_t)((uint32_t)(t.px[j] & 0xffff) | ((uint32_t)t.py[j] << 16));
     orig_at[j] = j;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -449,7 +451,7 @@ extern "C" void mpp_launch_papangelou_tiles(hipStream_t st, const DevParams *P, 
   hipLaunchKernelGGL(k_papangelou_tiles, dim3(max_n, n_tiles), dim3(64), 0, st, P, tiles, cap, dE, Grid{grid_start, grid_items}, sstride,
                      istride);
 }
-extern "C" void mpp_launch_dedupe_tiles(hipStream_t st, const TileRef *tiles, int n_tiles, int max_n, int cap, const double *dE, int dist2,
+extern "C" void mpp_launch_dedupe_tiles(hipStream_t st, const TileRef *tiles, int n_tiles, int max_n, int cap, const double *dE, long long dist2,
                                         int32_t *work, int32_t *slot_of, int32_t *tx, int32_t *ty, double *ts, double *tr,
                                         double *ta, int32_t *n_removed) {
   if (n_tiles <= 0) return;
