@@ -196,6 +196,12 @@ int mpp_pack_detections(mpp_ctx *ctx, int n, const int32_t *tile_ids, const int3
                         double *out_dev, int32_t *count);
 /* total_energy(): combined energy and, optionally, [n][n_unit+n_pair] per-point vectors */
 int mpp_total_energy(mpp_ctx *ctx, int tile, double *energy, double *vectors_or_null);
+/* total_energy() of every chain of the ctx at once (n_chains = tiles x "replicas"), from the state the last mpp_run /
+ * mpp_set_points left (the state mpp_get_points_all reads): energy [n_chains], energy[t] bit for bit what
+ * mpp_total_energy(ctx, t, ..) returns (the same kernel, the points summed in slot order on the device), 0.0 for an empty
+ * chain.  A fixed number of launches, one copy of n_chains doubles and one synchronise, however many chains; honours
+ * "scratch_grid_min_points".  What the choice among restarts reads (sampler.select_replicas). */
+int mpp_total_energy_all(mpp_ctx *ctx, double *energy);
 /* energy_delta(Perturbation) for a batch of perturbations with list removals/additions:
  * case i removes slots rem[rem_off[i]..rem_off[i+1]) and adds rectangles add_off[i]..add_off[i+1] */
 int mpp_delta_batch(mpp_ctx *ctx, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,

@@ -25,7 +25,14 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def main():
+def _restarts(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"{text}: at least 1")
+    return v
+
+
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-m", "--model", help="model to use")
     parser.add_argument("-d", "--dataset", help="dataset to use, defaults to the one specified in config")
@@ -42,7 +49,14 @@ def main():
                         help="at most this many (padded) pixels per U-Net forward: larger images are walked in crops whose "
                              "maps are stitched exactly (unet.chunk_plan); default: the whole image at once, in crops only "
                              "if that runs out of device memory")
-    args = parser.parse_args()
+    parser.add_argument("--restarts", type=_restarts, default=None,
+                        help="(-m mpp, infer / infereval) independent chains per tile, the lowest-energy one is kept; "
+                             "overrides inference.restarts of the config (default 1)")
+    return parser
+
+
+def main():
+    args = build_parser().parse_args()
 
     from mpp_cnn_rs_object_detection_amd.paths import get_model_base_path, resolve_model_config_path
     with open(resolve_model_config_path(args.config)) as f:
@@ -64,6 +78,8 @@ def main():
 
     if args.model == "mpp":
         from mpp_cnn_rs_object_detection_amd.mpp_model import MPPModel
+        if args.restarts is not None and args.procedure in ("infer", "infereval"):
+            config.setdefault("inference", {})["restarts"] = args.restarts
         nets = None
         if args.unet:
             nets = load_nets(config, local_rank, args.unet_max_pixels)

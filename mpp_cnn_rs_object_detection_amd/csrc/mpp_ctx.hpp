@@ -112,6 +112,7 @@ struct mpp_ctx : TileMem {
   // uniform grid over one tile's configuration for the from-scratch energies (built per call; see mpp_scratch.hip)
   DevWs g_cells, g_items;            // cell starts [ncell + 1] then cursors [ncell]; the points by cell [cap]
   int grid_min_points = 256;
+  DevWs energy_ws;                   // mpp_total_energy_all: every chain's point energies, their sums, the chains' grids
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
   RescaleWs rescale;                 // workspace of mpp_rescale (mpp_rescale.hip)

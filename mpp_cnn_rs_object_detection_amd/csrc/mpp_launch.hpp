@@ -63,6 +63,8 @@ void mpp_launch_pack_detections(hipStream_t st, const TileRef *tiles, int n_tile
                                 const int32_t *anchors, int capacity, double *out);
 void mpp_launch_point_energies(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile, int n, double *e_pts,
                                double *vectors, const int32_t *grid_start, const int32_t *grid_items);
+void mpp_launch_chain_energies(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_chains, int cap, double *e_pts,
+                               double *energy, const int32_t *grid_start, const int32_t *grid_items, int sstride, int grid_min);
 void mpp_launch_delta_batch(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile, int n_cases,
                             const int32_t *rem_off, const int32_t *rem, const int32_t *add_off, const int32_t *add_xy,
                             const double *add_marks, double *dE, const int32_t *grid_start, const int32_t *grid_items);

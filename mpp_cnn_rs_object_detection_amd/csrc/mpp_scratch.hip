@@ -171,15 +171,33 @@ extern "C" void mpp_launch_grid_build_all(hipStream_t st, const DevParams *P, co
                      ncell + 1, cap);
 }
 
-__global__ void k_point_energies(const DevParams *P, const TileRef *tiles, int tile, double *e_pts, double *vectors, Grid g) {
+// (blockIdx.y: the launch takes gridDim.y consecutive tiles, their energies `estride` and their grids `sstride` / `istride`
+// entries apart -- 1 tile: 0; a tile of fewer than `grid_min` points scans although a grid is given.  One kernel for
+// mpp_total_energy and mpp_total_energy_all: the two return the same bits because they run the same code.)
+__global__ void k_point_energies(const DevParams *P, const TileRef *tiles, int tile, double *e_pts, double *vectors, Grid g,
+                                 int estride, int sstride, int istride, int grid_min) {
+  tile += blockIdx.y; e_pts += (size_t)blockIdx.y * estride;
   TileRef t = tiles[tile];
   int n = *t.n, i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  if (i >= n || (estride > 0 && i >= estride)) return;
+  if (g.start && n >= grid_min) { g.start += (size_t)blockIdx.y * sstride; g.items += (size_t)blockIdx.y * istride; }
+  else g = Grid{nullptr, nullptr};
   Overlay none{0, nullptr, 0, nullptr, nullptr};
   int nt = P->model.n_unit + P->model.n_pair;
   double vec[MPP_MAX_UNIT + MPP_MAX_PAIR];
   e_pts[i] = point_energy(P, t, n, tile_rect(t, i), i, -1, none, vec, g);
   if (vectors) for (int k = 0; k < nt; ++k) vectors[(size_t)i * nt + k] = vec[k];
+}
+// energy[t] = the sum of chain t's point energies in slot order, from 0.0: the loop of mpp_total_energy, one lane per chain
+// (a few hundred additions); an empty chain gives 0.0
+__global__ void k_chain_energy_sums(const TileRef *tiles, int n_chains, const double *e_pts, int estride, double *energy) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_chains) return;
+  const int n = min(*tiles[t].n, estride);
+  const double *e = e_pts + (size_t)t * estride;
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += e[i];
+  energy[t] = s;
 }
 
 // one workgroup per perturbation:  dE = sum_u [e_u(after)-e_u(before)] + sum e_added - sum e_removed
@@ -524,7 +542,18 @@ extern "C" void mpp_launch_point_energies(hipStream_t st, const DevParams *P, co
                                           const int32_t *grid_items) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_point_energies, dim3((n + 127) / 128), dim3(128), 0, st, P, tiles, tile, e_pts, vectors,
-                     Grid{grid_start, grid_items});
+                     Grid{grid_start, grid_items}, 0, 0, 0, 0);
+}
+// the point energies of chains 0 .. n_chains - 1 (e_pts [n_chains][cap], slots past a chain's count untouched), then their
+// sums in slot order (energy [n_chains]); the grids are those of mpp_launch_grid_build_all or nullptr
+extern "C" void mpp_launch_chain_energies(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_chains, int cap,
+                                          double *e_pts, double *energy, const int32_t *grid_start, const int32_t *grid_items,
+                                          int sstride, int grid_min) {
+  if (n_chains <= 0 || cap <= 0) return;
+  hipLaunchKernelGGL(k_point_energies, dim3((cap + 127) / 128, n_chains), dim3(128), 0, st, P, tiles, 0, e_pts, (double *)nullptr,
+                     Grid{grid_start, grid_items}, cap, sstride, cap, grid_min);
+  hipLaunchKernelGGL(k_chain_energy_sums, dim3((n_chains + 63) / 64), dim3(64), 0, st, tiles, n_chains, (const double *)e_pts, cap,
+                     energy);
 }
 extern "C" void mpp_launch_delta_batch(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile,
                                        int n_cases, const int32_t *rem_off, const int32_t *rem,

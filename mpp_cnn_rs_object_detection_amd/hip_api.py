@@ -24,7 +24,7 @@ MAX_UNIT, MAX_PAIR, NCLASS, NKERNEL = 8, 2, 32, 10
 ABI_SYMBOLS = [
     "mpp_create", "mpp_destroy", "mpp_last_error", "mpp_set_stream", "mpp_synchronize", "mpp_set_option",
     "mpp_get_option", "mpp_set_maps", "mpp_set_image", "mpp_set_model", "mpp_set_kernels", "mpp_set_points", "mpp_get_points",
-    "mpp_count", "mpp_get_points_all", "mpp_pack_detections", "mpp_total_energy", "mpp_delta_batch", "mpp_delta_vectors", "mpp_papangelou", "mpp_merge_score", "mpp_naive_init", "mpp_set_schedule",
+    "mpp_count", "mpp_get_points_all", "mpp_pack_detections", "mpp_total_energy", "mpp_total_energy_all", "mpp_delta_batch", "mpp_delta_vectors", "mpp_papangelou", "mpp_merge_score", "mpp_naive_init", "mpp_set_schedule",
     "mpp_replay", "mpp_run", "mpp_set_chain_keys", "mpp_step_index", "mpp_last_kernel_ms", "mpp_posnet_epilogue",
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
     "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
@@ -151,6 +151,7 @@ def load_library(path: Optional[str] = None):
         "mpp_get_points_all": (i32, [vp, i32, vp, vp, vp]),
         "mpp_pack_detections": (i32, [vp, i32, vp, vp, i32, vp, C.POINTER(C.c_int32)]),
         "mpp_total_energy": (i32, [vp, i32, C.POINTER(dbl), vp]),
+        "mpp_total_energy_all": (i32, [vp, vp]),
         "mpp_delta_batch": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
         "mpp_delta_vectors": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
         "mpp_papangelou": (i32, [vp, i32, vp]),
@@ -439,6 +440,12 @@ class MppContext:
         vec = np.zeros((self.count(tile), self.n_terms), np.float64) if return_vectors else None
         self._check(self._L.mpp_total_energy(self._h, tile, C.byref(e), _ptr(vec)))
         return (e.value, vec) if return_vectors else e.value
+
+    def total_energy_all(self) -> np.ndarray:
+        """``total_energy(t)`` of every chain of the context, bit for bit, with one device read (``mpp_total_energy_all``)"""
+        e = np.zeros(self.get_option("n_chains"), np.float64)
+        self._check(self._L.mpp_total_energy_all(self._h, _ptr(e)))
+        return e
 
     @staticmethod
     def _pack_cases(removals, add_xy, add_marks):

@@ -129,6 +129,19 @@ def _gc_paused(fn):
     return wrapped
 
 
+def check_restarts(config: Dict, world_size: int = 1) -> int:
+    """``inference.restarts`` of a config (default 1): an integer >= 1, the independent chains run per tile of which the
+    one with the lowest energy is kept.  More than one is a one-GPU feature: ranks that share ONE image (its tiles dealt
+    to them) cannot use it -- such an image fills every GPU already, and the gather packs chains 0..n-1."""
+    r = (config.get("inference") or {}).get("restarts", 1)
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 1:
+        raise ValueError(f"inference.restarts must be an integer >= 1, got {r!r}")
+    if r > 1 and world_size > 1:
+        raise ValueError(f"inference.restarts = {r} needs an image sampled by one GPU; {world_size} ranks share this one "
+                         f"(set inference.restarts to 1)")
+    return int(r)
+
+
 class MPPModel:
     def __init__(self, config: Dict, phase: str = "val", overwrite: bool = False, load: bool = False,
                  dataset: str = None, device: int = 0, nets=None, spec_waves: Optional[int] = None):
@@ -301,6 +314,7 @@ class MPPModel:
         every rank scores the gathered points of ITS tiles on its own maps (their neighbours lie inside the region by
         construction), one all-reduce shares the scores, every rank takes the same ``distance_merge`` decision, and a
         second scoring + all-reduce gives the final Papangelou scores of the survivors."""
+        check_restarts(self.config, world_size)               # (before any collective: every rank raises alike)
         shape = tuple(int(v) for v in image_data.shape[:2])
         patch, anchors = self.tile_layout(shape)
         n_tiles = len(anchors)
@@ -352,7 +366,9 @@ class MPPModel:
             results = [Detections(*r) for r in raw]            # (arrays that read like lists of Rectangle)
         self.last_run = {"seed": seed, "anchors": anchors, "patch": patch, "mine": mine, "tile_results": results,
                          "total_steps": total, "snapshot_step": snaps[-1] if snaps else total - 1,
-                         "kernel_ms": sampler.kernel_ms if sampler else 0.0}
+                         "kernel_ms": sampler.kernel_ms if sampler else 0.0,
+                         "replica_energy": sampler.replica_energy if sampler else None,
+                         "replica_winner": sampler.replica_winner if sampler else None}
         if world_size == 1 and arrays:
             # merge + scores on the device (``mpp_merge_score``); an image with more detections than its walk takes: the host
             xy = [r[0] + np.asarray(t.crop_data["tl_anchor"], dtype=np.int32) for r, t in zip(raw, tiles)]
@@ -435,7 +451,8 @@ class MPPModel:
         start = time.perf_counter()
         sampler = TileBatchSampler(tiles, self.energy_setup, self.energy_model, device=self.device,
                                    spec_waves=self.spec_waves, use_split_merge=bool(p.get("use_split_merge", False)),
-                                   stacked_maps=getattr(self, "_stacked_maps", None))
+                                   stacked_maps=getattr(self, "_stacked_maps", None),
+                                   restarts=check_restarts(self.config, world_size))
         self._stacked_maps = None
         sampler.init("naive")
         pack = None
@@ -453,7 +470,17 @@ class MPPModel:
                      f"{time.perf_counter() - start:.2f}s (kernel {sampler.kernel_ms:.1f} ms)")
         if sampler.hbm_chains:
             logging.info(f"{sampler.hbm_chains} chain(s) outgrew the LDS and continued with their state in device memory")
+        self._log_restarts(sampler)
         return sampler
+
+    @staticmethod
+    def _log_restarts(sampler):
+        if sampler.replica_winner is None:
+            return
+        e, w = sampler.replica_energy, sampler.replica_winner
+        gain = e[0] - e[w, np.arange(len(w))]
+        logging.info(f"restarts: {int(np.count_nonzero(w))} of {len(w)} tile(s) keep another replica than 0 of "
+                     f"{sampler.restarts}, summed energy gain {float(np.nansum(gain[w != 0])):.3f}")
 
     #: tiles sampled per launch when a dataset is inferred on one GPU: tiles of consecutive images are sampled together
     #: (one workgroup per tile: a launch wants at least the 256 CUs' worth), each with the seed and chain id of its image
@@ -472,6 +499,7 @@ class MPPModel:
         alpha, T_target, total, snaps = resolve_schedule(1, p["init_temperature"], p["alpha_t"], p["burn_in"],
                                                           p["samples_interval"], p["target_temperature"],
                                                           p.get("iter_multiplier"))
+        restarts = check_restarts(self.config)
         layout, tiles, seeds, chains = [], [], [], []
         for k, (data, region) in enumerate(zip(images, regions)):
             patch, anchors = self.tile_layout(tuple(int(v) for v in data.shape[:2]))
@@ -489,17 +517,20 @@ class MPPModel:
             raise ValueError("images whose tiles differ in size cannot share a launch")
         start = time.perf_counter()
         sampler = TileBatchSampler(tiles, self.energy_setup, self.energy_model, device=self.device, spec_waves=self.spec_waves,
-                                   use_split_merge=bool(p.get("use_split_merge", False)), keys=(seeds, chains))
+                                   use_split_merge=bool(p.get("use_split_merge", False)),
+                                   keys=(seeds, chains) if restarts == 1 else (seeds, chains, [n for _, n in layout for _ in range(n)]),
+                                   restarts=restarts)
         sampler.init("naive")
         # merge + scores on the device for the whole batch when the images share a shape and a picture-free energy setup
         # (the classic image energies read a per-image picture the batch context does not hold)
         on_device = (len({tuple(int(v) for v in r.shape[:2]) for r in regions}) == 1 and E.classic_image(sampler.model_units) is None
                      and not self.config["inference"].get("host_merge", False))
         out = sampler.run(total, snaps, 1, p["init_temperature"], alpha, T_target, seed=0, chain0=0, as_arrays=on_device)
-        logging.info(f"ran {len(tiles)} rjmcmc chains ({len(images)} images) of {total} steps in one launch in "
+        logging.info(f"ran {len(tiles) * restarts} rjmcmc chains ({len(images)} images) of {total} steps in one launch in "
                      f"{time.perf_counter() - start:.2f}s (kernel {sampler.kernel_ms:.1f} ms)")
         if sampler.hbm_chains:
             logging.info(f"{sampler.hbm_chains} chain(s) outgrew the LDS and continued with their state in device memory")
+        self._log_restarts(sampler)
         if on_device:
             aggregated = []
             for first, n in layout:
@@ -647,7 +678,8 @@ class MPPModel:
         # ---- this rank's images: the tiles of consecutive images share a launch (``infer_images``)
         def inferred():
             stream = zip(own, self._prefetch_images([todo[k][0] for k in own], dataset, subset))
-            limit = int(self.config["inference"].get("tiles_per_launch", self.TILES_PER_LAUNCH))
+            # (tiles_per_launch limits chains: with R restarts a batch takes limit // R tiles, but at least one image)
+            limit = int(self.config["inference"].get("tiles_per_launch", self.TILES_PER_LAUNCH)) // check_restarts(self.config)
             batch, n_batch, patch0 = [], 0, None
 
             def flush():

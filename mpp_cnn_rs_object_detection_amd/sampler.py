@@ -79,16 +79,58 @@ def choose_spec_waves(ctx: MppContext, n_tiles: int, use_split_merge: bool = Fal
     return best
 
 
+def replica_chain_ids(n_tiles: int, restarts: int, chain0: int = 0) -> np.ndarray:
+    """Chain ids of the ``restarts`` replicas of an image's ``n_tiles`` tiles, uint32 ``[restarts * n_tiles]`` in the
+    context's chain order (chain ``r * n_tiles + i``): replica ``r`` of tile ``i`` draws from ``chain0 + i + r * n_tiles``.
+    ``n_tiles`` is the tile count of the whole image, so no two chains of an image share an id and replica 0 keeps the id
+    the tile has without restarts."""
+    n_tiles, restarts, chain0 = int(n_tiles), int(restarts), int(chain0)
+    if n_tiles < 0 or restarts < 1 or chain0 < 0:
+        raise ValueError(f"replica_chain_ids: n_tiles {n_tiles}, restarts {restarts}, chain0 {chain0}")
+    if n_tiles and chain0 + restarts * n_tiles - 1 > 2 ** 32 - 1:
+        raise ValueError(f"replica_chain_ids: chain id {chain0 + restarts * n_tiles - 1} does not fit 32 bits "
+                         f"({restarts} restarts of {n_tiles} tiles from chain {chain0})")
+    return (chain0 + np.arange(restarts * n_tiles, dtype=np.int64)).astype(np.uint32)
+
+
+def select_replicas(energy, n_tiles: int) -> np.ndarray:
+    """The winning replica of every tile, int64 ``[n_tiles]``, from the chains' energies ``[restarts * n_tiles]`` (chain
+    ``r * n_tiles + i``) or ``[restarts, n_tiles]``.  Per tile the walk starts at replica 0; replica ``r`` replaces the
+    best so far when its energy is strictly lower, or when the best is not finite and ``r``'s is: ties go to the lowest
+    replica, a non-finite energy never beats a finite one, and replica 0 wins when none is finite."""
+    n_tiles = int(n_tiles)
+    e = np.asarray(energy, dtype=np.float64).reshape(-1, n_tiles) if n_tiles else np.zeros((1, 0))
+    if e.shape[0] < 1:
+        raise ValueError("select_replicas: no energies")
+    best, best_e = np.zeros(n_tiles, np.int64), e[0].copy()
+    with np.errstate(invalid="ignore"):
+        for r in range(1, e.shape[0]):
+            take = (e[r] < best_e) | (~np.isfinite(best_e) & np.isfinite(e[r]))
+            best[take], best_e[take] = r, e[r][take]
+    return best
+
+
 class TileBatchSampler:
     """All tiles of an image (or of a batch of images) sampled concurrently on one GPU."""
 
     def __init__(self, tiles: Sequence[ImageWMaps], energy_setup, energy_combinator, device: int = 0,
                  point_capacity: int = 1024, spec_waves: Optional[int] = 8, ctx: Optional[MppContext] = None,
-                 use_split_merge: bool = False, keys=None, stacked_maps=None):
+                 use_split_merge: bool = False, keys=None, stacked_maps=None, restarts: int = 1):
         """``keys`` = (seeds, chain ids), one per tile: the Philox key and chain id each tile's chain uses instead of the
         launch's seed and ``chain0 + tile`` -- tiles of several images in one launch keep the chains they would run in a
-        launch of their own image (``mpp_set_chain_keys``)."""
+        launch of their own image (``mpp_set_chain_keys``).
+
+        ``restarts`` R > 1: R independent chains per tile (the context's ``replicas``), all from the tile's initial
+        configuration; replica r of a tile draws from the chain id ``replica_chain_ids`` gives it (replica 0: the tile's
+        own), and ``run`` hands back, per tile, the replica whose returned state has the lowest total energy
+        (``select_replicas``; kept in ``replica_energy`` [R, n_tiles] and ``replica_winner`` [n_tiles]).  With ``keys`` of
+        several images a third entry gives, per tile, the tile count of its image (the images' tiles in order): replica
+        ids are per image."""
         self.use_split_merge = use_split_merge
+        self.restarts = int(restarts)
+        if self.restarts < 1:
+            raise ValueError(f"restarts must be >= 1, got {restarts}")
+        self.replica_energy = self.replica_winner = None
         shapes = {tuple(t.shape[:2]) for t in tiles}
         if len(shapes) != 1:
             raise ValueError(f"all tiles of a batch must have the same shape, got {shapes}")
@@ -100,7 +142,13 @@ class TileBatchSampler:
         self.model_units = unit
         self.model = E.build_model_desc(unit, pair, energy_combinator)
         auto_spec = spec_waves is None
-        self.ctx = ctx or MppContext(device, point_capacity=point_capacity, spec_waves=8 if auto_spec else spec_waves)
+        if self.restarts > 1:
+            if ctx is not None and ctx.get_option("replicas") != self.restarts:
+                raise ValueError(f"restarts={self.restarts}: the given context holds {ctx.get_option('replicas')} replica(s)")
+            self.ctx = ctx or MppContext(device, point_capacity=point_capacity, spec_waves=8 if auto_spec else spec_waves,
+                                         replicas=self.restarts)
+        else:
+            self.ctx = ctx or MppContext(device, point_capacity=point_capacity, spec_waves=8 if auto_spec else spec_waves)
         det0 = tiles[0].detection_map
         if stacked_maps is not None:                  # (det [T,p,p], marks 3 x [T,p,p,32]) already stacked on the GPU
             det, marks = stacked_maps
@@ -120,11 +168,34 @@ class TileBatchSampler:
             if spec_waves not in (1, 8):
                 auto_spec = False
                 self.ctx.set_option("spec_waves", 8)
-        if keys is not None:
+        self._replica_keys = None                     # restarts > 1 with ``keys``: (seeds, chain ids) of all chains
+        if keys is not None and self.restarts > 1:
+            self._replica_keys = self._keys_of_replicas(keys)
+        elif keys is not None:
             self.ctx.set_chain_keys(keys[0], keys[1])
         self.ctx.set_model(self.model, self.mappings)
         if auto_spec and ctx is None:
-            self.ctx.set_option("spec_waves", choose_spec_waves(self.ctx, len(self.tiles), use_split_merge))
+            self.ctx.set_option("spec_waves", choose_spec_waves(self.ctx, len(self.tiles) * self.restarts, use_split_merge))
+
+    def _keys_of_replicas(self, keys):
+        """(seeds, chain ids) of every chain from the per-tile ``keys`` = (seeds, chain ids, tiles of the tile's image)"""
+        n, R = len(self.tiles), self.restarts
+        if len(keys) < 3:
+            raise ValueError("restarts > 1 with keys: a third entry gives each tile's image's tile count")
+        seeds = np.asarray(keys[0], dtype=np.uint64).reshape(-1)
+        chains = np.asarray(keys[1], dtype=np.int64).reshape(-1)
+        per_image = np.asarray(keys[2], dtype=np.int64).reshape(-1)
+        if not (len(seeds) == len(chains) == len(per_image) == n):
+            raise ValueError("keys: one seed, one chain id and one tile count per tile")
+        out = np.zeros((R, n), np.uint32)
+        i = 0
+        while i < n:                                   # image after image: its tiles are consecutive, ids chain0 + 0..m-1
+            m = int(per_image[i])
+            if m < 1 or i + m > n or np.any(chains[i:i + m] != chains[i] + np.arange(m)) or np.any(per_image[i:i + m] != m):
+                raise ValueError("keys: the tiles of an image must be consecutive with consecutive chain ids")
+            out[:, i:i + m] = replica_chain_ids(m, R, int(chains[i])).reshape(R, m)
+            i += m
+        return np.tile(seeds, R), out.reshape(-1)
 
     def init(self, init_config: Union[str, None, Sequence[Sequence[Rectangle]]]):
         n = len(self.tiles)
@@ -142,17 +213,30 @@ class TileBatchSampler:
             for i, cfg in enumerate(configs):
                 xy = np.array([[p.x, p.y] for p in cfg], dtype=np.int32).reshape(-1, 2)
                 mk = np.array([[p.size, p.ratio, p.angle] for p in cfg], dtype=np.float64).reshape(-1, 3)
-                self.ctx.set_points(i, xy, mk)
+                for r in range(self.restarts):               # every replica starts where its tile starts
+                    self.ctx.set_points(r * n + i, xy, mk)
         counts = self.ctx.counts()[:n].astype(np.float64)
         self.intensity = np.maximum(1.0, counts)             # reference sample_rjmcmc.py:68
-        self.ctx.set_kernels(make_kernels(self.mappings, 1.0, use_split_merge=self.use_split_merge), intensity=self.intensity)
+        self.ctx.set_kernels(make_kernels(self.mappings, 1.0, use_split_merge=self.use_split_merge),
+                             intensity=self.intensity if self.restarts == 1 else np.tile(self.intensity, self.restarts))
 
     def run(self, total_steps: int, snapshot_steps: Sequence[int], num_samples: int, T0: float, alpha: float,
             T_target: float, seed: int, chain0: int = 0, on_device=None, as_arrays: bool = False):
         """-> per tile, the list of the last ``num_samples`` sampled configurations.
         ``on_device``: a callable ``f(ctx)`` that takes each sampled state where it lies (e.g.
         ``ctx.pack_detections`` into an all-gather buffer) instead of copying it to host rectangles.
-        ``as_arrays``: configurations as (xy [n, 2] int32, marks [n, 3] float64) instead of lists of ``Rectangle``."""
+        ``as_arrays``: configurations as (xy [n, 2] int32, marks [n, 3] float64) instead of lists of ``Rectangle``.
+        With ``restarts`` > 1 each tile's configuration is that of its winning replica, chosen on the returned state."""
+        n, R = len(self.tiles), self.restarts
+        if R > 1:
+            if num_samples > 1:
+                raise ValueError("restarts > 1 with num_samples > 1: a winner is defined for one returned state")
+            if on_device is not None:
+                raise ValueError("restarts > 1: the winners are chosen on the host, on_device is not supported")
+            if self._replica_keys is not None:
+                self.ctx.set_chain_keys(*self._replica_keys)
+            else:
+                self.ctx.set_chain_keys(np.full(R * n, int(seed), np.uint64), replica_chain_ids(n, R, chain0))
         self.ctx.set_schedule(T0, alpha, T_target)
         wanted = list(snapshot_steps)[-num_samples:] if snapshot_steps else []
         samples = [[] for _ in self.tiles]
@@ -161,7 +245,12 @@ class TileBatchSampler:
             if on_device is not None:
                 on_device(self.ctx)
                 return
-            for i, pts in enumerate(self.ctx.get_points_all()[:len(self.tiles)]):
+            chains = self.ctx.get_points_all()
+            if R > 1:
+                self.replica_energy = self.ctx.total_energy_all().reshape(R, n)
+                self.replica_winner = select_replicas(self.replica_energy, n)
+                chains = [chains[int(r) * n + i] for i, r in enumerate(self.replica_winner)]
+            for i, pts in enumerate(chains[:n]):
                 samples[i].append(pts if as_arrays else _to_rectangles(*pts))
 
         done = 0
@@ -187,12 +276,15 @@ def sample_rjmcmc_batch(tiles: Sequence[ImageWMaps], rng: np.random.Generator, n
                         init_config, init_temperature: float, alpha_t, burn_in: int, energy_setup,
                         samples_interval: int, target_temperature: float, verbose: int = 0, iter_multiplier=None,
                         use_split_merge: bool = False, device: int = 0, spec_waves: int = 8,
-                        point_capacity: int = 1024, chain0: int = 0):
-    """``sample_rjmcmc`` for many equally-shaped tiles at once; returns one result list per tile."""
+                        point_capacity: int = 1024, chain0: int = 0, restarts: int = 1):
+    """``sample_rjmcmc`` for many equally-shaped tiles at once; returns one result list per tile.
+    ``restarts`` R > 1: R chains per tile, the configuration of the one with the lowest energy is returned."""
+    if restarts > 1 and num_samples > 1:
+        raise ValueError("restarts > 1 with num_samples > 1: a winner is defined for one returned state")
     alpha, T_target, total, snaps = resolve_schedule(num_samples, init_temperature, alpha_t, burn_in, samples_interval,
                                                       target_temperature, iter_multiplier)
     sampler = TileBatchSampler(tiles, energy_setup, energy_combinator, device=device, spec_waves=spec_waves,
-                               point_capacity=point_capacity, use_split_merge=use_split_merge)
+                               point_capacity=point_capacity, use_split_merge=use_split_merge, restarts=restarts)
     sampler.init(init_config)
     seed = int(rng.integers(0, 2 ** 63 - 1))
     start = time.perf_counter()
@@ -209,7 +301,8 @@ def sample_rjmcmc(image_data: ImageWMaps, rng: np.random.Generator, num_samples:
                   target_temperature: float, verbose: int = 0, iter_multiplier: float = None,
                   use_split_merge: bool = False, **gpu_options):
     """Drop-in for the reference's ``sample_rjmcmc`` (one tile).  Returns ``[points]`` for
-    ``num_samples == 1`` and the last ``num_samples`` sampled configurations otherwise."""
+    ``num_samples == 1`` and the last ``num_samples`` sampled configurations otherwise.  ``restarts=R`` (among the
+    ``gpu_options``): the lowest-energy result of R independent chains."""
     return sample_rjmcmc_batch([image_data], rng, num_samples, energy_combinator, init_config, init_temperature,
                                alpha_t, burn_in, energy_setup, samples_interval, target_temperature, verbose,
                                iter_multiplier, use_split_merge, **gpu_options)[0]
