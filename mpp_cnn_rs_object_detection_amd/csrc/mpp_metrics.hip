@@ -44,7 +44,9 @@ __global__ __launch_bounds__(256) void k_quad_iou(int n, const double *__restric
   if (!(iw * ih > 0.0)) { out[idx] = -1.0; return; }
   double ax[4], ay[4], bx[4], by[4];
   const double A = load_ccw(qa, ax, ay), B = load_ccw(qb, bx, by);
-  const double inter = clip_area(ax, ay, bx, by);
+  // a quad without area has no intersection area (polyiou's fan sums to 0); as a clipper its edges have no side and would
+  // keep the whole subject
+  const double inter = (A > 0.0 && B > 0.0) ? clip_area(ax, ay, bx, by) : 0.0;
   const double uni = A + B - inter;
   out[idx] = uni == 0.0 ? (inter + 1.0) / (uni + 1.0) : inter / uni;
 }

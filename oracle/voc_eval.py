@@ -13,7 +13,13 @@ from __future__ import annotations
 
 import numpy as np
 
-EPS = 1e-8
+# polyiou.cpp decides every sign through sig(d) with an ABSOLUTE eps of 1e-8 on cross products.  At pixel coordinates that
+# snaps a crossing up to ~1e-9 px wide onto the line: against exact rational geometry (tests/overlap_ref.py) 14 of 490
+# touching poses displaced by 1e-9 px were off by up to 2.3e-8 px^2, 62 x the rounding bound of the arithmetic.  This oracle
+# is the yardstick of the device's k_quad_iou, which has no snap, so it decides on the sign of the double itself: with 0
+# the fan agrees with exact geometry to rounding on every family (tests/test_overlap_ref_host.py).  An IoU differs from the
+# devkit's by at most ~1e-8 through this.
+EPS = 0.0
 
 
 # ---- polyiou.cpp -----------------------------------------------------------------------------------------
