@@ -521,6 +521,22 @@ int mpp_rescale(mpp_ctx *ctx, const uint8_t *src, int H, int W, int64_t src_pitc
                 const double *row_w, int oh, int row_taps, const int32_t *col_idx, const double *col_w, int ow, int col_taps,
                 uint8_t *out, double *out_f64, int64_t workspace_limit);
 
+/* ---- the result pictures of infer (csrc/mpp_figures.hip) ---------------------------------------------------------------------
+ * What models/shape_net/display.py:37-59 draws with OpenCV -- rectangle outlines over the picture -- as RGB8 [H][W][3]
+ * (device, contiguous), composed where the picture and the score maps already are.  DESIGN.md section 11 has the rules:
+ *   base     rgb: float32 [H][W][3] in 0..1 (device), or scalar: float32 [H][W] (device) clipped to [vmin, vmax] and looked
+ *            up in lut, float32 [256][3] (host), at min(255, (int)((v - vmin) / (vmax - vmin) * 256)) in float64; exactly
+ *            one of rgb and scalar is given;
+ *   outline  corners: int32 [n][4][2] (host), (row, col) per corner, |coordinate| <= 2^20; edge k of a rectangle is the integer
+ *            8-connected Bresenham walk from corner k to corner (k + 1) % 4; pixels outside the image are skipped;
+ *   order    a pixel on several outlines takes the colour of the rectangle with the highest index, as drawing them one
+ *            after another does; colors: float32 [n][3] (host);
+ *   8 bits   (uint8)(v * 255) in float32, truncated, as matplotlib's imsave; a pixel with a NaN channel is (0, 0, 0).
+ * n = 0 gives the base picture.  Runs on the ctx's stream and returns when the picture is complete: the host tables are the
+ * caller's again. */
+int mpp_draw_outlines(mpp_ctx *ctx, int H, int W, const float *rgb, const float *scalar, double vmin, double vmax,
+                      const float *lut, int n, const int32_t *corners, const float *colors, uint8_t *out);
+
 void mpp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 int mpp_abi_version(void);
 

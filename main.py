@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Command-line entry, same flags as the reference's ``main.py:11-109``:
 
-    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o]
+    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures]
+    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
 hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the CNN-only baseline's detections (DOTA hbb /
@@ -12,6 +13,11 @@ that includes histogram matching, the whole ``strong`` augmentation recipe (shad
 HIP kernels too) and, for PosNet, the error-density resampling of ``data_loader.error_update_interval``,
 whose maps land in ``<dataset base>/error_maps/<dataset>/train/<model_name>/``).  With ``torchrun --nproc-per-node N`` the images of the dataset are
 dealt to N GPUs (one gather of the results at the end; RCCL).
+
+``-p detect`` runs the detector (U-Nets + sampler) on any image files, no dataset or annotation needed, and writes
+``<stem>_detections.csv`` / ``<stem>_results.pkl`` (and, with ``--figures``, ``<stem>_detection.png``) in the pixels of each
+file (``detect.py``).  ``--figures`` with ``-p infer`` writes the reference's two pictures per image; ``-p data_preview -m mpp``
+the annotation over each ``val`` image.
 
 ``-p translate_dota -c <config>`` / ``-p translate_cowc -c <config>`` (no ``-m``) turn a raw DOTA or COWC download into the
 dataset layout all of the above read (``dataset_translation``; the rescale to the target GSD is a HIP kernel; example configs
@@ -52,6 +58,17 @@ def build_parser():
     parser.add_argument("--restarts", type=_restarts, default=None,
                         help="(-m mpp, infer / infereval) independent chains per tile, the lowest-energy one is kept; "
                              "overrides inference.restarts of the config (default 1)")
+    parser.add_argument("--figures", action="store_true",
+                        help="(-m mpp, infer / infereval / detect) write the result pictures composed on the GPU: NNNN_detection.png, "
+                             "NNNN_gt.png (and NNNN_detection_map.png) beside NNNN_results.pkl; same as inference.figures in the config")
+    parser.add_argument("--images", nargs="+", default=None, metavar="PATH",
+                        help="(-p detect) image files, or directories whose image files are taken in sorted order")
+    parser.add_argument("--out", default=None, metavar="DIR", help="(-p detect) where the results go")
+    parser.add_argument("--gsd", type=float, default=None,
+                        help="(-p detect) ground sampling distance of the images in metres per pixel; finer than --model-gsd: the "
+                             "images are reduced to it first (default: --model-gsd, no rescale)")
+    parser.add_argument("--model-gsd", type=float, default=0.5, help="(-p detect) ground sampling distance the nets were trained at")
+    parser.add_argument("--min-score", type=float, default=None, help="(-p detect) drop detections scored below this from the CSV")
     return parser
 
 
@@ -76,15 +93,35 @@ def main():
         print("done !")
         return
 
+    if args.procedure == "detect":
+        if args.model != "mpp":
+            raise ValueError("-p detect runs the MPP detector: -m mpp")
+        if not args.images or not args.out:
+            raise ValueError("-p detect needs --images PATH [PATH ...] and --out DIR")
+        from mpp_cnn_rs_object_detection_amd import detect
+        from mpp_cnn_rs_object_detection_amd.mpp_model import MPPModel
+        detect.resolve_scale(args.gsd, args.model_gsd)          # (a coarser picture is refused before anything is loaded)
+        if args.restarts is not None:
+            config.setdefault("inference", {})["restarts"] = args.restarts
+        model = MPPModel(config, phase="val", load=True, device=local_rank,
+                         nets=load_nets(config, local_rank, args.unet_max_pixels), spec_waves=args.spec_waves)
+        detect.detect_files(model, args.images, args.out, gsd=args.gsd, model_gsd=args.model_gsd, min_score=args.min_score,
+                            figures=args.figures)
+        print("done !")
+        return
+
     if args.model == "mpp":
         from mpp_cnn_rs_object_detection_amd.mpp_model import MPPModel
         if args.restarts is not None and args.procedure in ("infer", "infereval"):
             config.setdefault("inference", {})["restarts"] = args.restarts
+        if args.figures:
+            config.setdefault("inference", {})["figures"] = True
         nets = None
         if args.unet:
             nets = load_nets(config, local_rank, args.unet_max_pixels)
+        # (data_preview only looks at the dataset: the stored model is loaded so that nothing is calibrated or trained for it)
         model = MPPModel(config, phase="train" if args.procedure == "train" else "val",
-                         load=args.procedure not in ["train", "data_preview"], dataset=args.dataset, device=local_rank,
+                         load=args.procedure != "train", dataset=args.dataset, device=local_rank,
                          nets=nets, spec_waves=args.spec_waves)
     elif args.model in ("posnet", "shapenet"):
         model = ScoreMapWriter(config, args.model, args.dataset, local_rank, args.unet_max_pixels)
@@ -101,6 +138,9 @@ def main():
         model.eval()
     elif args.procedure == "train":
         model.train()
+    elif args.procedure == "data_preview":
+        print("previewing data")
+        model.data_preview()
     else:
         raise ValueError(args.procedure)
     print("done !")

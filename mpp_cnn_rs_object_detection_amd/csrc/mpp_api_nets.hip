@@ -1,5 +1,6 @@
 // mpp_api_nets.hip -- the C ABI around the U-Nets, thin wrappers that check their arguments: inference (mpp_maps.hip,
-// mpp_conv.hip), detection (mpp_detect.hip), training (mpp_train.hip, mpp_resample.hip), rescale (mpp_rescale.hip).
+// mpp_conv.hip), detection (mpp_detect.hip), training (mpp_train.hip, mpp_resample.hip), rescale (mpp_rescale.hip), and the
+// result pictures (mpp_figures.hip).
 #include "mpp_ctx.hpp"
 
 extern "C" int mpp_affine_relu(mpp_ctx *c, void *x, int planes, int C, int64_t hw, int elem_bytes, const float *scale,
@@ -112,6 +113,34 @@ extern "C" int mpp_rescale(mpp_ctx *c, const uint8_t *src, int H, int W, int64_t
   HIPCHK(c, hipSetDevice(c->device));
   return mpp_rescale_run(c->stream, &c->rescale, src, H, W, src_pitch, row_idx, row_w, oh, row_taps, col_idx, col_w, ow, col_taps,
                          out, out_f64, workspace_limit, &c->err);
+}
+// ---- the result pictures (mpp_figures.hip): the small tables are the caller's host arrays, uploaded here; the call returns
+// when the picture is complete, so they are free again ----------------------------------------------------------------------
+extern "C" int mpp_draw_outlines(mpp_ctx *c, int H, int W, const float *rgb, const float *scalar, double vmin, double vmax,
+                                 const float *lut, int n, const int32_t *corners, const float *colors, uint8_t *out) {
+  if (!c || !out || H <= 0 || W <= 0 || H > 65536 || W > 65536 || n < 0 || n > (1 << 24) || (n > 0 && (!corners || !colors)))
+    return fail(c, -1, "bad draw_outlines arguments");
+  if ((rgb != nullptr) == (scalar != nullptr)) return fail(c, -1, "draw_outlines: give the RGB picture or the scalar map, not both");
+  if (scalar && (!lut || !(vmax > vmin) || !(vmax - vmin < INFINITY)))
+    return fail(c, -1, "draw_outlines: a scalar base needs a 256 x 3 table and finite vmin < vmax");
+  for (size_t i = 0; i < (size_t)n * 8; ++i)
+    if (corners[i] < -MPP_FIG_COORD_MAX || corners[i] > MPP_FIG_COORD_MAX)
+      return fail(c, -1, "draw_outlines: corner %d of rectangle %d lies beyond +-%d", (int)(i / 2 % 4), (int)(i / 8), MPP_FIG_COORD_MAX);
+  HIPCHK(c, hipSetDevice(c->device));
+  // workspace: colours [n][3] float32, table [256][3] float32, corners [n][8] int32, then the owner image (16-byte aligned)
+  const size_t col_b = (size_t)n * 3 * sizeof(float), lut_b = scalar ? 256 * 3 * sizeof(float) : 0, cor_b = (size_t)n * 8 * sizeof(int32_t);
+  const size_t own_off = (col_b + lut_b + cor_b + 15) & ~(size_t)15;
+  HIPCHK(c, c->figures.reserve(c->stream, own_off + (n > 0 ? (size_t)H * W * sizeof(int32_t) : 0)));
+  unsigned char *ws = c->figures;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(ws, colors, col_b, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ws + col_b + lut_b, corners, cor_b, hipMemcpyHostToDevice, c->stream));
+  }
+  if (scalar) HIPCHK(c, hipMemcpyAsync(ws + col_b, lut, lut_b, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, mpp_launch_draw_outlines(c->stream, H, W, rgb, scalar, vmin, vmax, (const float *)(ws + col_b), n,
+                                     (const int32_t *)(ws + col_b + lut_b), (const float *)ws, (int32_t *)(ws + own_off), out));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
 }
 // ---- histogram matching and error-density resampling (mpp_train.hip, mpp_resample.hip) ----------------------------------
 static bool no_dataset(const mpp_train_data *data) {

@@ -116,6 +116,7 @@ struct mpp_ctx : TileMem {
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
   RescaleWs rescale;                 // workspace of mpp_rescale (mpp_rescale.hip)
+  DevWs figures;                     // workspace of mpp_draw_outlines (mpp_figures.hip): the tables, then the owner image
 };
 
 static int fail(mpp_ctx *c, int code, const char *fmt, ...) {

@@ -84,4 +84,9 @@ int mpp_launch_shapenet_epilogue_nhwc(hipStream_t st, const void *logits, int el
                                       int ww, float *dst, int ld_dst);
 int mpp_launch_shapenet_heads(hipStream_t st, const float *h, int ldw, const float *wh, const float *bh, int wx0, int wy0,
                               int wh_, int ww, float *m0, float *m1, float *m2, int ld_dst);
+// the result pictures (mpp_figures.hip): every pointer device; owner [H][W] int32, used (and zeroed) only when n > 0
+#define MPP_FIG_COORD_MAX (1 << 20)                // corner coordinates lie within +- this: the walk's arithmetic stays in int32
+hipError_t mpp_launch_draw_outlines(hipStream_t st, int H, int W, const float *rgb, const float *scalar, double vmin, double vmax,
+                                    const float *lut, int n, const int32_t *corners, const float *colors, int32_t *owner,
+                                    uint8_t *out);
 }

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
     "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
     "mpp_image_histograms", "mpp_train_set_histograms", "mpp_posnet_error_map", "mpp_density_prefix", "mpp_density_anchors",
-    "mpp_train_aug_params", "mpp_rescale", "mpp_abi_version",
+    "mpp_train_aug_params", "mpp_rescale", "mpp_draw_outlines", "mpp_abi_version",
 ]
 
 
@@ -192,6 +192,7 @@ def load_library(path: Optional[str] = None):
         "mpp_density_prefix": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp]),
         "mpp_density_anchors": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, C.c_uint32, vp]),
         "mpp_rescale": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i64]),
+        "mpp_draw_outlines": (i32, [vp, i32, i32, vp, vp, dbl, dbl, vp, i32, vp, vp, vp]),
         "mpp_abi_version": (i32, []),
     }
     for name, (res, args) in protos.items():
@@ -821,6 +822,36 @@ class MppContext:
                                         None if out_f64 is None else self._dev("out_f64", out_f64, torch.float64, (oh, ow, 3)),
                                         int(workspace_limit)))
         return out if out_f64 is None else (out, out_f64)
+
+    # -- the result pictures (synchronous: the picture is complete on return) ------------------------------------------
+    def draw_outlines(self, base, corners=None, colors=None, lut=None, vmin: float = 0.0, vmax: float = 1.0, out=None):
+        """``mpp_draw_outlines``: base a contiguous float32 CUDA tensor, [H,W,3] (the picture, 0..1) or [H,W] (a scalar map:
+        clipped to [vmin, vmax] and looked up in ``lut`` [256,3] float32, numpy); corners [n,4,2] int32 (row, col) and colors
+        [n,3] float32, numpy (None or empty: the base picture alone).  Returns out, [H,W,3] uint8 CUDA tensor (made if None)."""
+        import torch
+        if not (_is_torch(base) and base.is_cuda and base.device.index == self.device and base.dtype == torch.float32
+                and base.is_contiguous() and (base.dim() == 2 or (base.dim() == 3 and base.shape[2] == 3))):
+            raise ValueError(f"draw_outlines: base must be a contiguous float32 [H,W,3] or [H,W] tensor on GPU {self.device}")
+        H, W = int(base.shape[0]), int(base.shape[1])
+        scalar = base.dim() == 2
+        if scalar:
+            if lut is None:
+                raise ValueError("draw_outlines: a scalar base needs a lut")
+            lut = np.ascontiguousarray(lut, dtype=np.float32)
+            if lut.shape != (256, 3):
+                raise ValueError("draw_outlines: lut must be [256,3]")
+        corners = np.zeros((0, 4, 2), np.int32) if corners is None else np.ascontiguousarray(corners, dtype=np.int32)
+        colors = np.zeros((0, 3), np.float32) if colors is None else np.ascontiguousarray(colors, dtype=np.float32)
+        n = int(corners.shape[0])
+        if corners.shape != (n, 4, 2) or colors.shape != (n, 3):
+            raise ValueError("draw_outlines: corners must be [n,4,2] and colors [n,3]")
+        if out is None:
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=base.device)
+        self._check(self._L.mpp_draw_outlines(self._h, H, W, None if scalar else _ptr(base), _ptr(base) if scalar else None,
+                                              float(vmin), float(vmax), _ptr(lut) if scalar else None, n,
+                                              _ptr(corners) if n else None, _ptr(colors) if n else None,
+                                              self._dev("out", out, torch.uint8, (H, W, 3))))
+        return out
 
     # -- evaluation --------------------------------------------------------------------------------
     def quad_iou(self, a, b) -> np.ndarray:

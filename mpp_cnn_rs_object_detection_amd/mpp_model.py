@@ -631,9 +631,35 @@ class MPPModel:
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
                 "det_poly": det_poly}
 
+    def _figure_ctx(self):
+        """the context the pictures are composed on (``figures``) and ``detect`` rescales on: made on first use, it holds no tiles"""
+        if getattr(self, "_fig_ctx", None) is None:
+            import torch
+            from .hip_api import MppContext
+            self._fig_ctx = MppContext(self.device)
+            # (its launches follow torch's work on the pictures and maps it is handed)
+            self._fig_ctx.set_stream(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        return self._fig_ctx
+
+    def _write_figures(self, patch_id: int, results_dir: str, image_data: ImageWMaps, region_data, merged, scores):
+        """``NNNN_detection.png`` and ``NNNN_gt.png`` of one image (mpp_model.py:306-323), and ``NNNN_detection_map.png`` when
+        the detection map of the whole image is on the device"""
+        from . import figures as F
+        import torch
+        ctx = self._figure_ctx()
+        image = torch.from_numpy(np.ascontiguousarray(image_data.image[:, :, :3], dtype=np.float32)).to(torch.device("cuda", self.device))
+        F.save_png(os.path.join(results_dir, f"{patch_id:04}_detection.png"), F.detection_picture(image, merged, scores, ctx))
+        F.save_png(os.path.join(results_dir, f"{patch_id:04}_gt.png"), F.gt_picture(image, image_data.labels, ctx))
+        det = getattr(region_data, "detection_map", None)
+        if hasattr(det, "data_ptr") and det.is_cuda and tuple(det.shape) == tuple(int(v) for v in image_data.shape[:2]):
+            F.save_png(os.path.join(results_dir, f"{patch_id:04}_detection_map.png"), F.map_picture(det, ctx))
+
     def infer(self, subset: str, min_confidence: float = 0.1, display_min_confidence: float = 0.5,
-              overwrite: bool = True):
-        """Reference ``mpp_model.py:202-370`` (figures are not drawn).
+              overwrite: bool = True, figures: Optional[bool] = None):
+        """Reference ``mpp_model.py:202-370``.  ``figures`` (default: ``inference.figures`` of the config, off): the two
+        pictures the reference writes per image, ``NNNN_detection.png`` and ``NNNN_gt.png``, beside ``NNNN_results.pkl``, by the
+        rank that writes the pickle (``_write_figures``; without the score text).  Off, nothing of
+        it runs.
 
         Several ranks (one per GPU): the DATASET is sharded by image -- the reference's own loop is serial over images
         (``mpp_model.py:220``) with a process pool inside each; here rank r takes the r-th block of the images and runs them
@@ -642,6 +668,8 @@ class MPPModel:
         every image is sampled with the seed -- and gives the files -- of a one-rank run.  Only an image with more tiles than
         one GPU runs chains at a time (``TILE_SHARD_MIN``) is sampled by all ranks together."""
         rank, world = mdist.init_process_group()
+        if figures is None:
+            figures = bool(self.config["inference"].get("figures", False))
         dataset = self.config["dataset"]["dataset"]
         results_dir = get_inference_path(os.path.split(self.save_path)[1], dataset, subset)
         os.makedirs(results_dir, exist_ok=True)
@@ -674,6 +702,8 @@ class MPPModel:
             merged, scores = self.infer_image(image_data, rank, world, region_data=region_data, seed=seeds[k])
             if rank == 0:
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores))
+                if figures:
+                    self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
 
         # ---- this rank's images: the tiles of consecutive images share a launch (``infer_images``)
         def inferred():
@@ -684,8 +714,8 @@ class MPPModel:
 
             def flush():
                 res = self.infer_images([b[1] for b in batch], [b[2] for b in batch], image_seeds=[seeds[b[0]] for b in batch])
-                for (k, image_data, _), (merged, scores) in zip(batch, res):
-                    yield k, image_data, merged, scores
+                for (k, image_data, region_data), (merged, scores) in zip(batch, res):
+                    yield k, image_data, region_data, merged, scores
 
             for k, (image_data, region_data) in stream:
                 patch, anchors = self.tile_layout(tuple(int(v) for v in image_data.shape[:2]))
@@ -698,8 +728,10 @@ class MPPModel:
                 yield from flush()
 
         try:
-            for k, image_data, merged, scores in inferred():
+            for k, image_data, region_data, merged, scores in inferred():
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores))
+                if figures:
+                    self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all
             if world == 1:
                 raise
@@ -745,4 +777,16 @@ class MPPModel:
         return out
 
     def data_preview(self):
-        raise NotImplementedError("figures are outside this build")
+        """``mpp_model.py:389-399``: ``preview_<name>_gt.png`` per ``val`` image under ``<model>/data_preview``, the annotation
+        drawn through ``figures.gt_picture`` (the reference shows eight training patches through matplotlib's axes)"""
+        from matplotlib import pyplot as plt
+        from . import figures as F
+        out_dir = os.path.join(self.save_path, "data_preview")
+        os.makedirs(out_dir, exist_ok=True)
+        ctx = self._figure_ctx()
+        paths = fetch_data_paths(self.dataset, "val")
+        for pf, af in zip(paths["images"], paths["annotations"]):
+            name = re.match(r"([0-9]+).*.png", os.path.split(pf)[1]).group(1)
+            with open(af, "rb") as f:
+                labels = pickle.load(f)
+            F.save_png(os.path.join(out_dir, f"preview_{name}_gt.png"), F.gt_picture(plt.imread(pf)[:, :, :3], labels, ctx))
