@@ -22,12 +22,16 @@
   c.P = P; c.t = tiles[tile];
   load_model_regs(c);
   load_hot(c);
+#if MPP_STATE_HBM
   const int ncell = P->nx * P->ny, cap = P->cap;
   const int rowbase_n = P->rowbase_lds ? P->H + 1 : 0;
-#if MPP_STATE_HBM
   c.L = carve_hbm(lds_raw, ws + (size_t)blockIdx.x * ws_stride, cap, ncell, P->cell_cap, SPEC, rowbase_n, WAVES);
 #else
-  c.L = carve(lds_raw, cap, ncell, P->cell_cap, SPEC, rowbase_n, WAVES);
+  // the sizes behind every LDS address, from the kernel arguments and not from the staged copy of the block: a read of LDS
+  // lands in vector registers, and every array base derived from it would hold one for the whole launch
+  const int ncell = Pv.nx * Pv.ny, cap = Pv.cap;
+  const int rowbase_n = Pv.rowbase_lds ? Pv.H + 1 : 0;
+  c.L = carve(lds_raw, cap, ncell, Pv.cell_cap, SPEC, rowbase_n, WAVES);
 #endif
   c.lane = threadIdx.x & (WAVE - 1);
   c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);   // wave-uniform: lets Philox etc. run on the scalar unit

@@ -61,7 +61,8 @@ struct DeepLds {
                                // reductions the step changes
   double *st;                  // [nmax][5] ... and their new reductions (2 x 2 values, then the two slots as bits): a step that
                                // commits writes them; only a step that changes more than two neighbours needs a second pass
-  uint4 *pw;                   // [nmax] Philox block 0 of the steps, in sorted order
+  uint4 *pw;                   // [nmax] Philox block 0 of the steps, in sorted order (queue rounds: lin_a and gate_a of the
+                               // step at that offset, see deep_park)
   unsigned short *poff;        // [nmax] sorted position -> offset of the step in the round
   unsigned short *tcnt;        // [WAVES][16] steps of each kernel type per wave
   double *tring;               // [4 * nmax] temperature of step (offset & mask), filled two rounds ahead
@@ -673,6 +674,31 @@ __device__ __forceinline__ void deep_load_birth(const PreTab &pt, unsigned int o
   r.dE = 0.0; r.n_stash = 0; r.ra0 = r.ra1 = 0.0;
 }
 
+// (QUE) The fields of a step that the neighbour pass does not read wait in LDS while it runs, in space of the step's own
+// offset that nothing else uses at that time: u_acc and qf in its report D.info[off], qb in D.nb[off] (both are written only
+// after deep_post, and every wave has finished reading the previous round's reports before barrier (1)); lin_a and gate_a
+// in D.pw[off] (the queue rounds sort nothing: no Philox words), where they stay until deep_mutate writes the slot.
+__device__ __forceinline__ uint4 pack_dd(double a, double b) {
+  const unsigned long long x = (unsigned long long)__double_as_longlong(a), y = (unsigned long long)__double_as_longlong(b);
+  return make_uint4((unsigned)x, (unsigned)(x >> 32), (unsigned)y, (unsigned)(y >> 32));
+}
+__device__ __forceinline__ double unpack_d(unsigned lo, unsigned hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); }
+__device__ __forceinline__ void deep_park(const DeepLds &D, int off, const Rec &r) {
+  D.info[off] = pack_dd(r.u_acc, r.qf);
+  D.nb[off] = pack_dd(r.qb, 0.0);
+  const uint4 l = pack_dd(r.lin_a, 0.0);
+  D.pw[off] = make_uint4(l.x, l.y, (unsigned)r.gate_a, 0u);
+}
+__device__ __forceinline__ void deep_unpark_green(const DeepLds &D, int off, Rec &r) {
+  const uint4 a = D.info[off];
+  const uint2 b = *(const uint2 *)(D.nb + off);
+  r.u_acc = unpack_d(a.x, a.y); r.qf = unpack_d(a.z, a.w); r.qb = unpack_d(b.x, b.y);
+}
+__device__ __forceinline__ void deep_unpark_unit(const DeepLds &D, int off, Rec &r) {
+  const uint4 l = D.pw[off];
+  r.lin_a = unpack_d(l.x, l.y); r.gate_a = (int)l.z;
+}
+
 // (QUE) the queues a wave serves: queue a, and for wave 1 queue b (wave 1: the uniform birth, a, and the uniform death, b;
 // waves 4 and 5: the even and the odd entries of the data-driven translation's queue); ca / cb the position of the first
 // entry not committed yet, ea / eb the end of the queue -- positions in the chain's part (reg) of pt.qoff / pt.qent;
@@ -691,7 +717,8 @@ template <> struct DeepQueues<true> {
 // QUE: (with TAB, eight waves, the cost deal) every wave takes its steps from the pre-pass queues of its kernel types, in the
 //      same deal: no kernel type, no sort, no Philox block in the round (the round's window ends early where a wave would
 //      have more than 64 steps)
-template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false>
+// NCH: chunks of 64 step reports the commit decision keeps per lane (nmax <= 64 * NCH; the launcher picks it from nmax)
+template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false, int NCH = DEEP_NMAX_LIMIT / 64>
 __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevParams Pv, const TileRef *tiles, int tile0,
                                                                  const long long *until, long long trace_base,
                                                                  unsigned long long seed, unsigned int chain0, int trace_tile,
@@ -702,7 +729,6 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   static_assert(!QUE || (TAB && WAVES == 8), "the queues are dealt to eight waves");
   const bool by_type = (gain8 & 0x100) == 0;      // (bit 8 of the gain word: deal the sorted steps in blocks instead -- A/B tests)
   gain8 &= 0xff;
-  constexpr int NCH = DEEP_NMAX_LIMIT / 64;              // chunks of 64 step reports a lane may have to look at
   const DevParams *P = deep_stage_params<(WAVES >= MPP_LDS_PARAMS_MIN_WAVES)>(Pv, WAVE * WAVES);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = tile0 + blockIdx.x;
@@ -710,10 +736,12 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   c.P = P; c.t = tiles[tile];
   load_model_regs(c);
   load_hot(c);
-  const int ncell = P->nx * P->ny, cap = P->cap;
-  const int rowbase_n = P->rowbase_lds ? P->H + 1 : 0;
-  c.L = carve(lds_raw, cap, ncell, P->cell_cap, 0, rowbase_n, WAVES);
-  const DeepLds D = deep_carve(lds_raw + deep_base_bytes(cap, ncell, P->cell_cap, rowbase_n, WAVES), nmax, WAVES, EXT ? 1 : 0);
+  // the sizes behind every LDS address, from the kernel arguments and not from the staged copy of the block: a read of LDS
+  // lands in vector registers, and the thirty-odd array bases derived from it would each hold one for the whole launch
+  const int ncell = Pv.nx * Pv.ny, cap = Pv.cap;
+  const int rowbase_n = Pv.rowbase_lds ? Pv.H + 1 : 0;
+  c.L = carve(lds_raw, cap, ncell, Pv.cell_cap, 0, rowbase_n, WAVES);
+  const DeepLds D = deep_carve(lds_raw + deep_base_bytes(cap, ncell, Pv.cell_cap, rowbase_n, WAVES), nmax, WAVES, EXT ? 1 : 0);
   c.lane = threadIdx.x & (WAVE - 1);
   c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   const Lds &L = c.L;
@@ -804,7 +832,6 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   bool mine = false, my_commit = false;
   int myoff = 0, lim = 0, committed = 0, cur_n = n, nb0 = 0, nb1 = 0, nbr = 0, ring_todo = 0;
   long long ring_from = 0;
-  double Tm = 0.0;
   DeepQueues<QUE> qs;                           // (QUE) the wave's cursors into the queues
   if constexpr (QUE) {
     const int w = c.wave;
@@ -875,9 +902,12 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       if (!mine) myoff = 0;
       DPH(2);
       // ---- B: evaluate my step (the TAB path below, its head from the entry instead of Philox words)
+      // (every field anew, also in the lanes without a step: nothing of the last round's step stays live through the draw)
       r.valid = 0; r.kernel = 0; r.accepted = 0; r.has_rem = r.has_add = 0; r.tslot = -1; r.tidx = -1;
+      r.ax = r.ay = r.rx = r.ry = 0; r.pid = -1; r.ncls = -1; r.acls = 0; r.n_stash = 0; r._pad2 = 0; r.gate_a = 1;
+      r.as = r.ar = r.aa = r.aux0 = r.aux1 = r.u_acc = r.qf = r.qb = r.dE = 0.0;
+      r.hl = r.hw = r.ca = r.sa = r.rad = r.lin_a = r.ra0 = r.ra1 = 0.0;
       if (mine) {
-        Tm = D.tring[(int)((done + myoff) & (long long)rmask)];
         r.valid = 1;
         int keep = 0;
         const bool pre_b = kq == MPP_K_UBIRTH || kq == MPP_K_DBIRTH;      // a birth: the table has it all
@@ -890,6 +920,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
           deep_add_geo(c, r, keep);
           deep_pre<false>(c, r, keep, tracing, pmv, nullptr);
         }
+        deep_park(D, myoff, r);
       }
       do_eval = mine && r.valid && (r.has_rem || r.has_add);
       DPH(4);
@@ -995,10 +1026,12 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     }
     myoff = mine ? (int)D.poff[es] : 0;
     r.valid = 0; r.kernel = 0; r.accepted = 0; r.has_rem = r.has_add = 0; r.tslot = -1; r.tidx = -1;
+    r.ax = r.ay = r.rx = r.ry = 0; r.pid = -1; r.ncls = -1; r.acls = 0; r.n_stash = 0; r._pad2 = 0; r.gate_a = 1;      // (as in the queue rounds)
+    r.as = r.ar = r.aa = r.aux0 = r.aux1 = r.u_acc = r.qf = r.qb = r.dE = 0.0;
+    r.hl = r.hw = r.ca = r.sa = r.rad = r.lin_a = r.ra0 = r.ra1 = 0.0;
     int keep_x = 0;                                    // (EXT only: what deep_pre needs after the cooperative pass below)
     MapVals pmv_x{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
     if (mine) {
-      Tm = D.tring[(int)((done + myoff) & (long long)rmask)];
       r.valid = 1;
       int keep = 0;
       MapVals pmv{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
@@ -1063,6 +1096,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
                  r.ar, r.aa, r.hl, r.hw, r.ca, r.sa, r.rad, stage == 0, &sde, &ra0, &ra1, &ns, &nb0, &nb1, &nbr, &nresc, &su, sv, &nonf DPH_PASS);
       if (stage == 1 && do_eval) {
         double dE = sde;
+        if constexpr (QUE) deep_unpark_unit(D, myoff, r);
         if (ha) dE += finish_energy_c(c, r.lin_a + pair_part_c(c, r.gate_a, ra0, ra1));
         if (hr) dE -= finish_energy_c(c, L.lin[r.tslot] + pair_part_c(c, (int)L.gate[r.tslot], L.red0[r.tslot], L.red1[r.tslot]));
         if (EXT && nonf) dE = nan("");
@@ -1076,6 +1110,9 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     DPH(stage == 1 ? 5 : 9);
     if (stage == 1) {
     if (mine) {
+      // the step's temperature: its ring entry stays as it is while the step is in the window (the ring is filled two rounds ahead)
+      const double Tm = D.tring[(int)((done + myoff) & (long long)rmask)];
+      if constexpr (QUE) deep_unpark_green(D, myoff, r);
       if (r.valid) deep_post(c, r, n, Tm, tracing);
       // does the step change the configuration?  An accepted move that writes the values the slot already holds does not
       // (its cached geometry, unit energy and reductions are functions of those values: the same bits)
@@ -1256,7 +1293,8 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       const long long idx = tr0 + done + myoff;
       if (out) {
         mpp_step_out so;
-        so.dE = r.dE; so.fwd = r.fwd; so.bwd = r.bwd; so.log_alpha = r.log_alpha; so.T = Tm;
+        so.dE = r.dE; so.fwd = r.fwd; so.bwd = r.bwd; so.log_alpha = r.log_alpha;
+        so.T = D.tring[(int)((done + myoff) & (long long)rmask)];
         so.accepted = r.accepted; so.n_after = (my_commit && !(r.has_rem && r.has_add)) ? cur_n : n;
         out[idx] = so;
       }
@@ -1282,7 +1320,10 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     // decision above works on the reports alone).
     if (any_apply) stage = 0;                   // (my_commit of the steps without such neighbours: they just skip the pass)
     else {
-      if (any_commit && my_commit) deep_mutate(c, r, n, D.st + (size_t)5 * myoff);
+      if (any_commit && my_commit) {
+        if constexpr (QUE) deep_unpark_unit(D, myoff, r);
+        deep_mutate(c, r, n, D.st + (size_t)5 * myoff);
+      }
       my_commit = false;
       ring_from = done + 2 * nmax; ring_todo = committed;
       done += committed;
@@ -1292,7 +1333,10 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       // ---- D: the committed changes (stage 0; their neighbours' reductions were written just above)
       __syncthreads();                          // (4) every reduction is written before a list or a slot changes
       DPH(10);
-      if (my_commit) deep_mutate(c, r, n, D.st + (size_t)5 * myoff);
+      if (my_commit) {
+        if constexpr (QUE) deep_unpark_unit(D, myoff, r);
+        deep_mutate(c, r, n, D.st + (size_t)5 * myoff);
+      }
       my_commit = false;
       ring_from = done + 2 * nmax; ring_todo = committed;
       done += committed;
@@ -1327,15 +1371,16 @@ extern "C" size_t mpp_deep_static_lds_bytes(int waves) {
   return waves >= MPP_LDS_PARAMS_MIN_WAVES ? ((sizeof(DevParams) + 15) & ~(size_t)15) : 0;
 }
 
-template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false>
+template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false, int NCH = DEEP_NMAX_LIMIT / 64>
 static hipError_t launch_deep_d(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
                                 const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
                                 int trace_tile, mpp_step_out *out, mpp_proposal *props, int nmax, int fixed_depth, int gain8,
                                 unsigned long long *stats, const PreTab &pt) {
-  hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE>,
+  if (nmax > 64 * NCH) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
+  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
                      trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, pt);
   return hipGetLastError();
 }
@@ -1350,9 +1395,15 @@ extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int gr
                                       mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext,
                                       const PreTab *pt) {
   const bool diag = out || props, tab = pt->word != nullptr && !ext;
-  if (tab && pt->qoff != nullptr && waves == 8 && (gain8 & 0x100) == 0)
-    return diag ? launch_deep_d<8, true, 2, false, true, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
-                : launch_deep_d<8, false, 2, false, true, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt);
+  if (tab && pt->qoff != nullptr && waves == 8 && (gain8 & 0x100) == 0) {
+    // the queue rounds keep two chunks of step reports per lane where the round has at most 128 steps (the default depth), four above
+#define GOQ_(N)                                                                                                                  \
+  return diag ? launch_deep_d<8, true, 2, false, true, true, N>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt) \
+              : launch_deep_d<8, false, 2, false, true, true, N>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
+    if (nmax <= 128) { GOQ_(2); }
+    GOQ_(DEEP_NMAX_LIMIT / 64);
+#undef GOQ_
+  }
 #define GO_(W, O, X, T)                                                                                                   \
   return diag ? launch_deep_d<W, true, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt) \
               : launch_deep_d<W, false, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
