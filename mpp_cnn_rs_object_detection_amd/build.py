@@ -20,7 +20,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibi
 # max-memory-clause schedulers: no gain or worse).  -unroll-runtime (loops whose trip count is only known at run time get an
 # unrolled body with a remainder loop): +0.6 % / +0.7 % on top.  Same arithmetic, byte-identical chains.
 _CHAIN_FLAGS = ["-mllvm", "-disable-machine-licm", "-mllvm", "-unroll-threshold=600", "-mllvm", "-unroll-runtime"]
-EXTRA = {"mpp_sampler.hip": _CHAIN_FLAGS, "mpp_sampler_hbm.hip": _CHAIN_FLAGS, "mpp_deep.hip": _CHAIN_FLAGS}
+EXTRA = {"mpp_sampler.hip": _CHAIN_FLAGS, "mpp_sampler_hbm.hip": _CHAIN_FLAGS, "mpp_deep.hip": _CHAIN_FLAGS, "mpp_hot.hip": _CHAIN_FLAGS}
 
 
 def sources():
@@ -42,7 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                                                    for d in [src] + deps()[len(sources()):]):
             todo.append([HIPCC] + FLAGS + EXTRA.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
         objs.append(obj)
-    if todo:                                            # (the three chain-kernel files take 1.5 minutes each: side by side)
+    if todo:                                            # (the four chain-kernel files take 1.5 minutes each: side by side)
         from concurrent.futures import ThreadPoolExecutor
 
         def run(cmd):

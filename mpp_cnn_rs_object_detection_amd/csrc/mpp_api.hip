@@ -135,6 +135,9 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
   } else if (!strcmp(name, "prepass_queues")) {
     if (v < 0 || v > 1) return fail(c, -1, "prepass_queues must be 0 or 1");
     c->prepass_queues = (int)v;
+  } else if (!strcmp(name, "hot_table")) {
+    if (v < 0 || v > 1) return fail(c, -1, "hot_table must be 0 or 1");
+    c->hot_table = (int)v;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -169,6 +172,8 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "prepass_used")) return c->prepass_used;
   if (!strcmp(name, "prepass_queues")) return c->prepass_queues;
   if (!strcmp(name, "prepass_queues_used")) return c->prepass_queues_used;
+  if (!strcmp(name, "hot_table")) return c->hot_table;
+  if (!strcmp(name, "hot_table_used")) return c->hot_table_used;
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now

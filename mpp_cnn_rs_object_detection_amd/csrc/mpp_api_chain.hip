@@ -79,8 +79,13 @@ static int ensure_birth_tables(mpp_ctx *c) {
 // The birth table of a deep launch (mpp_prepass.hip), on the launch's stream right before it: every chain of the launch,
 // every step it has left (at most n_steps).  pt->word stays nullptr -- the launch draws its births itself -- when the pre-pass
 // is off or the table would exceed prepass_mb; pt->qoff stays nullptr -- births only -- when the queues would.
+// The hot launch builds the table of the call (launch_lds): it covers every step the call has left, and the launches that
+// follow with the same chain list -- the hot start's re-launch after a capacity stop, the deep launch after the handover,
+// its re-launches -- read it from the step their chains have reached (PreTab::base).  A launch whose chain list differs
+// (routing to device memory: compacted tile tables) builds its own.
+// need_queues (the hot launch): a table without queues whose words carry positions is of no use -- nothing is launched then.
 static int build_prepass(mpp_ctx *c, const DevParams *P, const TileRef *tiles, int tile0, int n, const long long *until,
-                         int64_t n_steps, uint64_t seed, uint32_t chain0, PreTab *pt) {
+                         int64_t n_steps, uint64_t seed, uint32_t chain0, PreTab *pt, bool need_queues = false) {
   *pt = PreTab{};
   if (!c->prepass || n <= 0 || n > 65535 || n_steps <= 0) return 0;       // (the chains are the grid's second dimension)
   const long long stride = n_steps;
@@ -97,6 +102,7 @@ static int build_prepass(mpp_ctx *c, const DevParams *P, const TileRef *tiles, i
                need_q = qent_off + (size_t)n * stride * sizeof(QEnt);
   const bool queues = c->prepass_queues && c->spec == 8 && (c->deep_gain & 0x100) == 0 && P->n_kernels <= MPP_K_SPLIT &&
                       stride < 0x7fffffffll && need_q <= budget;
+  if (need_queues && !(queues && stride < (1ll << 28))) return 0;
   HIPCHK(c, c->pre_ws.reserve(c->stream, queues ? need_q : need_b));
   unsigned char *ws = c->pre_ws.p;
   unsigned long long *total = (unsigned long long *)ws;
@@ -114,15 +120,15 @@ static int build_prepass(mpp_ctx *c, const DevParams *P, const TileRef *tiles, i
   // the queues and the birth records together over the budget: the births table alone may still fit (the queues' counts
   // are then left unused)
   const bool use_q = queues && need_q + rec_bytes <= budget;
-  if ((use_q ? need_q : need_b) + rec_bytes > budget) return 0;
+  if ((use_q ? need_q : need_b) + rec_bytes > budget || (need_queues && !use_q)) return 0;
   if (!use_q) { qtot = nullptr; qcnt = nullptr; qoff = nullptr; qent = nullptr; }
   HIPCHK(c, c->pre_rec.reserve(c->stream, rec_bytes));   // (the stream is idle: synchronised just above)
   double *rec = (double *)c->pre_rec.p;
-  HIPCHK(c, mpp_prepass_fill(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, word, rec, qcnt, qoff, qent));
-  pt->word = word; pt->rec = rec; pt->stride = stride;
+  HIPCHK(c, c->pre_base.reserve(c->stream, (size_t)n * sizeof(long long)));
+  long long *base = (long long *)c->pre_base.p;
+  HIPCHK(c, mpp_prepass_fill(c->stream, P, tiles, tile0, n, until, seed, chain0, nblk, stride, cnt, word, rec, qcnt, qoff, qent, base));
+  pt->word = word; pt->rec = rec; pt->stride = stride; pt->base = base;
   pt->qoff = qoff; pt->qent = qent; pt->qcnt = qcnt; pt->qtot = qtot; pt->qnblk = nblk;
-  c->prepass_used = 1;
-  if (use_q) c->prepass_queues_used = 1;
   return 0;
 }
 
@@ -140,6 +146,9 @@ struct ChainRun {
   int deep_nmax = 0, occ = 1, hbm_waves = 8;     // deep_nmax: most steps of a deep round (0: one wave per step)
   long long trace_base = 0;
   bool hot_start = false, hot_checked = false;
+  PreTab call_pt{};                  // the table the hot launch built, and the chain list it was built for
+  const TileRef *call_pt_tiles = nullptr; int call_pt_tile0 = 0, call_pt_n = 0;
+  bool call_pt_fits() const { return call_pt.qent && n_hbm == 0 && call_pt_tiles == tiles && call_pt_tile0 == tile0_r && call_pt_n == n_lds; }
   // this round: its LDS capacities, the chains of each home, their tile / until tables (LDS from tile0_r, the others from n_lds)
   bool decoupled;
   int lcap, lcell, n_lds, n_hbm, trace_l, trace_h, tile0_r;
@@ -254,12 +263,34 @@ int ChainRun::launch_lds() {
     int fixed = c->deep_fixed > nmax ? nmax : c->deep_fixed;
     if (fixed > 0) { fixed = fixed / sh.waves * sh.waves; if (fixed < sh.waves) fixed = sh.waves; }
     PreTab pt{};
-    if (!sh.ext && (rc = build_prepass(c, &lp, tiles, tile0_r, n_lds, until, n_steps, seed, chain0, &pt))) return rc;
+    if (call_pt_fits()) pt = call_pt;
+    else {
+      call_pt = PreTab{};                      // (a build reuses the table's buffers)
+      if (!sh.ext && (rc = build_prepass(c, &lp, tiles, tile0_r, n_lds, until, n_steps, seed, chain0, &pt))) return rc;
+    }
+    if (pt.word) c->prepass_used = 1;
+    if (pt.qoff) c->prepass_queues_used = 1;
     HIPCHK(c, mpp_launch_deep(c->stream, sh.waves, occ, n_lds, lds, &lp, tiles, tile0_r, until, trace_base, seed, chain0, trace_l,
                               d_out, d_props, nmax, fixed, c->deep_gain, (unsigned long long *)c->deep_stats.p, sh.ext, &pt));
-  } else
-    HIPCHK(c, mpp_launch_chain(c->stream, c->spec, c->lanes, occ, n_lds, lds, &lp, tiles, tile0_r, until, trace_base, seed, chain0,
-                               d_tape, trace_l, d_out, d_props));
+  } else {
+    // the hot start reads its steps' draws from a table (mpp_hot.hip) where the pre-pass builds one with queues whose words can
+    // carry a queue position; otherwise -- and for every other one-wave-per-step launch -- the chain draws them itself
+    // (MPP_NO_FAST=1 asks for the generic pair loops, mpp_sampler.hip: the table kernel has the specialised ones only)
+    static const bool no_fast = getenv("MPP_NO_FAST") != nullptr;
+    PreTab pt{};
+    if (call_pt_fits()) pt = call_pt;
+    else if (hot_start && c->hot_table && !sh.ext && !no_fast) {
+      if ((rc = build_prepass(c, &lp, tiles, tile0_r, n_lds, until, n_steps, seed, chain0, &pt, true))) return rc;
+      call_pt = PreTab{};
+      if (n_hbm == 0) { call_pt = pt; call_pt_tiles = tiles; call_pt_tile0 = tile0_r; call_pt_n = n_lds; }
+    }
+    if (pt.qent && pt.stride < (1ll << 28)) {
+      HIPCHK(c, mpp_launch_hot(c->stream, n_lds, lds, &lp, tiles, tile0_r, until, &pt));
+      c->hot_table_used = 1;
+    } else
+      HIPCHK(c, mpp_launch_chain(c->stream, c->spec, c->lanes, occ, n_lds, lds, &lp, tiles, tile0_r, until, trace_base, seed, chain0,
+                                 d_tape, trace_l, d_out, d_props));
+  }
   return 0;
 }
 
@@ -377,7 +408,7 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
     k.trace_base = s0;
   }
   c->last_ms = 0.0;
-  c->hbm_chains = 0; c->prepass_used = 0; c->prepass_queues_used = 0;
+  c->hbm_chains = 0; c->prepass_used = 0; c->prepass_queues_used = 0; c->hot_table_used = 0;
   if ((int)c->hbm_tile.size() != c->n_tiles) c->hbm_tile.assign(c->n_tiles, 0);
   k.occ = (grid >= 1024) ? 2 : 1;          // many chains in one launch: prefer the instantiation that lets two waves share a SIMD
   k.hbm_waves = (c->lanes == 0 && c->spec == 1) ? 1 : 8;

@@ -262,6 +262,9 @@ __device__ __forceinline__ double finish_energy_c(const Chain &c, double lin) {
 #ifndef MPP_STATE_HBM
 #define MPP_STATE_HBM 0
 #endif
+#ifndef MPP_HOT_TABLE
+#define MPP_HOT_TABLE 0       // 1 in mpp_hot.hip: mpp_chain_body.inc takes every step's draw from the pre-pass table
+#endif
 __device__ __forceinline__ void wave_lds_fence() {
 #if MPP_STATE_HBM
   // The state arrays are in device memory.  The argument below does not carry over: the LLVM AMDGPU memory model
@@ -1192,6 +1195,7 @@ __device__ __forceinline__ void window_draw_lane(const Chain &c, int x, int y, d
 #define KEEP_QFB 8            // forward AND backward probability were computed while drawing (data-driven transform)
 #define KEEP_EDGE_ANGLE 16    // the proposed angle is the lower edge of class r.ncls: its cos / sin are in the LDS table
 #define KEEP_MV 32            // the score-map values of the proposed rectangle were fetched while drawing
+#define KEEP_REC 64           // a birth from the pre-pass table: density, geometry and unit terms are in the record (deep_load_birth)
 
 // Wave mode with remap tables: the kernels that draw a mark class from a score-map row (data-driven birth and
 // transform) know the PIXEL of the proposed rectangle one memory latency before they know its classes.  The three
@@ -1427,6 +1431,8 @@ __device__ __forceinline__ void draw_proposal(const Chain &c, const uint32_t w[8
 // the head depends on the step's Philox blocks 0 and 1 alone -- the pre-pass computes it for every step with a target (deaths,
 // translations, transforms) and keeps it in the step's queue entry -- the tail, in the lane form, finishes the proposal
 // against the configuration.  Together they run the operations of draw_proposal<true>() on the same values: the same bits.
+// draw_tail_q<false> is the wave form of the tail (the table form of the hot start, mpp_hot.hip): the operations of
+// draw_proposal<false>() after the head -- window_draw, the remap-table rows, KEEP_MV.  A change in one form is made in the others.
 __device__ __forceinline__ void draw_head_q(const DevParams *P, int k, const uint32_t w[8], QEnt &e) {
   e.w2 = w[2]; e.u_acc = u53(w[6], w[7]); e.a = 0.0; e.b = 0.0;
   double z0 = 0.0, z1 = 0.0;
@@ -1442,7 +1448,8 @@ __device__ __forceinline__ void draw_head_q(const DevParams *P, int k, const uin
     e.a = u32d(w[4]); e.b = (double)mulhi32(w[3], 3u);
   }
 }
-__device__ __forceinline__ void draw_tail_q(const Chain &c, int k, const QEnt &e, int n, Rec &r, int *keep) {
+template <bool LANE = true>
+__device__ __forceinline__ void draw_tail_q(const Chain &c, int k, const QEnt &e, int n, Rec &r, int *keep, MapVals *pmv = nullptr) {
   const DevParams *P = c.P;
   r.kernel = k; r.tidx = -1; r.tslot = -1; r.has_rem = 0; r.has_add = 0; r.pid = -1; r.ncls = -1; r.acls = 0; r._pad2 = 0;
   r.aux0 = r.aux1 = 0.0; r.ax = r.ay = 0; r.as = r.ar = r.aa = 0.0; r.rx = r.ry = 0;
@@ -1464,7 +1471,8 @@ __device__ __forceinline__ void draw_tail_q(const Chain &c, int k, const QEnt &e
     *keep = KEEP_TRIG | KEEP_SIZE;
   } else if (k == MPP_K_DTRANS) {
     int ex, ey;
-    window_draw_lane(c, q.x, q.y, e.a, &ex, &ey);
+    if constexpr (LANE) window_draw_lane(c, q.x, q.y, e.a, &ex, &ey);
+    else window_draw(c, q.x, q.y, e.a, &ex, &ey);
     q.x = ex; q.y = ey;
     *keep = KEEP_TRIG | KEEP_SIZE;
   } else if (k == MPP_K_GTRANSF) {
@@ -1478,15 +1486,43 @@ __device__ __forceinline__ void draw_tail_q(const Chain &c, int k, const QEnt &e
     int cls;
     const int oc = value_to_class_tab(P, c.L.edges + pid * MPP_NCLASS, pid, mark_of(q, pid));
     double pb = 0.0;
-    r.qf = row_prob(c, pid, q.x, q.y, 0, true, e.a, &cls, oc, &pb);
-    r.qb = pb;
-    set_mark(q, pid, c.L.edges[pid * MPP_NCLASS + cls]);
-    r.pid = pid; r.ncls = cls; r.acls = cls;
-    *keep = (pid == 2 ? KEEP_SIZE : KEEP_TRIG) | KEEP_QFB | (pid == 2 ? KEEP_EDGE_ANGLE : 0);
+    if constexpr (LANE) {
+      r.qf = row_prob(c, pid, q.x, q.y, 0, true, e.a, &cls, oc, &pb);
+      r.qb = pb;
+      set_mark(q, pid, c.L.edges[pid * MPP_NCLASS + cls]);
+      r.pid = pid; r.ncls = cls; r.acls = cls;
+      *keep = (pid == 2 ? KEEP_SIZE : KEEP_TRIG) | KEEP_QFB | (pid == 2 ? KEEP_EDGE_ANGLE : 0);
+    } else {
+      const bool pre = c.t.rm[0] != nullptr;
+      TabRows tr{0.0, 0.0};
+      float detv = 0.f;
+      if (pre) { detv = c.t.det[(size_t)q.x * c.h.W + q.y]; tr = tab_rows_request(c, ((size_t)q.x * c.h.W + q.y) * MPP_NCLASS); }
+      r.qf = row_prob(c, pid, q.x, q.y, 0, true, e.a, &cls, oc, &pb);
+      r.qb = pb;
+      set_mark(q, pid, c.L.edges[pid * MPP_NCLASS + cls]);
+      r.pid = pid; r.ncls = cls; r.acls = cls;
+      *keep = (pid == 2 ? KEEP_SIZE : KEEP_TRIG) | KEEP_QFB | (pid == 2 ? KEEP_EDGE_ANGLE : 0);
+      if (pre) { *pmv = tab_rows_pick(c, tr, detv, q); *keep |= KEEP_MV; }
+    }
   }
   int fx = q.x, fy = q.y;
   asm volatile("" : "+v"(fx), "+v"(fy));     // (as in draw_proposal)
   r.ax = fx; r.ay = fy; r.as = q.s; r.ar = q.r; r.aa = q.a;
+}
+
+// a birth step's proposal, geometry and unit terms from the pre-pass table (what draw_proposal, deep_add_geo and deep_pre
+// give a birth lane; mpp_prepass.hip computes them with those functions)
+__device__ __forceinline__ void deep_load_birth(const PreTab &pt, unsigned int ord, int k, Rec &r) {
+  const double2 *q = (const double2 *)(pt.rec + (size_t)ord * PRE_REC_DOUBLES);
+  const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(q5.y);
+  r.kernel = k; r.tidx = -1; r.tslot = -1; r.has_rem = 0; r.has_add = 1; r.pid = -1; r.ncls = -1; r.acls = 0; r._pad2 = 0;
+  r.aux0 = r.aux1 = 0.0; r.rx = r.ry = 0;
+  r.u_acc = q0.x; r.qf = q0.y; r.qb = 1.0;
+  r.ax = (int)(bits & 0xffffu); r.ay = (int)((bits >> 16) & 0xffffu); r.gate_a = (int)(bits >> 32);
+  r.as = q1.x; r.ar = q1.y; r.aa = q2.x; r.lin_a = q2.y;
+  r.hl = q3.x; r.hw = q3.y; r.ca = q4.x; r.sa = q4.y; r.rad = q5.x;
+  r.dE = 0.0; r.n_stash = 0; r.ra0 = r.ra1 = 0.0;
 }
 
 // the geometry of the rectangle a lane-form step adds (what of it the step keeps from its target comes from the target's cached values)
@@ -1588,6 +1624,17 @@ __device__ __forceinline__ void green_terms(const DevParams *P, const Rec &r, in
   }
 }
 
+// the accept test of a step whose dE and proposal densities are in r (population n, temperature T)
+// rjmcmc.py:105-113: accept <=> log(u+eps) < -dE/T + log(bwd+eps) - log(fwd+eps)
+//                           <=> u+eps < exp(-dE/T) * (bwd+eps)/(fwd+eps)      (one exp instead of three logs)
+__device__ __forceinline__ void accept_step(const DevParams *P, Rec &r, int n, double intensity, double T, bool tracing) {
+  double fwd, bwd;
+  green_terms(P, r, n, intensity, &fwd, &bwd);
+  double ratio = (bwd + EPS_GREEN) / (fwd + EPS_GREEN);
+  r.accepted = (P->force_accept || (r.u_acc + EPS_GREEN) < exp(-r.dE / T) * ratio) ? 1 : 0;
+  if (tracing) { r.fwd = fwd; r.bwd = bwd; r.log_alpha = (-r.dE / T) + log(bwd + EPS_GREEN) - log(fwd + EPS_GREEN); }
+}
+
 // ---- state mutation (energy_point_set.py:118-154), wave 0 only ----------------------------------
 __device__ void cell_remove(const Chain &c, int cell, int slot) {
   const Lds &L = c.L;
@@ -1681,13 +1728,18 @@ __device__ void evaluate(const Chain &c, Rec &r, int ri, int keep, int n, double
                               &r.n_stash, apply);
     EPROF(7);
   }
-  double fwd, bwd;
-  green_terms(P, r, n, c.t.intensity, &fwd, &bwd);
-  // rjmcmc.py:105-113: accept <=> log(u+eps) < -dE/T + log(bwd+eps) - log(fwd+eps)
-  //                           <=> u+eps < exp(-dE/T) * (bwd+eps)/(fwd+eps)      (one exp instead of three logs)
-  double ratio = (bwd + EPS_GREEN) / (fwd + EPS_GREEN);
-  r.accepted = (P->force_accept || (r.u_acc + EPS_GREEN) < exp(-r.dE / T) * ratio) ? 1 : 0;
-  if (tracing) { r.fwd = fwd; r.bwd = bwd; r.log_alpha = (-r.dE / T) + log(bwd + EPS_GREEN) - log(fwd + EPS_GREEN); }
+  accept_step(P, r, n, c.t.intensity, T, tracing);
   EPROF(8);
 }
 
+// evaluate() for a birth whose record came from the pre-pass table (deep_load_birth: KEEP_REC): its density, geometry and unit
+// terms are in r, what is left depends on the configuration -- dE against the neighbours, then accept_step as in evaluate()
+template <bool FAST>
+__device__ void evaluate_tab_birth(const Chain &c, Rec &r, int ri, int n, double T, bool apply) {
+  const DevParams *P = c.P;
+  const Rect add{r.ax, r.ay, r.as, r.ar, r.aa};
+  Geo2 ag;
+  ag.g.x = add.x; ag.g.y = add.y; ag.g.hl = r.hl; ag.g.hw = r.hw; ag.g.ca = r.ca; ag.g.sa = r.sa; ag.rad = r.rad;
+  r.dE = eval_delta<FAST>(c, ri, -1, true, add, ag, r.lin_a, r.gate_a, &r.ra0, &r.ra1, &r.n_stash, apply);
+  accept_step(P, r, n, c.t.intensity, T, false);
+}

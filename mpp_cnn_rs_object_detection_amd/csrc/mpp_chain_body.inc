@@ -6,6 +6,8 @@
 // of the 40 instantiations), and the LDS kernels are meant to stay the code objects they were.
 // In scope: the kernel's parameters (Pv, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props;
 // ws and ws_stride with MPP_STATE_HBM) and template constants WAVES, LPW, DIAG, SM, FAST.
+// A third home is mpp_hot_kernel (mpp_hot.hip, MPP_HOT_TABLE): the untraced hot start whose steps take their draw from the
+// pre-pass table `pt` of the launch (mpp_prepass.hpp) instead of Philox; it has no seed, chain0, tape or trace arguments.
   constexpr bool LANE = LPW > 0;
   constexpr int SPEC = LANE ? WAVES * LPW : WAVES;
   // the parameter block travels BY VALUE: it then lives in the kernel-argument segment (constant address space),
@@ -102,9 +104,15 @@
   const long long n_steps = until[tile] - step0;
   // records of a traced tile / tape entries are indexed from the step the host's call started at
   const long long tr0 = step0 - trace_base;
+#if MPP_HOT_TABLE
+  // this chain's part of pt.word / pt.qent, from the entry of step0 (a re-launch after a capacity stop starts in mid-table)
+  const size_t pre_ent = (size_t)blockIdx.x * (size_t)pt.stride;
+  const size_t pre_reg = pre_ent + (size_t)(pt.base ? step0 - pt.base[blockIdx.x] : 0);
+#else
   const unsigned long long seed_t = c.t.key_on ? (unsigned long long)c.t.key_seed : seed;
   const uint32_t chain_t = c.t.key_on ? c.t.key_chain : chain0 + (uint32_t)tile;
   const uint32_t k0 = (uint32_t)seed_t, k1 = (uint32_t)(seed_t >> 32);
+#endif
 #ifdef MPP_PROFILE
   unsigned long long prof_[16] = {0};
 #endif
@@ -169,6 +177,19 @@
           r.valid = 0; r.kernel = -1;
         }
       } else {
+#if MPP_HOT_TABLE
+        // the step's word, then its birth record or its queue entry (the head of its proposal): nothing of the draw that
+        // does not depend on the configuration is computed here.  An apply round reads the same entry again.
+        const uint32_t wd = pt.word[pre_reg + (size_t)my];
+        const int k = (int)(wd & 15u);
+        if (k == MPP_K_UBIRTH || k == MPP_K_DBIRTH) {
+          deep_load_birth(pt, wd >> 4, k, r);
+          keep = KEEP_REC;
+        } else {
+          const QEnt e = pt.qent[pre_ent + (size_t)(wd >> 4)];
+          draw_tail_q<false>(c, k, e, n, r, &keep, &pmv);
+        }
+#else
         uint32_t w[8];
         uint64_t s = (uint64_t)(step0 + my);
 #pragma unroll
@@ -180,6 +201,7 @@
           sm_draw(c, r, ri, n, w, k0, k1, s, chain_t, &e);
           if (e) { r.valid = 0; r.kernel = -2 - e; }
         } else if (!SM && r.kernel >= MPP_K_SPLIT) { r.valid = 0; r.kernel = -1; }
+#endif
       }
 #ifdef MPP_PROFILE
       { unsigned long long n_ = clock64(); if (c.wave == 0 && c.lane == 0 && r.kernel >= 0 && r.kernel < 8) atomicAdd(&g_prof4[r.kernel], n_ - pt_); }
@@ -196,6 +218,10 @@
           sm_step(c, r, ri, n, T, tracing, &e);
           if (e) { r.valid = 0; r.kernel = -2 - e; }
         }
+#if MPP_HOT_TABLE
+      } else if (r.valid && (keep & KEEP_REC)) {
+        evaluate_tab_birth<FAST>(c, r, ri, n, T, apply_round);
+#endif
       } else if (r.valid) {
 #ifdef MPP_PROFILE
         evaluate<LANE, FAST, SM>(c, r, ri, keep, n, T, tracing, apply_round, pmv, prof_);

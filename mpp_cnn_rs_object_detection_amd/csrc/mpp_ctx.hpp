@@ -84,8 +84,12 @@ struct mpp_ctx : TileMem {
   // ... and with it the steps of every kernel type in queues (prepass_queues 1), from which the rounds of a chain of eight
   // waves take their steps (the deep kernel's QUE instantiation); prepass_queues_used: a deep launch of the last call did
   int prepass_queues = 1, prepass_queues_used = 0;
+  // ... and the hot start takes its steps' draws from a table of its own launch (hot_table 1: mpp_hot.hip; it needs the queues);
+  // hot_table_used: a hot launch of the last call read one
+  int hot_table = 1, hot_table_used = 0;
   DevWs pre_ws;                      // the table's total, block counts and step words
   DevWs pre_rec;                     // its birth records
+  DevWs pre_base;                    // per chain of the table: the step its part starts at (PreTab::base)
   int replicas = 1, n_maps = 0;      // n_tiles = n_maps * replicas chains; chain t samples on the maps of tile t % n_maps
   bool remap_dirty = true;
   int remap_mode = -1;               // option "remap_table": -1 auto (when the tables fit remap_budget), 0 never, 1 always

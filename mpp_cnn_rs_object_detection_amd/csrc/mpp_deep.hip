@@ -659,21 +659,6 @@ __device__ __forceinline__ void deep_mutate(const Chain &c, const Rec &r, int n,
 }
 __device__ __forceinline__ unsigned long long low_mask(int k) { return k <= 0 ? 0ull : (k >= 64 ? ~0ull : ((1ull << k) - 1ull)); }
 
-// a birth step's proposal, geometry and unit terms from the pre-pass table (what draw_proposal, deep_add_geo and deep_pre
-// give a birth lane; mpp_prepass.hip computes them with those functions)
-__device__ __forceinline__ void deep_load_birth(const PreTab &pt, unsigned int ord, int k, Rec &r) {
-  const double2 *q = (const double2 *)(pt.rec + (size_t)ord * PRE_REC_DOUBLES);
-  const double2 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
-  const unsigned long long bits = (unsigned long long)__double_as_longlong(q5.y);
-  r.kernel = k; r.tidx = -1; r.tslot = -1; r.has_rem = 0; r.has_add = 1; r.pid = -1; r.ncls = -1; r.acls = 0; r._pad2 = 0;
-  r.aux0 = r.aux1 = 0.0; r.rx = r.ry = 0;
-  r.u_acc = q0.x; r.qf = q0.y; r.qb = 1.0;
-  r.ax = (int)(bits & 0xffffu); r.ay = (int)((bits >> 16) & 0xffffu); r.gate_a = (int)(bits >> 32);
-  r.as = q1.x; r.ar = q1.y; r.aa = q2.x; r.lin_a = q2.y;
-  r.hl = q3.x; r.hw = q3.y; r.ca = q4.x; r.sa = q4.y; r.rad = q5.x;
-  r.dE = 0.0; r.n_stash = 0; r.ra0 = r.ra1 = 0.0;
-}
-
 // (QUE) The fields of a step that the neighbour pass does not read wait in LDS while it runs, in space of the step's own
 // offset that nothing else uses at that time: u_acc and qf in its report D.info[off], qb in D.nb[off] (both are written only
 // after deep_post, and every wave has finished reading the previous round's reports before barrier (1)); lin_a and gate_a
@@ -787,7 +772,9 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   }
   if (tid == nthr - 1) {                        // temperatures of the first 2 * nmax steps (rjmcmc.py:158-159, one multiply per step)
     double Tc = *c.t.T;
-    for (int i = 0; i < 2 * nmax; ++i) { D.tring[i] = Tc; if (Tc > T_target) Tc *= alpha; }
+    long long d0 = 0;                           // (QUE) the ring is indexed by the step's offset from the table's first
+    if constexpr (QUE) d0 = pt.base ? *c.t.step - pt.base[blockIdx.x] : 0;
+    for (int i = 0; i < 2 * nmax; ++i) { D.tring[(int)((d0 + i) & (long long)rmask)] = Tc; if (Tc > T_target) Tc *= alpha; }
   }
   __syncthreads();
   err = __builtin_amdgcn_readfirstlane(L.sh[1]);
@@ -808,14 +795,17 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   __syncthreads();
 
   // ---------------------------------------------------------------- the chain
-  const long long step0 = *c.t.step;
+  // (QUE) A launch may start in mid-table -- after the hot start's handover, after a capacity stop: step0 is then the table's
+  // first step and done starts at the chain's offset from it, so the round loop indexes the table as ever.
+  long long done = 0;
+  if constexpr (QUE) done = pt.base ? *c.t.step - pt.base[blockIdx.x] : 0;
+  const long long step0 = *c.t.step - done;
   const long long n_steps = until[tile] - step0;
   const long long tr0 = step0 - trace_base;
   const unsigned long long seed_t = c.t.key_on ? (unsigned long long)c.t.key_seed : seed;
   const uint32_t chain_t = c.t.key_on ? c.t.key_chain : chain0 + (uint32_t)tile;
   const uint32_t k0 = (uint32_t)seed_t, k1 = (uint32_t)(seed_t >> 32);
   const unsigned long long below = (1ull << c.lane) - 1ull;
-  long long done = 0;
   int n = n0;                                   // the population, tracked by every wave
   int depth = WAVES, ema16 = WAVES * 16;        // steps of the next round; committed steps per round, x16, smoothed
   unsigned long long st_rounds = 0, st_eval = 0, st_apply = 0;
@@ -845,6 +835,22 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     qs.eb = __builtin_amdgcn_readfirstlane((int)qc[(size_t)(MPP_K_UDEATH + 1) * pt.qnblk]);
     qs.reg = (size_t)blockIdx.x * (size_t)pt.stride;
     qs.xa = qs.xb = 0xffffffffu;
+    if (done > 0) {
+      // the cursors start at the first entry of their queue that is not below `done`: the scanned counts give the position at
+      // the enclosing block of PRE_BLOCK steps, a pass over that block's entries the rest (once, before the round loop)
+      const size_t blk = (size_t)(done / PRE_BLOCK);
+      auto first_at = [&](int qt, int end) {
+        const int p0 = (int)qc[(size_t)qt * pt.qnblk + blk];
+        int cnt = 0;
+        for (int j = 0; j < PRE_BLOCK; j += WAVE) {
+          const int i = p0 + j + c.lane;
+          cnt += __popcll(__ballot(i < end && pt.qoff[qs.reg + i] < (uint32_t)done));
+        }
+        return __builtin_amdgcn_readfirstlane(p0 + cnt);
+      };
+      qs.ca = first_at(qs.qt_a, qs.ea);
+      qs.cb = first_at(MPP_K_UDEATH, qs.eb);
+    }
   }
   while (stage == 0 || (done < n_steps && err == 0)) {
     bool do_eval = my_commit && r.n_stash > 2;  // stage 0: the steps that commit and change more neighbours than they could note
@@ -1357,9 +1363,11 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   if (stats && c.lane == 0) for (int i = 0; i < DPH_N; ++i) atomicAdd(stats + 16 + DPH_N * c.wave + i, dph_[i]);
 #endif
   if (tid == 0) {
+    long long start = 0;                        // (QUE) where in the table this launch started
+    if constexpr (QUE) start = *c.t.step - step0;
     *c.t.n = n; *c.t.err = err; *c.t.step = step0 + done;
     *c.t.T = D.tring[(int)(done & (long long)rmask)];
-    if (stats) { atomicAdd(stats, st_rounds); atomicAdd(stats + 1, st_eval); atomicAdd(stats + 2, st_apply); atomicAdd(stats + 3, (unsigned long long)done); }
+    if (stats) { atomicAdd(stats, st_rounds); atomicAdd(stats + 1, st_eval); atomicAdd(stats + 2, st_apply); atomicAdd(stats + 3, (unsigned long long)(done - start)); }
   }
 }
 

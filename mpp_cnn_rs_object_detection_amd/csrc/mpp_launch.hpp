@@ -22,6 +22,8 @@ hipError_t mpp_launch_chain(hipStream_t st, int spec, int lanes, int occ, int gr
                             const TileRef *tiles, int tile0, const long long *until, long long trace_base,
                             unsigned long long seed, unsigned int chain0, const mpp_proposal *tape, int trace_tile,
                             mpp_step_out *out, mpp_proposal *props);
+hipError_t mpp_launch_hot(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
+                          const long long *until, const PreTab *pt);
 size_t mpp_deep_lds_bytes(int cap, int ncell, int cell_cap, int rowbase_n, int waves, int nmax, int ext);
 size_t mpp_deep_static_lds_bytes(int waves);
 hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int grid, size_t lds, const DevParams *P, const TileRef *tiles,
@@ -34,7 +36,7 @@ hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *
 hipError_t mpp_prepass_fill(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                             const long long *until, unsigned long long seed, unsigned int chain0, int nblk, long long stride,
                             const unsigned int *off, uint32_t *word, double *rec, const unsigned int *qcnt, uint32_t *qoff,
-                            QEnt *qent);
+                            QEnt *qent, long long *base);
 void mpp_launch_papangelou_tiles(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int cap,
                                  double *dE, const int32_t *grid_start, const int32_t *grid_items, int sstride, int istride);
 void mpp_launch_grid_build_all(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, int max_n, int ncell,

@@ -3,7 +3,7 @@
 // Three kernels on the launch's stream, one thread per step of every chain of the launch:
 //   count  kernel type of each step (Philox block 0), births per block of PRE_BLOCK steps;
 //   scan   the births' ordinals: exclusive prefix of the block counts over all chains (one workgroup);
-//   fill   per step its word (type | ordinal), per birth its record: draw_head / draw_birth (lane forms), deep_add_geo and
+//   fill   per step its word (type | ordinal, or type | queue position), per birth its record: draw_head / draw_birth (lane forms), deep_add_geo and
 //          deep_pre -- the very functions the deep kernel ran for a birth lane, so the record holds its bits.
 // The host reads the number of births back between scan and fill (the records' size; a table over the prepass_mb budget
 // is not built and the launch draws its births itself).
@@ -84,7 +84,8 @@ __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevPa
                                                                      const long long *until, unsigned long long seed,
                                                                      unsigned int chain0, int nblk, long long stride,
                                                                      const unsigned int *off, uint32_t *word, double *rec,
-                                                                     const unsigned int *qcnt, uint32_t *qoff, QEnt *qent) {
+                                                                     const unsigned int *qcnt, uint32_t *qoff, QEnt *qent,
+                                                                     long long *base) {
   __shared__ double s_edges[3 * MPP_NCLASS];
   __shared__ unsigned int s_wcnt[PRE_BLOCK / WAVE];
   __shared__ unsigned int s_tcnt[PRE_BLOCK / WAVE][MPP_NKERNEL];
@@ -101,6 +102,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevPa
   c.wave = tid / WAVE;
   const long long s0 = *c.t.step, rel = (long long)blockIdx.x * PRE_BLOCK + tid, s = s0 + rel;
   const bool in = s < until[tile] && rel < stride;
+  if (base && blockIdx.x == 0 && tid == 0) base[ch] = s0;
   uint32_t k0, k1, chain, w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   pre_key(c.t, seed, chain0, tile, &k0, &k1, &chain);
   int kt = 15;
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevPa
   __syncthreads();
   unsigned int ord = off[(size_t)ch * nblk + blockIdx.x] + (unsigned int)__popcll(m & ((1ull << c.lane) - 1ull));
   for (int v = 0; v < c.wave; ++v) ord += s_wcnt[v];
-  if (in) word[(size_t)ch * stride + rel] = (uint32_t)kt | (birth ? ord << 4 : 0u);
+  uint32_t wd = (uint32_t)kt | (birth ? ord << 4 : 0u);
   if (qoff) {
     // my position in my type's queue: the block's first, then the waves before mine, then the lanes before mine
     unsigned long long same = 0ull;
@@ -140,8 +142,12 @@ __global__ __launch_bounds__(PRE_BLOCK) void mpp_prepass_fill_kernel(const DevPa
       const size_t at = (size_t)ch * stride + pos;
       qoff[at] = (uint32_t)rel;
       qent[at] = e;
+      // step to entry: the hot start (mpp_hot.hip) looks a step up by its index, so the word of a step that is no birth
+      // carries its queue position where a birth's carries its ordinal (28 bits)
+      if (!birth && stride < (1ll << 28)) wd |= pos << 4;
     }
   }
+  if (in) word[(size_t)ch * stride + rel] = wd;
   if (!birth) return;
   philox4x32_10((uint32_t)s, (uint32_t)((uint64_t)s >> 32), 1u, chain, k0, k1, w + 4);
   Rec r;
@@ -177,8 +183,8 @@ extern "C" hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, cons
 extern "C" hipError_t mpp_prepass_fill(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                                        const long long *until, unsigned long long seed, unsigned int chain0, int nblk,
                                        long long stride, const unsigned int *off, uint32_t *word, double *rec,
-                                       const unsigned int *qcnt, uint32_t *qoff, QEnt *qent) {
+                                       const unsigned int *qcnt, uint32_t *qoff, QEnt *qent, long long *base) {
   hipLaunchKernelGGL(mpp_prepass_fill_kernel, dim3(nblk, n_chains), dim3(PRE_BLOCK), 0, st, *P, tiles, tile0, until, seed,
-                     chain0, nblk, stride, off, word, rec, qcnt, qoff, qent);
+                     chain0, nblk, stride, off, word, rec, qcnt, qoff, qent, base);
   return hipGetLastError();
 }

@@ -9,8 +9,9 @@
 #include <cstdint>
 
 // per chain of the launch (launch-local index, the deep kernel's blockIdx.x) and step s in [step0, until), step0 the chain's
-// step when the launch starts (the pre-pass runs on the launch's stream right before it):
-//   word[chain * stride + s - step0] = kernel type (bits 0..3) | birth ordinal << 4 (births only)
+// step when the table is built (PreTab::base; the pre-pass runs on the stream before the first launch that reads it):
+//   word[chain * stride + s - step0] = kernel type (bits 0..3) | birth ordinal << 4 (births); with the queues and
+//                                      stride < 2^28, every other step: | its position p in qent << 4 (the hot start reads it)
 // and per birth (ordinal, over all chains of the launch) PRE_REC_DOUBLES values, six 16-byte pairs:
 //   (u_acc, qf) (as, ar) (aa, lin_a) (hl, hw) (ca, sa) (rad, bits: ax | ay << 16 | (gate_a) << 32)
 // (qb of a birth is always 1: proposal_densities() sets it so for both births)
@@ -39,6 +40,9 @@ struct PreTab {
   const unsigned int *qcnt;
   const unsigned long long *qtot;
   int qnblk;
+  const long long *base;       // per chain of the launch: the step its part of the table starts at (nullptr: the chain's step when
+                               // the launch starts).  A launch that finds its chain beyond it starts in mid-table: the hot start's
+                               // re-launch after a capacity stop, the deep launch after the handover
 };
 #define PRE_REC_DOUBLES 12
 #define PRE_REC_BYTES (PRE_REC_DOUBLES * 8)

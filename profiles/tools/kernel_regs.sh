@@ -1,7 +1,7 @@
 #!/bin/bash
 # registers / scratch of every instantiation of the chain kernels in a built object:
-#   bash profiles/tools/kernel_regs.sh [path/to/mpp_sampler.o | path/to/mpp_deep.o]
-# mpp_chain_kernel: WAVES,LPW,DIAG,OCC,SM,FAST; mpp_deep_kernel: WAVES,DIAG,OCC,EXT[,TAB[,QUE[,NCH]]]
+#   bash profiles/tools/kernel_regs.sh [path/to/mpp_sampler.o | path/to/mpp_deep.o | path/to/mpp_hot.o]
+# mpp_chain_kernel: WAVES,LPW,DIAG,OCC,SM,FAST; mpp_deep_kernel: WAVES,DIAG,OCC,EXT[,TAB[,QUE[,NCH]]]; mpp_hot_kernel: WAVES,OCC
 obj=${1:-mpp_cnn_rs_object_detection_amd/csrc/mpp_sampler.o}
 tmp=$(mktemp -d)
 B=/opt/rocm/lib/llvm/bin
@@ -21,6 +21,9 @@ for blk in re.split(r"\n\s+- \.agpr_count", txt)[1:]:
     elif "mpp_deep_kernel" in n:
         targs = re.search(r"ILi(\d+)ELb(\d)ELi(\d+)ELb(\d)E(?:Lb(\d)E)?(?:Lb(\d)E)?(?:Li(\d+)E)?", n)
         label = "deep WAVES,DIAG,OCC,EXT,TAB[,QUE[,NCH]] = " + (",".join(v for v in targs.groups() if v is not None) if targs else n)
+    elif "mpp_hot_kernel" in n:
+        targs = re.search(r"ILi(\d+)ELi(\d+)E", n)
+        label = "hot WAVES,OCC = " + (",".join(targs.groups()) if targs else n)
     else:
         continue
     print(label, " vgpr", g("vgpr_count"), "spill", g("vgpr_spill_count"), "sgpr", g("sgpr_count"), "sgpr_spill", g("sgpr_spill_count"), "scratch", g("private_segment_fixed_size"))
