@@ -364,8 +364,9 @@ int push_state(mpp_ctx *c) {
   if (!c->have_maps) return fail(c, -1, "mpp_set_maps has not been called");
   if (!c->have_model) return fail(c, -1, "mpp_set_model has not been called");
   {
-    int grad = 0;
-    if (has_classic(c->hp.model, &grad)) {
+    const ModelClass mc = model_class(c->hp);
+    const bool grad = mc.gradient;
+    if (mc.classic) {
       if (!c->img) return fail(c, -1, "the model has a classic image energy: mpp_set_image has not been called");
       if (grad ? (c->img_c != 2 && c->img_c != 6) : (c->img_c != 1 && c->img_c != 3))
         return fail(c, -1, "the image has %d channels: the %s energy wants %s", c->img_c, grad ? "gradient" : "contrast",

@@ -143,6 +143,7 @@ struct ChainRun {
   std::vector<long long> tab_until, h_until;
   std::vector<TileRef> tab;          // (tab, tab_until: the compacted tables of a round)
   LaunchShape sh;
+  ModelClass mc;
   int deep_nmax = 0, occ = 1, hbm_waves = 8;     // deep_nmax: most steps of a deep round (0: one wave per step)
   long long trace_base = 0;
   bool hot_start = false, hot_checked = false;
@@ -153,16 +154,17 @@ struct ChainRun {
   bool decoupled;
   int lcap, lcell, n_lds, n_hbm, trace_l, trace_h, tile0_r;
   const TileRef *tiles; const long long *until;
+  // the round's arguments as a launch takes them; launch_lds / launch_hbm set grid, lds, P, tile0 and trace_tile for their home
+  ChainLaunch args() const {
+    return ChainLaunch{c->stream, 0, 0, nullptr, tiles, 0, until, trace_base, seed, chain0, d_tape, -1, d_out, d_props};
+  }
   int decide_deep(), plan_route(), launch_lds(), launch_hbm(), settle();
 };
 
 // deep rounds: chains of the shipped energy setups drawn from Philox (no tape, no split / merge, no classic image energy)
 int ChainRun::decide_deep() {
-  const mpp_model &M = c->hp.model;
-  const bool fast = M.n_pair == 2 && M.pair[0].kind == MPP_P_OVERLAP && M.pair[0].reduce == MPP_REDUCE_MAX &&
-                    M.pair[1].kind == MPP_P_ALIGN && M.pair[1].reduce == MPP_REDUCE_MIN;
-  if (c->deep > 0 && c->lanes == 0 && c->spec <= 8 && !d_tape && fast && c->hp.n_kernels <= MPP_K_SPLIT &&
-      (!has_classic(M) || c->spec == 1 || c->spec == 8) && !c->hp.force_accept && c->hp.nx < 256 && c->hp.ny < 256) {
+  if (c->deep > 0 && c->lanes == 0 && c->spec <= 8 && !d_tape && mc.fast && !mc.split_merge &&
+      (!mc.classic || c->spec == 1 || c->spec == 8) && !c->hp.force_accept && c->hp.nx < 256 && c->hp.ny < 256) {
     deep_nmax = c->deep < 64 * c->spec ? c->deep : 64 * c->spec;
     if (deep_nmax < c->spec) deep_nmax = c->spec;
     if (c->H <= 1024) c->hp.rowbase_lds = 1;
@@ -259,6 +261,8 @@ int ChainRun::launch_lds() {
   c->hp.cap = c->cap; c->hp.cell_cap = c->cell_cap;
   DevParams lp = c->hp;
   lp.cap = lcap; lp.cell_cap = lcell;
+  ChainLaunch a = args();
+  a.grid = n_lds; a.lds = lds; a.P = &lp; a.tile0 = tile0_r; a.trace_tile = trace_l;
   if (nmax > 0) {
     int fixed = c->deep_fixed > nmax ? nmax : c->deep_fixed;
     if (fixed > 0) { fixed = fixed / sh.waves * sh.waves; if (fixed < sh.waves) fixed = sh.waves; }
@@ -270,26 +274,23 @@ int ChainRun::launch_lds() {
     }
     if (pt.word) c->prepass_used = 1;
     if (pt.qoff) c->prepass_queues_used = 1;
-    HIPCHK(c, mpp_launch_deep(c->stream, sh.waves, occ, n_lds, lds, &lp, tiles, tile0_r, until, trace_base, seed, chain0, trace_l,
-                              d_out, d_props, nmax, fixed, c->deep_gain, (unsigned long long *)c->deep_stats.p, sh.ext, &pt));
+    HIPCHK(c, mpp_launch_deep(a, sh.waves, occ, nmax, fixed, c->deep_gain, (unsigned long long *)c->deep_stats.p, sh.ext, &pt));
   } else {
     // the hot start reads its steps' draws from a table (mpp_hot.hip) where the pre-pass builds one with queues whose words can
     // carry a queue position; otherwise -- and for every other one-wave-per-step launch -- the chain draws them itself
     // (MPP_NO_FAST=1 asks for the generic pair loops, mpp_sampler.hip: the table kernel has the specialised ones only)
-    static const bool no_fast = getenv("MPP_NO_FAST") != nullptr;
     PreTab pt{};
     if (call_pt_fits()) pt = call_pt;
-    else if (hot_start && c->hot_table && !sh.ext && !no_fast) {
+    else if (hot_start && c->hot_table && !sh.ext && !mc.no_fast) {
       if ((rc = build_prepass(c, &lp, tiles, tile0_r, n_lds, until, n_steps, seed, chain0, &pt, true))) return rc;
       call_pt = PreTab{};
       if (n_hbm == 0) { call_pt = pt; call_pt_tiles = tiles; call_pt_tile0 = tile0_r; call_pt_n = n_lds; }
     }
     if (pt.qent && pt.stride < (1ll << 28)) {
-      HIPCHK(c, mpp_launch_hot(c->stream, n_lds, lds, &lp, tiles, tile0_r, until, &pt));
+      HIPCHK(c, mpp_launch_hot(a, &pt));
       c->hot_table_used = 1;
     } else
-      HIPCHK(c, mpp_launch_chain(c->stream, c->spec, c->lanes, occ, n_lds, lds, &lp, tiles, tile0_r, until, trace_base, seed, chain0,
-                                 d_tape, trace_l, d_out, d_props));
+      HIPCHK(c, mpp_launch_chain(a, c->spec, c->lanes, occ));
   }
   return 0;
 }
@@ -301,9 +302,9 @@ int ChainRun::launch_hbm() {
   c->hp.cap = c->cap; c->hp.cell_cap = c->cell_cap;
   DevParams hpp = c->hp;
   hpp.handover = 0;
-  const size_t lds = mpp_chain_hbm_lds_bytes(hbm_waves, sh.rb_rows);
-  HIPCHK(c, mpp_launch_chain_hbm(c->stream, hbm_waves, n_hbm, lds, &hpp, tiles, n_lds, until, trace_base, seed, chain0,
-                                 d_tape, trace_h, d_out, d_props, c->hbm_ws.p, stride));
+  ChainLaunch a = args();
+  a.grid = n_hbm; a.lds = mpp_chain_hbm_lds_bytes(hbm_waves, sh.rb_rows); a.P = &hpp; a.tile0 = n_lds; a.trace_tile = trace_h;
+  HIPCHK(c, mpp_launch_chain_hbm(a, hbm_waves, c->hbm_ws.p, stride));
   return 0;
 }
 
@@ -393,10 +394,12 @@ static int run_chain(mpp_ctx *c, int grid, int tile0, int64_t n_steps, uint64_t 
   // the row level of the birth CDF goes to LDS when it fits and the chain speculates (it shortens the slowest
   // wave of a round); throughput launches of one-wave chains keep their LDS for occupancy
   c->hp.rowbase_lds = (c->H <= 1024 && (c->lanes > 0 || c->spec > 1)) ? 1 : 0;
-  if ((c->hp.n_kernels > MPP_K_SPLIT || has_classic(c->hp.model)) && !(c->lanes == 0 && (c->spec == 1 || c->spec == 8)))
+  const ModelClass mc = model_class(c->hp);
+  if (mc.extended() && !(c->lanes == 0 && (c->spec == 1 || c->spec == 8)))
     return fail(c, -1, "the split / merge kernels and the classic image energies are built for spec_waves 1 or 8 with spec_lanes 0");
   ChainRun k{c, grid, tile0, n_steps, seed, chain0, d_tape, trace_tile, d_out, d_props, std::vector<int32_t>(grid), std::vector<int32_t>(grid),
              std::vector<uint8_t>(grid, 0), std::vector<uint8_t>(grid, 0), std::vector<long long>(grid), {}, std::vector<TileRef>(grid)};
+  k.mc = mc;
   if ((rc = k.decide_deep())) return rc;
   k.sh = launch_shape(c, c->hp.rowbase_lds != 0);
   mpp_launch_set_until(c->stream, c->d_tiles, tile0, grid, (long long)n_steps, c->until);

@@ -26,9 +26,9 @@
 //    The chain is bit-for-bit the sequential one for every SPEC.
 #pragma once
 #include "mpp_device.hpp"
+#include "mpp_layout.hpp"
 #include "mpp_prepass.hpp"
 
-#define STASH 32              // neighbour updates remembered per speculative step
 #define MPP_LDS_PARAMS_MIN_WAVES 4   // chains with at least this many waves read the parameter block from an LDS copy
 #define ERR_CELL_OVERFLOW 1
 #define ERR_POINT_OVERFLOW 2
@@ -52,130 +52,6 @@ __device__ unsigned long long g_strag[64];
 #define PROF_T0()
 #define PROF_ADD(i)
 #endif
-
-struct Rec {                  // one speculative step, fully evaluated
-  int kernel, tidx, tslot, has_rem, has_add, valid;
-  int ax, ay, rx, ry, pid, ncls;
-  int accepted, n_stash, gate_a, _pad;
-  int acls, _pad2;            // class of the proposed angle when it is a class edge (KEEP_EDGE_ANGLE), else unused
-  double as, ar, aa, aux0, aux1, u_acc, qf, qb, dE;
-  double hl, hw, ca, sa, rad, lin_a, ra0, ra1;   // derived data of the proposed point
-  double fwd, bwd, log_alpha;                    // filled only when the tile is traced
-};
-
-struct Lds {
-  double *s, *r, *a, *ca, *sa, *hl, *hw, *rad, *lin, *red0, *red1;
-  double *edges;              // [3][32] copy of the mark bin edges
-  double *trig;               // [2][32] cos / sin of (angle-class edge + pi/2): the corner trigonometry of a rectangle whose
-                              // angle was drawn from the class distribution (data-driven birth / transform) without a sincos
-  double *rowbase;            // [H+1] copy of the birth CDF's row level (H <= 1024), else nullptr
-  double *stash_v0, *stash_v1;
-  double *clip;               // [waves][CLIP_SLOTS][32] polygon buffers of the rectangle clipper
-  int *xy;
-  unsigned short *order, *cell_items, *cell_cnt, *stash_slot;
-  unsigned char *gate;
-  Rec *rec;
-  int *sh;                    // [0]=n [1]=err [2]=committed ; sh[4..5] = T (double)
-};
-
-#define ROWBASE_LDS_MAX 1024
-#define CLIP_SLOTS 4          // lanes of one wave that clip at the same time (the others take the next turn)
-__host__ __device__ inline size_t lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves) {
-  size_t b = 0;
-  b += (size_t)waves * CLIP_SLOTS * 32 * sizeof(double);
-  b += (size_t)11 * cap * sizeof(double);
-  b += (size_t)rowbase_n * sizeof(double);
-  b += (size_t)3 * MPP_NCLASS * sizeof(double);
-  b += (size_t)2 * MPP_NCLASS * sizeof(double);               // trig
-  b += (size_t)2 * spec * STASH * sizeof(double);
-  b += (size_t)cap * sizeof(int);
-  b += (size_t)cap * sizeof(unsigned short);                  // order
-  b += (size_t)ncell * cell_cap * sizeof(unsigned short);     // cell items
-  b += (size_t)ncell * sizeof(unsigned short);                // cell counts
-  b += (size_t)spec * STASH * sizeof(unsigned short);
-  b += (size_t)cap;                                           // gate
-  b = (b + 15) & ~(size_t)15;
-  b += (size_t)spec * sizeof(Rec);
-  b += 16 * sizeof(int);
-  return b + 64;
-}
-
-__device__ inline Lds carve(unsigned char *base, int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves) {
-  Lds L;
-  double *d = (double *)base;
-  L.s = d; d += cap; L.r = d; d += cap; L.a = d; d += cap; L.ca = d; d += cap; L.sa = d; d += cap;
-  L.hl = d; d += cap; L.hw = d; d += cap; L.rad = d; d += cap; L.lin = d; d += cap; L.red0 = d; d += cap;
-  L.red1 = d; d += cap;
-  L.edges = d; d += 3 * MPP_NCLASS;
-  L.trig = d; d += 2 * MPP_NCLASS;
-  L.rowbase = rowbase_n > 0 ? d : nullptr; d += rowbase_n;
-  L.stash_v0 = d; d += (size_t)spec * STASH; L.stash_v1 = d; d += (size_t)spec * STASH;
-  L.clip = d; d += (size_t)waves * CLIP_SLOTS * 32;
-  L.xy = (int *)d;
-  unsigned short *u = (unsigned short *)(L.xy + cap);
-  L.order = u; u += cap;
-  L.cell_items = u; u += (size_t)ncell * cell_cap;
-  L.cell_cnt = u; u += ncell;
-  L.stash_slot = u; u += (size_t)spec * STASH;
-  L.gate = (unsigned char *)u;
-  size_t off = (size_t)((unsigned char *)u + cap - base);
-  off = (off + 15) & ~(size_t)15;
-  L.rec = (Rec *)(base + off);
-  L.sh = (int *)(base + off + (size_t)spec * sizeof(Rec));
-  return L;
-}
-
-// ---- the HBM-state chain (mpp_sampler_hbm.hip): a chain that outgrows the LDS keeps everything that scales with its
-// capacity -- the 11 per-point double arrays, xy, order, gate, cell_items and cell_cnt -- in its own slice of a device
-// workspace (each array 256-B aligned); the per-step buffers (edges, trig, rowbase, the stash, clip, rec, sh) and the
-// staged parameter block stay in LDS, whose footprint then no longer depends on the capacity.
-#define HBM_ALIGN 256
-__host__ __device__ inline size_t hbm_align(size_t b) { return (b + HBM_ALIGN - 1) & ~(size_t)(HBM_ALIGN - 1); }
-__host__ __device__ inline size_t hbm_state_bytes(int cap, int ncell, int cell_cap) {
-  return 11 * hbm_align((size_t)cap * sizeof(double)) + hbm_align((size_t)cap * sizeof(int)) +
-         hbm_align((size_t)cap * sizeof(unsigned short)) + hbm_align((size_t)ncell * cell_cap * sizeof(unsigned short)) +
-         hbm_align((size_t)ncell * sizeof(unsigned short)) + hbm_align((size_t)cap);
-}
-__host__ __device__ inline size_t hbm_lds_bytes(int spec, int rowbase_n, int waves) {
-  size_t b = 0;
-  b += (size_t)waves * CLIP_SLOTS * 32 * sizeof(double);
-  b += (size_t)rowbase_n * sizeof(double);
-  b += (size_t)5 * MPP_NCLASS * sizeof(double);               // edges, trig
-  b += (size_t)2 * spec * STASH * sizeof(double);
-  b += (size_t)spec * STASH * sizeof(unsigned short);
-  b = (b + 15) & ~(size_t)15;
-  b += (size_t)spec * sizeof(Rec);
-  b += 16 * sizeof(int);
-  return b + 64;
-}
-__device__ inline Lds carve_hbm(unsigned char *lds, unsigned char *ws, int cap, int ncell, int cell_cap, int spec,
-                                int rowbase_n, int waves) {
-  Lds L;
-  const size_t dc = hbm_align((size_t)cap * sizeof(double));
-  L.s = (double *)ws; L.r = (double *)(ws + dc); L.a = (double *)(ws + 2 * dc); L.ca = (double *)(ws + 3 * dc);
-  L.sa = (double *)(ws + 4 * dc); L.hl = (double *)(ws + 5 * dc); L.hw = (double *)(ws + 6 * dc);
-  L.rad = (double *)(ws + 7 * dc); L.lin = (double *)(ws + 8 * dc); L.red0 = (double *)(ws + 9 * dc);
-  L.red1 = (double *)(ws + 10 * dc);
-  size_t o = 11 * dc;
-  L.xy = (int *)(ws + o); o += hbm_align((size_t)cap * sizeof(int));
-  L.order = (unsigned short *)(ws + o); o += hbm_align((size_t)cap * sizeof(unsigned short));
-  L.cell_items = (unsigned short *)(ws + o); o += hbm_align((size_t)ncell * cell_cap * sizeof(unsigned short));
-  L.cell_cnt = (unsigned short *)(ws + o); o += hbm_align((size_t)ncell * sizeof(unsigned short));
-  L.gate = ws + o;
-  double *d = (double *)lds;
-  L.edges = d; d += 3 * MPP_NCLASS;
-  L.trig = d; d += 2 * MPP_NCLASS;
-  L.rowbase = rowbase_n > 0 ? d : nullptr; d += rowbase_n;
-  L.stash_v0 = d; d += (size_t)spec * STASH; L.stash_v1 = d; d += (size_t)spec * STASH;
-  L.clip = d; d += (size_t)waves * CLIP_SLOTS * 32;
-  unsigned short *u = (unsigned short *)d;
-  L.stash_slot = u; u += (size_t)spec * STASH;
-  size_t off = (size_t)((unsigned char *)u - lds);
-  off = (off + 15) & ~(size_t)15;
-  L.rec = (Rec *)(lds + off);
-  L.sh = (int *)(lds + off + (size_t)spec * sizeof(Rec));
-  return L;
-}
 
 // the pair terms' parameters, read ONCE per launch into registers: inside the non-unrolled loops of eval_delta every
 // P->model.pair[p].field was a scalar load followed by a wait (the chain kernel is built without machine LICM)

@@ -1,7 +1,7 @@
 // mpp_chain_body.inc -- the body of the one-wave-per-step chain kernel, included INSIDE the kernel functions of its two
 // homes of the chain state: mpp_chain_kernel (mpp_sampler.hip, the whole state in the workgroup's LDS) and
 // mpp_chain_hbm_kernel (mpp_sampler_hbm.hip, MPP_STATE_HBM: the arrays that scale with the capacity in a per-chain slice
-// of device memory, see carve_hbm).  A textual include, not a function: as a __forceinline__ template called from the
+// of device memory, see hbm_state_layout in mpp_layout.hpp).  A textual include, not a function: as a __forceinline__ template called from the
 // kernel the same code compiled differently (a private copy of the parameter block, other register assignments in most
 // of the 40 instantiations), and the LDS kernels are meant to stay the code objects they were.
 // In scope: the kernel's parameters (Pv, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props;

@@ -149,15 +149,6 @@ static const char *chain_error_text(int e) {
   return e >= 1 && e <= 4 ? text[e - 1] : "unknown chain error";
 }
 
-static bool has_classic(const mpp_model &M, int *want_gradient = nullptr) {
-  bool any = false;
-  for (int k = 0; k < M.n_unit; ++k) {
-    if (M.unit[k].kind == MPP_U_CONTRAST) any = true;
-    if (M.unit[k].kind == MPP_U_GRADIENT) { any = true; if (want_gradient) *want_gradient = 1; }
-  }
-  return any;
-}
-
 // What the launches of a chain have in common, taken once from the context.
 struct LaunchShape {
   int waves;       // waves of a chain's workgroup (lane mode: 4)
@@ -168,13 +159,13 @@ struct LaunchShape {
 };
 static LaunchShape launch_shape(const mpp_ctx *c, bool rowbase_lds) {
   return LaunchShape{c->lanes > 0 ? 4 : c->spec, c->lanes > 0 ? 4 * c->lanes : c->spec, c->hp.nx * c->hp.ny,
-                     rowbase_lds ? c->H + 1 : 0, has_classic(c->hp.model) ? 1 : 0};
+                     rowbase_lds ? c->H + 1 : 0, model_class(c->hp).classic ? 1 : 0};
 }
 // dynamic + static LDS of a chain with one wave per step / in deep rounds of at most nmax steps: what has to fit a CU's 160 KB
 static size_t chain_lds_total(const LaunchShape &s, int cap, int cell_cap) {
   return mpp_chain_lds_bytes(cap, s.ncell, cell_cap, s.steps, s.rb_rows, s.waves) + mpp_chain_static_lds_bytes(s.waves);
 }
 static size_t deep_lds_total(const LaunchShape &s, int cap, int cell_cap, int nmax) {
-  return mpp_deep_lds_bytes(cap, s.ncell, cell_cap, s.rb_rows, s.waves, nmax, s.ext) + mpp_deep_static_lds_bytes(s.waves);
+  return mpp_deep_lds_bytes(cap, s.ncell, cell_cap, s.rb_rows, s.waves, nmax, s.ext) + mpp_chain_static_lds_bytes(s.waves);
 }
 static int doubled(int v, int limit) { return v * 2 > limit ? limit : v * 2; }

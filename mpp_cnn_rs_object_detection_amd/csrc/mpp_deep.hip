@@ -27,7 +27,6 @@
 #include "mpp_launch.hpp"
 
 #define DEEP_NMAX_LIMIT 256      // most steps of one round (deeper rounds commit no more: the first conflict ends them)
-#define DEEP_CLIST 192         // candidate neighbours a wave collects before it evaluates them (>= 64: one cell's entries fit)
 #ifdef MPP_DEEP_PROF
 // diagnostic build only (profiles/tools/build_deep_prof.sh): cycles of wave 0 per phase of a round, summed over the launch,
 // in stats[16 + 24 * wave + phase]
@@ -54,58 +53,6 @@
 #define DI_NBOV (1 << 24)    // ... of more than two neighbours (their positions are not all reported)
 #define DI_NB2 (1 << 26)     // ... of at least two neighbours
 #define DI_RESC (1 << 25)    // the evaluation re-reduced a neighbour: it looked two interaction ranges away
-
-struct DeepLds {
-  uint4 *info;                 // [nmax] (flags | slot, removed xy, added xy, cell coordinates) -- indexed by the step's offset in the round
-  uint4 *nb;                   // [nmax] positions (and circumradii, rounded up) of the (at most two) neighbours whose cached
-                               // reductions the step changes
-  double *st;                  // [nmax][5] ... and their new reductions (2 x 2 values, then the two slots as bits): a step that
-                               // commits writes them; only a step that changes more than two neighbours needs a second pass
-  uint4 *pw;                   // [nmax] Philox block 0 of the steps, in sorted order (queue rounds: lin_a and gate_a of the
-                               // step at that offset, see deep_park)
-  unsigned short *poff;        // [nmax] sorted position -> offset of the step in the round
-  unsigned short *tcnt;        // [WAVES][16] steps of each kernel type per wave
-  double *tring;               // [4 * nmax] temperature of step (offset & mask), filled two rounds ahead
-  unsigned long long *racc;    // [WAVES][3][64] per step of a wave: max of the overlaps / min of the alignments with the added point;
-                               // a candidate neighbour of the step has a non-finite energy (classic image energies only)
-  unsigned int *clist;         // [WAVES][DEEP_CLIST] (step << 16 | slot): the neighbours in range of a wave's steps, in order
-  unsigned char *ltab;         // [WAVES][128] the 3 x 3 blocks of cells a wave's steps look at (lane | 0x80: the added point's)
-};
-__host__ __device__ inline size_t deep_extra_bytes(int nmax, int waves, int ext) {
-  return (size_t)nmax * 16 + (size_t)4 * nmax * 8 + (size_t)waves * (2 + (ext ? 1 : 0)) * 64 * 8 + (size_t)waves * DEEP_CLIST * 4 + (size_t)nmax * 32 + (size_t)nmax * 40 +
-         (size_t)nmax * 2 + (size_t)waves * 16 * 2 + (size_t)waves * 128 + 64;
-}
-__host__ __device__ inline size_t deep_base_bytes(int cap, int ncell, int cell_cap, int rowbase_n, int waves) {
-  return (lds_bytes(cap, ncell, cell_cap, 0, rowbase_n, waves) + 15) & ~(size_t)15;
-}
-__device__ inline DeepLds deep_carve(unsigned char *base, int nmax, int waves, int ext) {
-  DeepLds D;
-  D.pw = (uint4 *)base; base += (size_t)nmax * 16;
-  D.tring = (double *)base; base += (size_t)4 * nmax * 8;
-  D.racc = (unsigned long long *)base; base += (size_t)waves * (2 + (ext ? 1 : 0)) * 64 * 8;
-  D.clist = (unsigned int *)base; base += (size_t)waves * DEEP_CLIST * 4;
-  D.info = (uint4 *)base; base += (size_t)nmax * 16;
-  D.nb = (uint4 *)base; base += (size_t)nmax * 16;
-  D.st = (double *)base; base += (size_t)nmax * 40;
-  D.poff = (unsigned short *)base; base += (size_t)nmax * 2;
-  D.tcnt = (unsigned short *)base; base += (size_t)waves * 16 * 2;
-  D.ltab = base;
-  return D;
-}
-
-template <bool IN_LDS>
-__device__ __forceinline__ const DevParams *deep_stage_params(const DevParams &Pv, int nthr) {
-  if constexpr (IN_LDS) {
-    __shared__ DevParams s_P;
-    const int *src = (const int *)&Pv;
-    int *dst = (int *)&s_P;
-    for (int i = threadIdx.x; i < (int)(sizeof(DevParams) / 4); i += nthr) dst[i] = src[i];
-    __syncthreads();
-    return &s_P;
-  } else {
-    return &Pv;
-  }
-}
 
 // ---- state mutation by ONE lane (energy_point_set.py:118-154); two steps that commit in the same round touch different
 // cells and slots
@@ -714,7 +661,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   static_assert(!QUE || (TAB && WAVES == 8), "the queues are dealt to eight waves");
   const bool by_type = (gain8 & 0x100) == 0;      // (bit 8 of the gain word: deal the sorted steps in blocks instead -- A/B tests)
   gain8 &= 0xff;
-  const DevParams *P = deep_stage_params<(WAVES >= MPP_LDS_PARAMS_MIN_WAVES)>(Pv, WAVE * WAVES);
+  const DevParams *P = stage_params<(WAVES >= MPP_LDS_PARAMS_MIN_WAVES)>(Pv, WAVE * WAVES);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int tile = tile0 + blockIdx.x;
   Chain c;
@@ -1375,21 +1322,16 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
 extern "C" size_t mpp_deep_lds_bytes(int cap, int ncell, int cell_cap, int rowbase_n, int waves, int nmax, int ext) {
   return deep_base_bytes(cap, ncell, cell_cap, rowbase_n, waves) + deep_extra_bytes(nmax, waves, ext);
 }
-extern "C" size_t mpp_deep_static_lds_bytes(int waves) {
-  return waves >= MPP_LDS_PARAMS_MIN_WAVES ? ((sizeof(DevParams) + 15) & ~(size_t)15) : 0;
-}
 
 template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false, int NCH = DEEP_NMAX_LIMIT / 64>
-static hipError_t launch_deep_d(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                                const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
-                                int trace_tile, mpp_step_out *out, mpp_proposal *props, int nmax, int fixed_depth, int gain8,
-                                unsigned long long *stats, const PreTab &pt) {
+static hipError_t launch_deep_d(const ChainLaunch &a, int nmax, int fixed_depth, int gain8, unsigned long long *stats,
+                                const PreTab &pt) {
   if (nmax > 64 * NCH) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0, until,
-                     trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, pt);
+  hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>), dim3(a.grid), dim3(WAVE * WAVES), a.lds, a.st, *a.P, a.tiles,
+                     a.tile0, a.until, a.trace_base, a.seed, a.chain0, a.trace_tile, a.out, a.props, nmax, fixed_depth, gain8, stats, pt);
   return hipGetLastError();
 }
 
@@ -1397,24 +1339,19 @@ static hipError_t launch_deep_d(hipStream_t st, int grid, size_t lds, const DevP
 // ext: a classic image energy among the unit terms (built for 1 and 8 waves, like the one-wave-per-step kernels)
 // pt: the launch's birth table (mpp_prepass.hip), or pt->word == nullptr: the chains draw their births themselves; with
 // pt->qoff, eight waves and the cost deal (gain8 without bit 8), the rounds take their steps from the table's queues
-extern "C" hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int grid, size_t lds, const DevParams *P,
-                                      const TileRef *tiles, int tile0, const long long *until, long long trace_base,
-                                      unsigned long long seed, unsigned int chain0, int trace_tile, mpp_step_out *out,
-                                      mpp_proposal *props, int nmax, int fixed_depth, int gain8, unsigned long long *stats, int ext,
-                                      const PreTab *pt) {
-  const bool diag = out || props, tab = pt->word != nullptr && !ext;
+// (a.tape is not read: deep rounds draw their proposals from Philox)
+extern "C" hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8,
+                                      unsigned long long *stats, int ext, const PreTab *pt) {
+  const bool diag = a.out || a.props, tab = pt->word != nullptr && !ext;
+  // GO_(W, O, X, T[, Q, N]): that instantiation, traced or not
+#define GO_(W, ...)                                                                                        \
+  return diag ? launch_deep_d<W, true, __VA_ARGS__>(a, nmax, fixed_depth, gain8, stats, *pt)               \
+              : launch_deep_d<W, false, __VA_ARGS__>(a, nmax, fixed_depth, gain8, stats, *pt)
   if (tab && pt->qoff != nullptr && waves == 8 && (gain8 & 0x100) == 0) {
     // the queue rounds keep two chunks of step reports per lane where the round has at most 128 steps (the default depth), four above
-#define GOQ_(N)                                                                                                                  \
-  return diag ? launch_deep_d<8, true, 2, false, true, true, N>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt) \
-              : launch_deep_d<8, false, 2, false, true, true, N>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
-    if (nmax <= 128) { GOQ_(2); }
-    GOQ_(DEEP_NMAX_LIMIT / 64);
-#undef GOQ_
+    if (nmax <= 128) { GO_(8, 2, false, true, true, 2); }
+    GO_(8, 2, false, true, true, DEEP_NMAX_LIMIT / 64);
   }
-#define GO_(W, O, X, T)                                                                                                   \
-  return diag ? launch_deep_d<W, true, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt) \
-              : launch_deep_d<W, false, O, X, T>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, trace_tile, out, props, nmax, fixed_depth, gain8, stats, *pt)
 #define GO(W, O, X) do { if (!(X) && tab) { GO_(W, O, false, true); } GO_(W, O, X, false); } while (0)
   if (ext) {
     switch (waves) {

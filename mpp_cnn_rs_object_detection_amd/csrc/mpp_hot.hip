@@ -24,13 +24,13 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_hot_kernel(const DevPara
 #include "mpp_chain_body.inc"
 }
 
-// lds: mpp_chain_lds_bytes of the launch (the layout is mpp_chain_kernel's); pt: a table with queues whose stride is below
-// 2^28 (every step's word then carries its queue position), built for exactly these chains at their current steps
-extern "C" hipError_t mpp_launch_hot(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                                     const long long *until, const PreTab *pt) {
+// a.lds: mpp_chain_lds_bytes of the launch (the layout is mpp_chain_kernel's: chain_layout of mpp_layout.hpp); pt: a table with
+// queues whose stride is below 2^28 (every step's word then carries its queue position), built for exactly these chains at
+// their current steps.  Of the bundle the kernel takes the parameter block, the tile table and the until table.
+extern "C" hipError_t mpp_launch_hot(const ChainLaunch &a, const PreTab *pt) {
   if (!pt->word || !pt->qent || pt->stride >= (1ll << 28)) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute((const void *)mpp_hot_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = hipFuncSetAttribute((const void *)mpp_hot_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_hot_kernel<8, 2>), dim3(grid), dim3(WAVE * 8), lds, st, *P, tiles, tile0, until, *pt);
+  hipLaunchKernelGGL((mpp_hot_kernel<8, 2>), dim3(a.grid), dim3(WAVE * 8), a.lds, a.st, *a.P, a.tiles, a.tile0, a.until, *pt);
   return hipGetLastError();
 }

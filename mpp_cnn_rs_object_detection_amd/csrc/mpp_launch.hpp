@@ -2,6 +2,7 @@
 // defines each and by the API files that call them: extern "C" symbols link whatever their prototype says, here a drift fails to compile.
 #pragma once
 #include <cstddef>
+#include <cstdlib>
 
 #include "mpp_device.hpp"
 #include "mpp_prepass.hpp"
@@ -9,27 +10,52 @@
 #define MPP_LDS_LIMIT (160 * 1024)                 // the LDS of a CU: what a chain's dynamic + static LDS has to fit
 #define MPP_DEDUPE_LDS_MAX (MPP_LDS_LIMIT - 256)   // the most the dedupe walk of mpp_merge_score may ask for (k_dedupe_tiles)
 
+// What every chain launch is given: ChainRun (mpp_api_chain.hip) fills one per round, the launchers pass it down to the
+// hipLaunchKernelGGL of the instantiation they pick, where the kernel takes the fields as its individual arguments.
+struct ChainLaunch {
+  hipStream_t st; int grid; size_t lds;          // the chains are tiles[tile0 .. tile0 + grid); lds: the kernel's dynamic LDS
+  const DevParams *P;                            // (host) the parameter block, passed by value
+  const TileRef *tiles; int tile0; const long long *until;
+  long long trace_base; unsigned long long seed; unsigned int chain0;
+  const mpp_proposal *tape;                      // replay: the proposals to take instead of Philox draws
+  int trace_tile; mpp_step_out *out; mpp_proposal *props;   // the tile whose steps are recorded (-1: none), and where
+};
+
+// Which kind of model runs: it decides the instantiation a launch takes and what run_chain may do with the chains.
+struct ModelClass {
+  bool fast;         // pair 0 = rectangle overlap / max, pair 1 = alignment / min -- both shipped setups: the FAST pair loops apply
+  bool classic;      // a classic image energy among the unit terms (energies/classics.py) ...
+  bool gradient;     // ... the gradient one among them
+  bool split_merge;  // split / merge kernels in the mixture
+  bool no_fast;      // MPP_NO_FAST=1: the launches that have the choice keep the generic pair loops
+  bool extended() const { return classic || split_merge; }   // the SM / EXT instantiations, built for 1 and 8 waves
+};
+static inline ModelClass model_class(const DevParams &P) {
+  static const bool no_fast = getenv("MPP_NO_FAST") != nullptr;
+  const mpp_model &M = P.model;
+  ModelClass m{};
+  m.fast = M.n_pair == 2 && M.pair[0].kind == MPP_P_OVERLAP && M.pair[0].reduce == MPP_REDUCE_MAX &&
+           M.pair[1].kind == MPP_P_ALIGN && M.pair[1].reduce == MPP_REDUCE_MIN;
+  for (int k = 0; k < M.n_unit; ++k) {
+    m.classic = m.classic || M.unit[k].kind == MPP_U_CONTRAST || M.unit[k].kind == MPP_U_GRADIENT;
+    m.gradient = m.gradient || M.unit[k].kind == MPP_U_GRADIENT;
+  }
+  m.split_merge = P.n_kernels > MPP_K_SPLIT;
+  m.no_fast = no_fast;
+  return m;
+}
+
 extern "C" {
 size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
-size_t mpp_chain_static_lds_bytes(int waves);
+size_t mpp_chain_static_lds_bytes(int waves);      // the staged parameter block: the same for every chain kernel
 size_t mpp_chain_hbm_state_bytes(int cap, int ncell, int cell_cap);
 size_t mpp_chain_hbm_lds_bytes(int spec, int rowbase_n);
-hipError_t mpp_launch_chain_hbm(hipStream_t st, int waves, int grid, size_t lds, const DevParams *P, const TileRef *tiles,
-                                int tile0, const long long *until, long long trace_base, unsigned long long seed,
-                                unsigned int chain0, const mpp_proposal *tape, int trace_tile, mpp_step_out *out,
-                                mpp_proposal *props, unsigned char *ws, size_t ws_stride);
-hipError_t mpp_launch_chain(hipStream_t st, int spec, int lanes, int occ, int grid, size_t lds, const DevParams *P,
-                            const TileRef *tiles, int tile0, const long long *until, long long trace_base,
-                            unsigned long long seed, unsigned int chain0, const mpp_proposal *tape, int trace_tile,
-                            mpp_step_out *out, mpp_proposal *props);
-hipError_t mpp_launch_hot(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                          const long long *until, const PreTab *pt);
 size_t mpp_deep_lds_bytes(int cap, int ncell, int cell_cap, int rowbase_n, int waves, int nmax, int ext);
-size_t mpp_deep_static_lds_bytes(int waves);
-hipError_t mpp_launch_deep(hipStream_t st, int waves, int occ, int grid, size_t lds, const DevParams *P, const TileRef *tiles,
-                           int tile0, const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
-                           int trace_tile, mpp_step_out *out, mpp_proposal *props, int nmax, int fixed_depth, int gain8,
+hipError_t mpp_launch_chain(const ChainLaunch &a, int spec, int lanes, int occ);
+hipError_t mpp_launch_chain_hbm(const ChainLaunch &a, int waves, unsigned char *ws, size_t ws_stride);
+hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8,
                            unsigned long long *stats, int ext, const PreTab *pt);
+hipError_t mpp_launch_hot(const ChainLaunch &a, const PreTab *pt);
 hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
                              const long long *until, unsigned long long seed, unsigned int chain0, int nblk, long long stride,
                              unsigned int *cnt, unsigned long long *total, unsigned int *qcnt, unsigned long long *qtot);

@@ -64,66 +64,50 @@ extern "C" void mpp_launch_set_until(hipStream_t st, const TileRef *tiles, int t
 extern "C" size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves) {
   return lds_bytes(cap, ncell, cell_cap, spec, rowbase_n, waves);
 }
-// static LDS a chain kernel with `waves` waves uses besides its dynamic allocation (the staged parameter block)
+// static LDS a chain kernel with `waves` waves uses besides its dynamic allocation (the staged parameter block of stage_params,
+// the same in mpp_chain_kernel, mpp_chain_hbm_kernel, mpp_hot_kernel and mpp_deep_kernel)
 extern "C" size_t mpp_chain_static_lds_bytes(int waves) {
   return waves >= MPP_LDS_PARAMS_MIN_WAVES ? ((sizeof(DevParams) + 15) & ~(size_t)15) : 0;
 }
 
 template <int WAVES, int LPW, bool DIAG, int OCC, bool SM, bool FAST = false>
-static hipError_t launch_spec_d(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                              const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
-                              const mpp_proposal *tape, int trace_tile, mpp_step_out *out, mpp_proposal *props) {
+static hipError_t launch_spec_d(const ChainLaunch &a) {
   hipError_t e = hipFuncSetAttribute((const void *)mpp_chain_kernel<WAVES, LPW, DIAG, OCC, SM, FAST>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_chain_kernel<WAVES, LPW, DIAG, OCC, SM, FAST>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0,
-                     until, trace_base, seed, chain0, tape, trace_tile, out, props);
+  hipLaunchKernelGGL((mpp_chain_kernel<WAVES, LPW, DIAG, OCC, SM, FAST>), dim3(a.grid), dim3(WAVE * WAVES), a.lds, a.st, *a.P, a.tiles,
+                     a.tile0, a.until, a.trace_base, a.seed, a.chain0, a.tape, a.trace_tile, a.out, a.props);
   return hipGetLastError();
 }
 template <int WAVES, int LPW>
-static hipError_t launch_spec(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                              const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
-                              const mpp_proposal *tape, int trace_tile, mpp_step_out *out, mpp_proposal *props,
-                              int occ) {
+static hipError_t launch_spec(const ChainLaunch &a, int occ) {
   constexpr int BASE = (WAVES + 3) / 4;      // waves per SIMD one workgroup needs anyway
-  const bool diag = tape || out || props;
-  bool classic = false;                      // a classic image energy among the unit terms (energies/classics.py)
-  for (int k = 0; k < P->model.n_unit; ++k)
-    classic = classic || P->model.unit[k].kind == MPP_U_CONTRAST || P->model.unit[k].kind == MPP_U_GRADIENT;
-  if (P->n_kernels > MPP_K_SPLIT || classic) {   // split / merge kernels in the mixture, or a classic image energy: the
-                                                 // extended instantiations, built for 1 and 8 waves
+  const bool diag = a.tape || a.out || a.props;
+  const ModelClass mc = model_class(*a.P);
+  if (mc.extended()) {                       // split / merge kernels in the mixture, or a classic image energy: the
+                                             // extended instantiations, built for 1 and 8 waves
     if constexpr (LPW == 0 && (WAVES == 1 || WAVES == 8)) {
-      if (diag) return launch_spec_d<WAVES, LPW, true, BASE, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
-      return launch_spec_d<WAVES, LPW, false, BASE, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
+      if (diag) return launch_spec_d<WAVES, LPW, true, BASE, true>(a);
+      return launch_spec_d<WAVES, LPW, false, BASE, true>(a);
     } else {
       return hipErrorNotSupported;
     }
   }
-  if (diag)
-    return launch_spec_d<WAVES, LPW, true, BASE, false>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
+  if (diag) return launch_spec_d<WAVES, LPW, true, BASE, false>(a);
   // the production launches of the shipped energy setups: pair loops specialised (FAST); MPP_NO_FAST=1 keeps the generic code
-  const mpp_model &M = P->model;
-  static const bool no_fast = getenv("MPP_NO_FAST") != nullptr;
-  const bool fast = !no_fast && M.n_pair == 2 && M.pair[0].kind == MPP_P_OVERLAP && M.pair[0].reduce == MPP_REDUCE_MAX &&
-                    M.pair[1].kind == MPP_P_ALIGN && M.pair[1].reduce == MPP_REDUCE_MIN;
   if constexpr (LPW == 0 && WAVES <= 8) {
-    if (fast) {
-      if (WAVES <= 4 && occ >= 2)
-        return launch_spec_d<WAVES, LPW, false, 2, false, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
-      return launch_spec_d<WAVES, LPW, false, BASE, false, true>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
+    if (mc.fast && !mc.no_fast) {
+      if (WAVES <= 4 && occ >= 2) return launch_spec_d<WAVES, LPW, false, 2, false, true>(a);
+      return launch_spec_d<WAVES, LPW, false, BASE, false, true>(a);
     }
   }
-  if (WAVES <= 4 && LPW == 0 && occ >= 2)
-    return launch_spec_d<WAVES, LPW, false, 2, false>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
-  return launch_spec_d<WAVES, LPW, false, BASE, false>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props);
+  if (WAVES <= 4 && LPW == 0 && occ >= 2) return launch_spec_d<WAVES, LPW, false, 2, false>(a);
+  return launch_spec_d<WAVES, LPW, false, BASE, false>(a);
 }
 
 // spec = steps evaluated per round; lanes = 0: one wave per step (spec waves); lanes > 0: 4 waves x lanes lanes
-extern "C" hipError_t mpp_launch_chain(hipStream_t st, int spec, int lanes, int occ, int grid, size_t lds,
-                                       const DevParams *P, const TileRef *tiles, int tile0, const long long *until,
-                                       long long trace_base, unsigned long long seed, unsigned int chain0, const mpp_proposal *tape,
-                                       int trace_tile, mpp_step_out *out, mpp_proposal *props) {
-#define GO(W, L) return launch_spec<W, L>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props, occ)
+extern "C" hipError_t mpp_launch_chain(const ChainLaunch &a, int spec, int lanes, int occ) {
+#define GO(W, L) return launch_spec<W, L>(a, occ)
   if (lanes == 0) {
     switch (spec) { case 1: GO(1, 0); case 2: GO(2, 0); case 4: GO(4, 0); case 8: GO(8, 0); case 16: GO(16, 0); }
   } else {

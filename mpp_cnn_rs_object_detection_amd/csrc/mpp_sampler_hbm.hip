@@ -1,5 +1,5 @@
 // mpp_sampler_hbm.hip -- the one-wave-per-step chain with its state in device memory, for the chains that outgrow a
-// CU's LDS (see run_chain in mpp_api_chain.hip for the routing, mpp_chain.hpp: carve_hbm for the layout and wave_lds_fence for
+// CU's LDS (see run_chain in mpp_api_chain.hip for the routing, mpp_layout.hpp: hbm_state_layout / hbm_lds_layout for the layout, mpp_chain.hpp: and wave_lds_fence for
 // the memory ordering).  Same body as mpp_chain_kernel (mpp_chain_body.inc), same Philox stream, same arithmetic: the
 // chain is the one an unlimited LDS would have run.
 #define MPP_STATE_HBM 1
@@ -20,31 +20,20 @@ __global__ __launch_bounds__(WAVE *WAVES, (WAVES + 3) / 4) void mpp_chain_hbm_ke
 }
 
 template <int WAVES, bool DIAG, bool SM>
-static hipError_t launch_hbm_d(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                               const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
-                               const mpp_proposal *tape, int trace_tile, mpp_step_out *out, mpp_proposal *props,
-                               unsigned char *ws, size_t ws_stride) {
+static hipError_t launch_hbm_d(const ChainLaunch &a, unsigned char *ws, size_t ws_stride) {
   hipError_t e = hipFuncSetAttribute((const void *)mpp_chain_hbm_kernel<WAVES, DIAG, SM>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((mpp_chain_hbm_kernel<WAVES, DIAG, SM>), dim3(grid), dim3(WAVE * WAVES), lds, st, *P, tiles, tile0,
-                     until, trace_base, seed, chain0, tape, trace_tile, out, props, ws, ws_stride);
+  hipLaunchKernelGGL((mpp_chain_hbm_kernel<WAVES, DIAG, SM>), dim3(a.grid), dim3(WAVE * WAVES), a.lds, a.st, *a.P, a.tiles, a.tile0,
+                     a.until, a.trace_base, a.seed, a.chain0, a.tape, a.trace_tile, a.out, a.props, ws, ws_stride);
   return hipGetLastError();
 }
 template <int WAVES>
-static hipError_t launch_hbm(hipStream_t st, int grid, size_t lds, const DevParams *P, const TileRef *tiles, int tile0,
-                             const long long *until, long long trace_base, unsigned long long seed, unsigned int chain0,
-                             const mpp_proposal *tape, int trace_tile, mpp_step_out *out, mpp_proposal *props,
-                             unsigned char *ws, size_t ws_stride) {
-  const bool diag = tape || out || props;
-  bool sm = P->n_kernels > MPP_K_SPLIT;      // split / merge kernels in the mixture, or a classic image energy
-  for (int k = 0; k < P->model.n_unit; ++k)
-    sm = sm || P->model.unit[k].kind == MPP_U_CONTRAST || P->model.unit[k].kind == MPP_U_GRADIENT;
-#define GO(D, S) return launch_hbm_d<WAVES, D, S>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props, ws, ws_stride)
-  if (sm) { if (diag) GO(true, true); GO(false, true); }
-  if (diag) GO(true, false);
-  GO(false, false);
-#undef GO
+static hipError_t launch_hbm(const ChainLaunch &a, unsigned char *ws, size_t ws_stride) {
+  const bool diag = a.tape || a.out || a.props;
+  if (model_class(*a.P).extended())          // split / merge kernels in the mixture, or a classic image energy
+    return diag ? launch_hbm_d<WAVES, true, true>(a, ws, ws_stride) : launch_hbm_d<WAVES, false, true>(a, ws, ws_stride);
+  return diag ? launch_hbm_d<WAVES, true, false>(a, ws, ws_stride) : launch_hbm_d<WAVES, false, false>(a, ws, ws_stride);
 }
 
 // bytes of one chain's workspace slice (a multiple of 256) and of the kernel's dynamic LDS
@@ -52,14 +41,8 @@ extern "C" size_t mpp_chain_hbm_state_bytes(int cap, int ncell, int cell_cap) { 
 extern "C" size_t mpp_chain_hbm_lds_bytes(int spec, int rowbase_n) { return hbm_lds_bytes(spec, rowbase_n, spec); }
 
 // waves: 1 (contexts with spec_waves 1) or 8 (every other context: speculation does not change the chain)
-extern "C" hipError_t mpp_launch_chain_hbm(hipStream_t st, int waves, int grid, size_t lds, const DevParams *P,
-                                           const TileRef *tiles, int tile0, const long long *until, long long trace_base,
-                                           unsigned long long seed, unsigned int chain0, const mpp_proposal *tape,
-                                           int trace_tile, mpp_step_out *out, mpp_proposal *props, unsigned char *ws,
-                                           size_t ws_stride) {
-  if (waves == 1)
-    return launch_hbm<1>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props, ws, ws_stride);
-  if (waves == 8)
-    return launch_hbm<8>(st, grid, lds, P, tiles, tile0, until, trace_base, seed, chain0, tape, trace_tile, out, props, ws, ws_stride);
+extern "C" hipError_t mpp_launch_chain_hbm(const ChainLaunch &a, int waves, unsigned char *ws, size_t ws_stride) {
+  if (waves == 1) return launch_hbm<1>(a, ws, ws_stride);
+  if (waves == 8) return launch_hbm<8>(a, ws, ws_stride);
   return hipErrorInvalidValue;
 }
