@@ -168,6 +168,11 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
   int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+__device__ __forceinline__ double shfl_d(double v, int lane) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __shfl((int)(b & 0xffffffffll), lane, WAVE), hi = __shfl((int)(b >> 32), lane, WAVE);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
 
 __device__ __forceinline__ int cell_coord(const Chain &c, int x) {
   return c.h.res_shift >= 0 ? (x >> c.h.res_shift) : (x / c.h.res_int);
@@ -192,6 +197,36 @@ __device__ __forceinline__ Rect load_rect(const Lds &L, int slot) {
   q.x = xy & 0xffff; q.y = (xy >> 16) & 0xffff;
   q.s = L.s[slot]; q.r = L.r[slot]; q.a = L.a[slot];
   return q;
+}
+// lane src's rectangle for the whole wave (scalar registers; src wave-uniform) / lane `lane`'s for this lane
+__device__ __forceinline__ Geo readlane_geo(const Geo &g, int src) {
+  Geo b;
+  b.x = __builtin_amdgcn_readlane(g.x, src); b.y = __builtin_amdgcn_readlane(g.y, src);
+  b.hl = readlane_d(g.hl, src); b.hw = readlane_d(g.hw, src);
+  b.ca = readlane_d(g.ca, src); b.sa = readlane_d(g.sa, src);
+  return b;
+}
+__device__ __forceinline__ Geo2 readlane_geo2(const Geo2 &g, int src) {
+  Geo2 b;
+  b.g = readlane_geo(g.g, src); b.rad = readlane_d(g.rad, src);
+  return b;
+}
+__device__ __forceinline__ Geo shfl_geo(const Geo &g, int lane) {
+  Geo b;
+  b.x = __shfl(g.x, lane, WAVE); b.y = __shfl(g.y, lane, WAVE);
+  b.hl = shfl_d(g.hl, lane); b.hw = shfl_d(g.hw, lane); b.ca = shfl_d(g.ca, lane); b.sa = shfl_d(g.sa, lane);
+  return b;
+}
+// corners of a pair for the wave clippers: subject (sx, sy) = the rectangle that comes first in the canonical order
+__device__ __forceinline__ void ordered_corners(bool u_first, const Geo &u, const Geo &v, double *sx, double *sy, double *cx,
+                                                double *cy) {
+  double ux[4], uy[4], vx[4], vy[4];
+  geo_corners(u, ux, uy); geo_corners(v, vx, vy);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    sx[i] = u_first ? ux[i] : vx[i]; sy[i] = u_first ? uy[i] : vy[i];
+    cx[i] = u_first ? vx[i] : ux[i]; cy[i] = u_first ? vy[i] : uy[i];
+  }
 }
 // is slot u ordered before the rectangle (vx,vy,vs,vr,va)?  marks are read only on coordinate ties
 __device__ __forceinline__ bool slot_first(const Lds &L, int u, const Geo &gu, int vx, int vy, double vs, double vr,
@@ -244,6 +279,33 @@ __device__ inline double clip_area_lds(double *buf, const double *sx, const doub
   }
   return 0.5 * fabs(s);
 }
+// One clipping edge (x0, y0) -> (x1, y1) of the two ballot clippers below.  A group of lanes holds one polygon: lane li
+// of the group owns vertex li of the na vertices in (ax, ay), the output positions in (bx, by) come from the group's part
+// of two ballots (the wave's ballot shifted right by `shift`, masked with `keep`).  Every vertex goes through exactly the
+// arithmetic of clip_area() / clip_area_lds().  Returns the new vertex count; the caller swaps the buffers and fences.
+__device__ __forceinline__ int clip_edge_stage(int li, int shift, unsigned long long keep, int na, double x0, double y0,
+                                               double x1, double y1, const double *ax, const double *ay, double *bx,
+                                               double *by) {
+  const double ex = x1 - x0, ey = y1 - y0;
+  const bool valid = li < na;
+  const int ii = valid ? li : 0, pi = ii == 0 ? (na > 0 ? na - 1 : 0) : ii - 1;
+  const double qx = ax[ii], qy = ay[ii], px = ax[pi], py = ay[pi];
+  const double sq = ex * (qy - y0) - ey * (qx - x0), sp = ex * (py - y0) - ey * (px - x0);
+  const bool e_int = valid && (sq >= 0 ? sp < 0 : sp >= 0), e_q = valid && sq >= 0;
+  const unsigned long long mi = (__ballot(e_int) >> shift) & keep, mq = (__ballot(e_q) >> shift) & keep;
+  const unsigned long long below = (1ull << li) - 1ull;
+  int off = __popcll(mi & below) + __popcll(mq & below);
+  if (e_int) {
+    if (off < 8) {
+      double t = sp / (sp - sq);
+      bx[off] = px + t * (qx - px); by[off] = py + t * (qy - py);
+    }
+    ++off;
+  }
+  if (e_q && off < 8) { bx[off] = qx; by[off] = qy; }
+  const int nb = __popcll(mi) + __popcll(mq);
+  return nb < 8 ? nb : 8;
+}
 // The same clipper with the whole wave on ONE polygon pair (uniform control flow required): lane i owns
 // vertex i of the current polygon, the output positions come from two ballots, the shoelace sum is accumulated in
 // vertex order.  Every vertex goes through exactly the arithmetic of clip_area()/clip_area_lds(), so the area is
@@ -258,30 +320,11 @@ __device__ inline double clip_area_wave(const Chain &c, const double *sx, const 
     ay[l] = l == 0 ? sy[0] : (l == 1 ? sy[1] : (l == 2 ? sy[2] : sy[3]));
   }
   wave_lds_fence();
-  const unsigned long long below = (1ull << c.lane) - 1ull;
   int na = 4;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     if (na <= 0) break;
-    const double x0 = cx[e], y0 = cy[e], x1 = cx[(e + 1) & 3], y1 = cy[(e + 1) & 3];
-    const double ex = x1 - x0, ey = y1 - y0;
-    const bool valid = c.lane < na;
-    const int ii = valid ? c.lane : 0, pi = ii == 0 ? na - 1 : ii - 1;
-    const double qx = ax[ii], qy = ay[ii], px = ax[pi], py = ay[pi];
-    const double sq = ex * (qy - y0) - ey * (qx - x0), sp = ex * (py - y0) - ey * (px - x0);
-    const bool e_int = valid && (sq >= 0 ? sp < 0 : sp >= 0), e_q = valid && sq >= 0;
-    const unsigned long long mi = __ballot(e_int), mq = __ballot(e_q);
-    int off = __popcll(mi & below) + __popcll(mq & below);
-    if (e_int) {
-      if (off < 8) {
-        double t = sp / (sp - sq);
-        bx[off] = px + t * (qx - px); by[off] = py + t * (qy - py);
-      }
-      ++off;
-    }
-    if (e_q && off < 8) { bx[off] = qx; by[off] = qy; }
-    int nb = __popcll(mi) + __popcll(mq);
-    na = nb < 8 ? nb : 8;
+    na = clip_edge_stage(c.lane, 0, ~0ull, na, cx[e], cy[e], cx[(e + 1) & 3], cy[(e + 1) & 3], ax, ay, bx, by);
     double *tx = ax, *ty = ay;
     ax = bx; ay = by; bx = tx; by = ty;
     wave_lds_fence();
@@ -300,9 +343,8 @@ __device__ inline double clip_area_wave(const Chain &c, const double *sx, const 
 __device__ inline double overlap_energy_chain(const Chain &c, const Geo &u, const Geo &v, bool u_first, double ru,
                                               double rv, double d2) {
   double A = geo_area(u), B = geo_area(v);
-  double mn = A < B ? A : B;
-  double reach = ru + rv;
-  bool need = !(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);
+  double mn;
+  bool need = pair_needs_clip(A, B, ru + rv, d2, &mn);
   double area = 0.0;
   unsigned long long m = __ballot(need);
   while (m) {
@@ -390,6 +432,122 @@ __device__ double rescan_lane(const Chain &c, int p, int u, const Geo2 &gu, int 
     }
   }
   return acc;
+}
+
+// The wave form of rescan_lane for the FAST model class (pair 0 = rectangle overlap / max, pair 1 = alignment / min), shared
+// by eval_delta<FAST> and the deep round's deep_delta: one source, so the eager and the deep chains agree bit for bit by
+// construction.  A neighbour lost the point that carried its extremum (its alignment minimum: 0.12 times per step; its
+// overlap maximum: rarely, often in crowded scenes) and the added point does not take over: re-reduce it over its own 3x3
+// cells.  Done in one lane (rescan_lane, what the generic instantiation does) this walk -- nine cells, dependent LDS reads
+// per entry, an inlined clipper -- cost ~50 VGPRs of pressure in the hottest region of the kernel (256 registers and spills
+// instead of ~200: 12 % of the speed) and ~2 000 cycles of one straggling wave.  Here the whole wave does it: the neighbour
+// is broadcast (scalar registers), lane 3k+e takes entry e of cell k (fuller cells: a flattened index space, 64 entries per
+// turn), overlaps that need clipping go through the wave-wide clipper one after the other, the extremum is collected with
+// ballots and readlanes.  Same values, same (exact) max / min: the same result as the in-lane walk.
+// Everything but c.lane and ag is wave-uniform.  us, bu: the neighbour's slot and rectangle; skip: the removed slot;
+// need0 / need1: which pair to re-reduce.  The added rectangle (has_add) is lane glane's ag, broadcast only inside the
+// branch that uses it (broadcast at the call it slows the deep round down: profiles/shared_rereduce.md); as_, ar_, aa_:
+// its marks.  *out0 / *out1: the new reductions (0.0 for a pair that was not asked for).
+__device__ __forceinline__ void rereduce_wave(const Chain &c, int us, const Geo2 &bu, int skip, bool need0, bool need1,
+                                              int maxd2_0, int maxd2_1, double rew, bool has_add, const Geo2 &ag, double as_,
+                                              double ar_, double aa_, int glane, double *out0, double *out1) {
+  const Lds &L = c.L;
+  const int ck = c.lane / 3, ce = c.lane - 3 * ck;
+  int uci, ucj;
+  cell_index(c, bu.g.x, bu.g.y, &uci, &ucj);
+  int cell2 = -1;
+  if (ck < 9) {
+    const int i = uci + ck / 3 - 1, j = ucj + ck % 3 - 1;
+    if (i >= 0 && i < c.h.nx && j >= 0 && j < c.h.ny) cell2 = j + i * c.h.ny;
+  }
+  const int cnt2 = cell2 >= 0 ? (int)L.cell_cnt[cell2] : 0;
+  const bool direct2 = __ballot(cnt2 > 3) == 0ull;
+  int M2 = WAVE;
+  if (!direct2) {
+    M2 = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M2 += __builtin_amdgcn_readlane(cnt2, 3 * k);
+  }
+  const double Au = geo_area(bu.g);
+  double acc0 = 0.0, acc1 = 0.0;                     // wave-uniform results
+  for (int base2 = 0; base2 < M2; base2 += WAVE) {
+    int it_base = cell2 * c.h.cell_cap, it_e = ce;
+    bool act2 = ce < cnt2;
+    if (!direct2) {
+      const int j = base2 + c.lane;
+      int lo = 0, my_lo = 0;
+      it_base = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const int cnt_k = __builtin_amdgcn_readlane(cnt2, 3 * k), cell_k = __builtin_amdgcn_readlane(cell2, 3 * k);
+        if (j >= lo && cnt_k > 0) { my_lo = lo; it_base = cell_k * c.h.cell_cap; }
+        lo += cnt_k;
+      }
+      act2 = j < M2;
+      it_e = j - my_lo;
+    }
+    const int w = act2 ? (int)L.cell_items[it_base + it_e] : 0;
+    if (act2 && (w == us || w == skip)) act2 = false;
+    int wx = 0, wy = 0, d2w = 0;
+    if (act2) {
+      const int wxy = L.xy[w];
+      wx = wxy & 0xffff; wy = (wxy >> 16) & 0xffff;
+      const int dx = bu.g.x - wx, dy = bu.g.y - wy;
+      d2w = dx * dx + dy * dy;
+    }
+    if (need1) {                                     // alignment, reduced with min
+      double v1 = 0.0;
+      if (act2 && d2w <= maxd2_1) v1 = 1.0 - fabs(bu.g.ca * L.ca[w] + bu.g.sa * L.sa[w]) - rew;
+      unsigned long long bm = __ballot(v1 < 0.0);
+      while (bm) {
+        const int l2 = __ffsll((long long)bm) - 1;
+        bm &= bm - 1;
+        acc1 = reduce2(MPP_REDUCE_MIN, acc1, readlane_d(v1, l2));
+      }
+    }
+    if (need0) {                                     // overlap, reduced with max
+      bool needc = act2 && d2w <= maxd2_0;
+      Geo gw;
+      gw.x = wx; gw.y = wy; gw.hl = gw.hw = gw.ca = gw.sa = 0.0;
+      double mn = 0.0;
+      bool uf = false;
+      if (needc) {
+        gw.hl = L.hl[w]; gw.hw = L.hw[w]; gw.ca = L.ca[w]; gw.sa = L.sa[w];
+        // (pair_needs_clip, written out: see profiles/shared_rereduce.md)
+        const double B = geo_area(gw), reach = bu.rad + L.rad[w], d2 = (double)d2w;
+        mn = Au < B ? Au : B;
+        needc = !(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);
+        if (needc) uf = slot_first(L, us, bu.g, wx, wy, L.s[w], L.r[w], L.a[w]);
+      }
+      unsigned long long m = __ballot(needc);
+      while (m) {
+        const int l2 = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const Geo bw = readlane_geo(gw, l2);
+        const bool u_first = __builtin_amdgcn_readlane((int)uf, l2) != 0;
+        const double mn2 = readlane_d(mn, l2);
+        double sx[4], sy[4], cx[4], cy[4];
+        ordered_corners(u_first, bu.g, bw, sx, sy, cx, cy);
+        acc0 = reduce2(MPP_REDUCE_MAX, acc0, clip_area_wave(c, sx, sy, cx, cy) / (mn2 + AREA_EPS));
+      }
+    }
+  }
+  if (has_add) {                                     // the proposed rectangle is a neighbour too (uniform)
+    const Geo2 ba = readlane_geo2(ag, glane);
+    const int dx = bu.g.x - ba.g.x, dy = bu.g.y - ba.g.y, d2a2 = dx * dx + dy * dy;
+    if (need1 && d2a2 <= maxd2_1)
+      acc1 = reduce2(MPP_REDUCE_MIN, acc1, 1.0 - fabs(bu.g.ca * ba.g.ca + bu.g.sa * ba.g.sa) - rew);
+    if (need0 && d2a2 <= maxd2_0) {
+      double mn;
+      if (pair_needs_clip(Au, geo_area(ba.g), bu.rad + ba.rad, (double)d2a2, &mn)) {
+        const bool u_first = slot_first(L, us, bu.g, ba.g.x, ba.g.y, as_, ar_, aa_);
+        double sx[4], sy[4], cx[4], cy[4];
+        ordered_corners(u_first, bu.g, ba.g, sx, sy, cx, cy);
+        acc0 = reduce2(MPP_REDUCE_MAX, acc0, clip_area_wave(c, sx, sy, cx, cy) / (mn + AREA_EPS));
+      }
+    }
+  }
+  *out0 = acc0; *out1 = acc1;
 }
 
 // dE of (remove slot `rem`, add rectangle `ar`) -- energy_graph.py:139-225 -- as
@@ -502,9 +660,7 @@ __device__ double eval_delta(const Chain &c, int ri, int rem, bool has_add, cons
       double mn = 0.0;                                                                                                    \
       bool uf = false;                                                                                                    \
       if (need) {                                                                                                         \
-        const double A = geo_area(gu.g), reach = gu.rad + gv.rad, d2 = (double)((which_) == 0 ? d2r : d2a);               \
-        mn = A < B ? A : B;                                                                                               \
-        need = !(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);                                              \
+        need = pair_needs_clip(geo_area(gu.g), B, gu.rad + gv.rad, (double)((which_) == 0 ? d2r : d2a), &mn);             \
         if (need) uf = slot_first(L, u, gu.g, rv.x, rv.y, rv.s, rv.r, rv.a);                                              \
       }                                                                                                                   \
       double val = 0.0;                                                                                                   \
@@ -512,19 +668,11 @@ __device__ double eval_delta(const Chain &c, int ri, int rem, bool has_add, cons
       while (m) {                                                                                                         \
         const int src = __ffsll((long long)m) - 1;                                                                        \
         m &= m - 1;                                                                                                       \
-        Geo bu;                                                                                                           \
-        bu.x = __builtin_amdgcn_readlane(gu.g.x, src); bu.y = __builtin_amdgcn_readlane(gu.g.y, src);                     \
-        bu.hl = readlane_d(gu.g.hl, src); bu.hw = readlane_d(gu.g.hw, src);                                               \
-        bu.ca = readlane_d(gu.g.ca, src); bu.sa = readlane_d(gu.g.sa, src);                                               \
+        const Geo bu = readlane_geo(gu.g, src);                                                                           \
         const bool u_first = __builtin_amdgcn_readlane((int)uf, src) != 0;                                                \
         DCOUNT(8, 1);                                                                                                     \
-        double ux[4], uy[4], vx[4], vy[4];                                                                                \
-        geo_corners(bu, ux, uy); geo_corners(gv.g, vx, vy);                                                               \
-        double sx[4], sy[4], cx[4], cy[4];          /* subject = the smaller rectangle in the canonical order */         \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                   \
-          sx[i] = u_first ? ux[i] : vx[i]; sy[i] = u_first ? uy[i] : vy[i];                                               \
-          cx[i] = u_first ? vx[i] : ux[i]; cy[i] = u_first ? vy[i] : uy[i];                                               \
-        }                                                                                                                 \
+        double sx[4], sy[4], cx[4], cy[4];                                                                                \
+        ordered_corners(u_first, bu, gv.g, sx, sy, cx, cy);                                                               \
         const double area = clip_area_wave(c, sx, sy, cx, cy);                                                            \
         if (c.lane == src) val = area / (mn + AREA_EPS);                                                                  \
       }                                                                                                                   \
@@ -592,15 +740,8 @@ __device__ double eval_delta(const Chain &c, int ri, int rem, bool has_add, cons
         MPP_PAIR_P(0, f0, true, resc0 = true);
         MPP_PAIR_P(1, f1, true, resc1 = true);
       }
-      // ---- a neighbour lost the point that carried its extremum (its alignment minimum: 0.12 times per step; its
-      // overlap maximum: rarely, often in crowded scenes) and the added point does not take over: re-reduce it over its
-      // own 3x3 cells.  Done in one lane (rescan_lane, what the generic instantiation does) this walk -- nine cells,
-      // dependent LDS reads per entry, an inlined clipper -- cost ~50 VGPRs of pressure in the hottest region of the
-      // kernel (256 registers and spills instead of ~200: 12 % of the speed) and ~2 000 cycles of one straggling wave.
-      // Here the whole wave does it: the neighbour is broadcast (scalar registers), lane 3k+e takes entry e of cell k
-      // (fuller cells: a flattened index space, 64 entries per turn), overlaps that need clipping go through the
-      // wave-wide clipper one after the other, the extremum is collected with ballots and readlanes.  Same values, same
-      // (exact) max / min: the same result as the in-lane walk.
+      // ---- a neighbour lost the point that carried its extremum and the added point does not take over: the whole wave
+      // re-reduces it over its own 3x3 cells (rereduce_wave), one such neighbour after the other
       unsigned long long rm = __ballot(resc0 || resc1);
 #ifdef MPP_PROFILE
       if (rm && c.lane == 0) c.L.sh[8 + (c.wave & 7)] = 1;
@@ -610,117 +751,10 @@ __device__ double eval_delta(const Chain &c, int ri, int rem, bool has_add, cons
         rm &= rm - 1;
         const bool need0 = __builtin_amdgcn_readlane((int)resc0, src) != 0, need1 = __builtin_amdgcn_readlane((int)resc1, src) != 0;
         const int us = __builtin_amdgcn_readlane(u, src);
-        Geo2 bu;                                           // the neighbour, wave-uniform
-        bu.g.x = __builtin_amdgcn_readlane(gu.g.x, src); bu.g.y = __builtin_amdgcn_readlane(gu.g.y, src);
-        bu.g.hl = readlane_d(gu.g.hl, src); bu.g.hw = readlane_d(gu.g.hw, src);
-        bu.g.ca = readlane_d(gu.g.ca, src); bu.g.sa = readlane_d(gu.g.sa, src); bu.rad = readlane_d(gu.rad, src);
-        int uci, ucj;
-        cell_index(c, bu.g.x, bu.g.y, &uci, &ucj);
-        int cell2 = -1;
-        if (ck < 9) {
-          const int i = uci + ck / 3 - 1, j = ucj + ck % 3 - 1;
-          if (i >= 0 && i < c.h.nx && j >= 0 && j < c.h.ny) cell2 = j + i * c.h.ny;
-        }
-        const int cnt2 = cell2 >= 0 ? (int)L.cell_cnt[cell2] : 0;
-        const bool direct2 = __ballot(cnt2 > 3) == 0ull;
-        int M2 = WAVE;
-        if (!direct2) {
-          M2 = 0;
-#pragma unroll
-          for (int k = 0; k < 9; ++k) M2 += __builtin_amdgcn_readlane(cnt2, 3 * k);
-        }
-        const double rew = f1.p0 != 0.0 ? 1.0 : 0.0, Au = geo_area(bu.g);
-        double acc0 = 0.0, acc1 = 0.0;                     // wave-uniform results
-        for (int base2 = 0; base2 < M2; base2 += WAVE) {
-          int it_base = cell2 * c.h.cell_cap, it_e = ce;
-          bool act2 = ce < cnt2;
-          if (!direct2) {
-            const int j = base2 + c.lane;
-            int lo = 0, my_lo = 0;
-            it_base = 0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) {
-              const int cnt_k = __builtin_amdgcn_readlane(cnt2, 3 * k), cell_k = __builtin_amdgcn_readlane(cell2, 3 * k);
-              if (j >= lo && cnt_k > 0) { my_lo = lo; it_base = cell_k * c.h.cell_cap; }
-              lo += cnt_k;
-            }
-            act2 = j < M2;
-            it_e = j - my_lo;
-          }
-          const int w = act2 ? (int)L.cell_items[it_base + it_e] : 0;
-          if (act2 && (w == us || w == rem)) act2 = false;
-          int wx = 0, wy = 0, d2w = 0;
-          if (act2) {
-            const int wxy = L.xy[w];
-            wx = wxy & 0xffff; wy = (wxy >> 16) & 0xffff;
-            const int dx = bu.g.x - wx, dy = bu.g.y - wy;
-            d2w = dx * dx + dy * dy;
-          }
-          if (need1) {                                     // alignment, reduced with min
-            double v1 = 0.0;
-            if (act2 && d2w <= f1.maxd2) v1 = 1.0 - fabs(bu.g.ca * L.ca[w] + bu.g.sa * L.sa[w]) - rew;
-            unsigned long long bm = __ballot(v1 < 0.0);
-            while (bm) {
-              const int l2 = __ffsll((long long)bm) - 1;
-              bm &= bm - 1;
-              acc1 = reduce2(MPP_REDUCE_MIN, acc1, readlane_d(v1, l2));
-            }
-          }
-          if (need0) {                                     // overlap, reduced with max
-            bool needc = act2 && d2w <= f0.maxd2;
-            Geo gw;
-            gw.x = wx; gw.y = wy; gw.hl = gw.hw = gw.ca = gw.sa = 0.0;
-            double mn = 0.0;
-            bool uf = false;
-            if (needc) {
-              gw.hl = L.hl[w]; gw.hw = L.hw[w]; gw.ca = L.ca[w]; gw.sa = L.sa[w];
-              const double B = geo_area(gw), reach = bu.rad + L.rad[w], d2 = (double)d2w;
-              mn = Au < B ? Au : B;
-              needc = !(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);
-              if (needc) uf = slot_first(L, us, bu.g, wx, wy, L.s[w], L.r[w], L.a[w]);
-            }
-            unsigned long long m = __ballot(needc);
-            while (m) {
-              const int l2 = __ffsll((long long)m) - 1;
-              m &= m - 1;
-              Geo bw;
-              bw.x = __builtin_amdgcn_readlane(gw.x, l2); bw.y = __builtin_amdgcn_readlane(gw.y, l2);
-              bw.hl = readlane_d(gw.hl, l2); bw.hw = readlane_d(gw.hw, l2);
-              bw.ca = readlane_d(gw.ca, l2); bw.sa = readlane_d(gw.sa, l2);
-              const bool u_first = __builtin_amdgcn_readlane((int)uf, l2) != 0;
-              const double mn2 = readlane_d(mn, l2);
-              double ux[4], uy[4], vx[4], vy[4];
-              geo_corners(bu.g, ux, uy); geo_corners(bw, vx, vy);
-              double sx[4], sy[4], cx[4], cy[4];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                sx[i] = u_first ? ux[i] : vx[i]; sy[i] = u_first ? uy[i] : vy[i];
-                cx[i] = u_first ? vx[i] : ux[i]; cy[i] = u_first ? vy[i] : uy[i];
-              }
-              acc0 = reduce2(MPP_REDUCE_MAX, acc0, clip_area_wave(c, sx, sy, cx, cy) / (mn2 + AREA_EPS));
-            }
-          }
-        }
-        if (has_add) {                                     // the proposed rectangle is a neighbour too (uniform)
-          const int dx = bu.g.x - ag.g.x, dy = bu.g.y - ag.g.y, d2a2 = dx * dx + dy * dy;
-          if (need1 && d2a2 <= f1.maxd2)
-            acc1 = reduce2(MPP_REDUCE_MIN, acc1, 1.0 - fabs(bu.g.ca * ag.g.ca + bu.g.sa * ag.g.sa) - rew);
-          if (need0 && d2a2 <= f0.maxd2) {
-            const double B = geo_area(ag.g), mn = Au < B ? Au : B, reach = bu.rad + ag.rad, d2 = (double)d2a2;
-            if (!(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001)) {
-              const bool u_first = slot_first(L, us, bu.g, ar.x, ar.y, ar.s, ar.r, ar.a);
-              double ux[4], uy[4], vx[4], vy[4];
-              geo_corners(bu.g, ux, uy); geo_corners(ag.g, vx, vy);
-              double sx[4], sy[4], cx[4], cy[4];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                sx[i] = u_first ? ux[i] : vx[i]; sy[i] = u_first ? uy[i] : vy[i];
-                cx[i] = u_first ? vx[i] : ux[i]; cy[i] = u_first ? vy[i] : uy[i];
-              }
-              acc0 = reduce2(MPP_REDUCE_MAX, acc0, clip_area_wave(c, sx, sy, cx, cy) / (mn + AREA_EPS));
-            }
-          }
-        }
+        const Geo2 bu = readlane_geo2(gu, src);            // the neighbour, wave-uniform
+        double acc0, acc1;
+        rereduce_wave(c, us, bu, rem, need0, need1, f0.maxd2, f1.maxd2, f1.p0 != 0.0 ? 1.0 : 0.0, has_add, ag, ar.s, ar.r, ar.a,
+                      src, &acc0, &acc1);
         if (c.lane == src) {
           if (need0) newv[0] = acc0;
           if (need1) newv[1] = acc1;

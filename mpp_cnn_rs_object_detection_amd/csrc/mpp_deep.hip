@@ -103,11 +103,6 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
   return v;
 }
-__device__ __forceinline__ double shfl_d(double v, int lane) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __shfl((int)(b & 0xffffffffll), lane, WAVE), hi = __shfl((int)(b >> 32), lane, WAVE);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 // clip_area_wave() for up to CLIP_SLOTS rectangle pairs at once: the wave works in groups of 16 lanes, lane li < 8 of a group
 // owns vertex li of its group's polygon (the group's two polygon buffers are those of one clip slot).  Every vertex goes
@@ -125,29 +120,10 @@ __device__ __forceinline__ double clip_area_groups(const Chain &c, bool gact, co
     ay[li] = li == 0 ? sy[0] : (li == 1 ? sy[1] : (li == 2 ? sy[2] : sy[3]));
   }
   wave_lds_fence();
-  const unsigned int belowg = (1u << li) - 1u;
   int na = gact ? 4 : 0;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const double x0 = cx[e], y0 = cy[e], x1 = cx[(e + 1) & 3], y1 = cy[(e + 1) & 3];
-    const double ex = x1 - x0, ey = y1 - y0;
-    const bool valid = li < na;
-    const int ii = valid ? li : 0, pi = ii == 0 ? (na > 0 ? na - 1 : 0) : ii - 1;
-    const double qx = ax[ii], qy = ay[ii], px = ax[pi], py = ay[pi];
-    const double sq = ex * (qy - y0) - ey * (qx - x0), sp = ex * (py - y0) - ey * (px - x0);
-    const bool e_int = valid && (sq >= 0 ? sp < 0 : sp >= 0), e_q = valid && sq >= 0;
-    const unsigned int mi = (unsigned int)(__ballot(e_int) >> (16 * g)) & 0xffffu, mq = (unsigned int)(__ballot(e_q) >> (16 * g)) & 0xffffu;
-    int off = __popc(mi & belowg) + __popc(mq & belowg);
-    if (e_int) {
-      if (off < 8) {
-        double t = sp / (sp - sq);
-        bx[off] = px + t * (qx - px); by[off] = py + t * (qy - py);
-      }
-      ++off;
-    }
-    if (e_q && off < 8) { bx[off] = qx; by[off] = qy; }
-    const int nb = __popc(mi) + __popc(mq);
-    na = nb < 8 ? nb : 8;
+    na = clip_edge_stage(li, 16 * g, 0xffffull, na, cx[e], cy[e], cx[(e + 1) & 3], cy[(e + 1) & 3], ax, ay, bx, by);
     double *tx = ax, *ty = ay;
     ax = bx; ay = by; bx = tx; by = ty;
     wave_lds_fence();
@@ -177,9 +153,10 @@ __device__ __forceinline__ double clip_area_groups(const Chain &c, bool gact, co
 //      eval_delta sums in;
 //   2  the list goes to the lanes, 64 (step, neighbour) pairs at a time: the neighbour's geometry and cached reductions from
 //      LDS, the step's added rectangle from its leader's registers (ds_bpermute); rectangle clips and the re-reduction of a
-//      neighbour that loses its extremum are done by the whole wave, one after the other, as in eval_delta<FAST>; the few
-//      neighbours whose energy changes are added to their step's sum in list order; the reductions of the added point
-//      itself (max / min: order-free) are LDS atomics on the bit patterns.
+//      neighbour that loses its extremum are done by the whole wave, one after the other, as in eval_delta<FAST> (the
+//      re-reduction is the function it calls, rereduce_wave of mpp_chain.hpp); the few neighbours whose energy changes are
+//      added to their step's sum in list order; the reductions of the added point itself (max / min: order-free) are LDS
+//      atomics on the bit patterns.
 // `apply` (wave-uniform): the changed reductions are written to the caches (the second pass of a step that commits).
 // Model: pair 0 = rectangle overlap / max, pair 1 = alignment / min (FAST).
 template <bool EXT>
@@ -341,9 +318,7 @@ __device__ __forceinline__ void deep_delta(const Chain &c, const DeepLds &D, boo
           double mn = 0.0;
           bool uf = false;
           if (need) {
-            const double B = geo_area(gv.g), reach = gu.rad + gv.rad, d2 = (double)(which == 0 ? d2r : d2a);
-            mn = Au < B ? Au : B;
-            need = !(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);
+            need = pair_needs_clip(Au, geo_area(gv.g), gu.rad + gv.rad, (double)(which == 0 ? d2r : d2a), &mn);
             if (need) {
               if (which == 0) uf = slot_first(L, u, gu.g, gv.g.x, gv.g.y, L.s[srem], L.r[srem], L.a[srem]);
               else uf = slot_first(L, u, gu.g, gv.g.x, gv.g.y, sa_s, sa_r, sa_a);
@@ -362,20 +337,10 @@ __device__ __forceinline__ void deep_delta(const Chain &c, const DeepLds &D, boo
             }
             const bool gact = my_src >= 0;
             const int sl = gact ? my_src : 0;
-            Geo bu, bv;
-            bu.x = __shfl(gu.g.x, sl, WAVE); bu.y = __shfl(gu.g.y, sl, WAVE);
-            bu.hl = shfl_d(gu.g.hl, sl); bu.hw = shfl_d(gu.g.hw, sl); bu.ca = shfl_d(gu.g.ca, sl); bu.sa = shfl_d(gu.g.sa, sl);
-            bv.x = __shfl(gv.g.x, sl, WAVE); bv.y = __shfl(gv.g.y, sl, WAVE);
-            bv.hl = shfl_d(gv.g.hl, sl); bv.hw = shfl_d(gv.g.hw, sl); bv.ca = shfl_d(gv.g.ca, sl); bv.sa = shfl_d(gv.g.sa, sl);
+            const Geo bu = shfl_geo(gu.g, sl), bv = shfl_geo(gv.g, sl);
             const bool u_first = __shfl((int)uf, sl, WAVE) != 0;
-            double ux[4], uy[4], vx[4], vy[4];
-            geo_corners(bu, ux, uy); geo_corners(bv, vx, vy);
-            double sx[4], sy[4], cx[4], cy[4];          // subject = the smaller rectangle in the canonical order
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              sx[q] = u_first ? ux[q] : vx[q]; sy[q] = u_first ? uy[q] : vy[q];
-              cx[q] = u_first ? vx[q] : ux[q]; cy[q] = u_first ? vy[q] : uy[q];
-            }
+            double sx[4], sy[4], cx[4], cy[4];
+            ordered_corners(u_first, bu, bv, sx, sy, cx, cy);
             const double area = clip_area_groups(c, gact, sx, sy, cx, cy);
             const double mine_ = shfl_d(area, (rank & (CLIP_SLOTS - 1)) << 4);
             if (need && rank < CLIP_SLOTS) { val = mine_ / (mn + AREA_EPS); need = false; }
@@ -408,9 +373,8 @@ __device__ __forceinline__ void deep_delta(const Chain &c, const DeepLds &D, boo
           }
         }
         // -- a neighbour lost the point that carried its extremum and the added point does not take over: the wave
-        //    re-reduces it over its own 3 x 3 cells (lane 3k+e on entry e of cell k; fuller cells: 64 entries per turn)
+        //    re-reduces it over its own 3 x 3 cells (rereduce_wave, the function eval_delta<FAST> calls)
         unsigned long long rm = __ballot(resc0 || resc1);
-        const int ck = c.lane / 3, ce = c.lane - 3 * ck;
         while (rm) {
           const int src = __ffsll((long long)rm) - 1;
           rm &= rm - 1;
@@ -419,120 +383,10 @@ __device__ __forceinline__ void deep_delta(const Chain &c, const DeepLds &D, boo
           if (c.lane == is) nresc += 1;
           const int rem_s = __builtin_amdgcn_readlane(srem, src);              // (the neighbour lost a removed point: has_rem)
           const bool ha_s = __builtin_amdgcn_readlane((int)s_ha, src) != 0;
-          Geo2 bu, ba;                                       // the neighbour and its step's added rectangle, wave-uniform
-          bu.g.x = __builtin_amdgcn_readlane(gu.g.x, src); bu.g.y = __builtin_amdgcn_readlane(gu.g.y, src);
-          bu.g.hl = readlane_d(gu.g.hl, src); bu.g.hw = readlane_d(gu.g.hw, src);
-          bu.g.ca = readlane_d(gu.g.ca, src); bu.g.sa = readlane_d(gu.g.sa, src); bu.rad = readlane_d(gu.rad, src);
-          ba.g.x = __builtin_amdgcn_readlane(ag.g.x, src); ba.g.y = __builtin_amdgcn_readlane(ag.g.y, src);
-          ba.g.hl = readlane_d(ag.g.hl, src); ba.g.hw = readlane_d(ag.g.hw, src);
-          ba.g.ca = readlane_d(ag.g.ca, src); ba.g.sa = readlane_d(ag.g.sa, src); ba.rad = readlane_d(ag.rad, src);
-          int uci, ucj;
-          cell_index(c, bu.g.x, bu.g.y, &uci, &ucj);
-          int cell2 = -1;
-          if (ck < 9) {
-            const int ii = uci + ck / 3 - 1, jj = ucj + ck % 3 - 1;
-            if (ii >= 0 && ii < c.h.nx && jj >= 0 && jj < c.h.ny) cell2 = jj + ii * c.h.ny;
-          }
-          const int cnt2 = cell2 >= 0 ? (int)L.cell_cnt[cell2] : 0;
-          const bool direct2 = __ballot(cnt2 > 3) == 0ull;
-          int M2 = WAVE;
-          if (!direct2) {
-            M2 = 0;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) M2 += __builtin_amdgcn_readlane(cnt2, 3 * k);
-          }
-          const double Aus = geo_area(bu.g);
-          double acc0 = 0.0, acc1 = 0.0;                     // wave-uniform results
-          for (int base2 = 0; base2 < M2; base2 += WAVE) {
-            int it_base = cell2 * c.h.cell_cap, it_e = ce;
-            bool act2 = ce < cnt2;
-            if (!direct2) {
-              const int jx = base2 + c.lane;
-              int lo = 0, my_lo = 0;
-              it_base = 0;
-#pragma unroll
-              for (int k = 0; k < 9; ++k) {
-                const int cnt_k = __builtin_amdgcn_readlane(cnt2, 3 * k), cell_k = __builtin_amdgcn_readlane(cell2, 3 * k);
-                if (jx >= lo && cnt_k > 0) { my_lo = lo; it_base = cell_k * c.h.cell_cap; }
-                lo += cnt_k;
-              }
-              act2 = jx < M2;
-              it_e = jx - my_lo;
-            }
-            const int w = act2 ? (int)L.cell_items[it_base + it_e] : 0;
-            if (act2 && (w == us || w == rem_s)) act2 = false;
-            int wx = 0, wy = 0, d2w = 0;
-            if (act2) {
-              const int wxy = L.xy[w];
-              wx = wxy & 0xffff; wy = (wxy >> 16) & 0xffff;
-              const int dx = bu.g.x - wx, dy = bu.g.y - wy;
-              d2w = dx * dx + dy * dy;
-            }
-            if (need1) {                                     // alignment, reduced with min
-              double v1 = 0.0;
-              if (act2 && d2w <= maxd2_1) v1 = 1.0 - fabs(bu.g.ca * L.ca[w] + bu.g.sa * L.sa[w]) - rew;
-              unsigned long long bm = __ballot(v1 < 0.0);
-              while (bm) {
-                const int l2 = __ffsll((long long)bm) - 1;
-                bm &= bm - 1;
-                acc1 = reduce2(MPP_REDUCE_MIN, acc1, readlane_d(v1, l2));
-              }
-            }
-            if (need0) {                                     // overlap, reduced with max
-              bool needc = act2 && d2w <= maxd2_0;
-              Geo gw;
-              gw.x = wx; gw.y = wy; gw.hl = gw.hw = gw.ca = gw.sa = 0.0;
-              double mn = 0.0;
-              bool uf = false;
-              if (needc) {
-                gw.hl = L.hl[w]; gw.hw = L.hw[w]; gw.ca = L.ca[w]; gw.sa = L.sa[w];
-                const double B = geo_area(gw), reach = bu.rad + L.rad[w], d2 = (double)d2w;
-                mn = Aus < B ? Aus : B;
-                needc = !(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);
-                if (needc) uf = slot_first(L, us, bu.g, wx, wy, L.s[w], L.r[w], L.a[w]);
-              }
-              unsigned long long m = __ballot(needc);
-              while (m) {
-                const int l2 = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                Geo bw;
-                bw.x = __builtin_amdgcn_readlane(gw.x, l2); bw.y = __builtin_amdgcn_readlane(gw.y, l2);
-                bw.hl = readlane_d(gw.hl, l2); bw.hw = readlane_d(gw.hw, l2);
-                bw.ca = readlane_d(gw.ca, l2); bw.sa = readlane_d(gw.sa, l2);
-                const bool u_first = __builtin_amdgcn_readlane((int)uf, l2) != 0;
-                const double mn2 = readlane_d(mn, l2);
-                double ux[4], uy[4], vx[4], vy[4];
-                geo_corners(bu.g, ux, uy); geo_corners(bw, vx, vy);
-                double sx[4], sy[4], cx[4], cy[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  sx[q] = u_first ? ux[q] : vx[q]; sy[q] = u_first ? uy[q] : vy[q];
-                  cx[q] = u_first ? vx[q] : ux[q]; cy[q] = u_first ? vy[q] : uy[q];
-                }
-                acc0 = reduce2(MPP_REDUCE_MAX, acc0, clip_area_wave(c, sx, sy, cx, cy) / (mn2 + AREA_EPS));
-              }
-            }
-          }
-          if (ha_s) {                                        // the proposed rectangle is a neighbour too (uniform)
-            const int dx = bu.g.x - ba.g.x, dy = bu.g.y - ba.g.y, d2a2 = dx * dx + dy * dy;
-            if (need1 && d2a2 <= maxd2_1)
-              acc1 = reduce2(MPP_REDUCE_MIN, acc1, 1.0 - fabs(bu.g.ca * ba.g.ca + bu.g.sa * ba.g.sa) - rew);
-            if (need0 && d2a2 <= maxd2_0) {
-              const double B = geo_area(ba.g), mn = Aus < B ? Aus : B, reach = bu.rad + ba.rad, d2 = (double)d2a2;
-              if (!(mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001)) {
-                const bool u_first = slot_first(L, us, bu.g, ba.g.x, ba.g.y, readlane_d(a_s, is), readlane_d(a_r, is), readlane_d(a_a, is));
-                double ux[4], uy[4], vx[4], vy[4];
-                geo_corners(bu.g, ux, uy); geo_corners(ba.g, vx, vy);
-                double sx[4], sy[4], cx[4], cy[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  sx[q] = u_first ? ux[q] : vx[q]; sy[q] = u_first ? uy[q] : vy[q];
-                  cx[q] = u_first ? vx[q] : ux[q]; cy[q] = u_first ? vy[q] : uy[q];
-                }
-                acc0 = reduce2(MPP_REDUCE_MAX, acc0, clip_area_wave(c, sx, sy, cx, cy) / (mn + AREA_EPS));
-              }
-            }
-          }
+          const Geo2 bu = readlane_geo2(gu, src);              // the neighbour, wave-uniform
+          double acc0, acc1;
+          rereduce_wave(c, us, bu, rem_s, need0, need1, maxd2_0, maxd2_1, rew, ha_s, ag, readlane_d(a_s, is), readlane_d(a_r, is),
+                        readlane_d(a_a, is), src, &acc0, &acc1);
           if (c.lane == src) {
             if (need0) nv0 = acc0;
             if (need1) nv1 = acc1;

@@ -168,14 +168,17 @@ __device__ __forceinline__ bool rect_less(int ax, int ay, double as, double ar, 
 #ifdef MPP_PROFILE
 __device__ unsigned long long g_clip_count;
 #endif
+// does the pair (areas A, B; reach = sum of the circumscribed radii; d2 = squared centre distance) need a clip?  Not when
+// the smaller area *mn is degenerate or the circumscribed circles are apart: the overlap is 0 then.
+__device__ __forceinline__ bool pair_needs_clip(double A, double B, double reach, double d2, double *mn) {
+  *mn = A < B ? A : B;
+  return !(*mn < DEGENERATE_AREA) && !(d2 > reach * reach * 1.0000001);
+}
 // RectangleOverlapEnergy (prior_energies.py:11-24); `u_first` tells whether u is the subject;
 // ru, rv: circumscribed-circle radii, d2: squared centre distance
 __device__ inline double overlap_energy_r(const Geo &u, const Geo &v, bool u_first, double ru, double rv, double d2) {
-  double A = geo_area(u), B = geo_area(v);
-  double mn = A < B ? A : B;
-  if (mn < DEGENERATE_AREA) return 0.0;
-  double reach = ru + rv;
-  if (d2 > reach * reach * 1.0000001) return 0.0;                  // circumscribed circles apart
+  double mn;
+  if (!pair_needs_clip(geo_area(u), geo_area(v), ru + rv, d2, &mn)) return 0.0;
 #ifdef MPP_PROFILE
   atomicAdd(&g_clip_count, 1ull);
 #endif
