@@ -251,12 +251,17 @@ int mpp_last_kernel_ms(mpp_ctx *ctx, double *ms);
 
 /* score-map epilogue of the two U-Nets (position_net/pos_net_model.py:186-200,338-346,
  * torch_div.py:8-43; shape_net/shape_net_model.py:139-141): all device pointers.
- * pos_out: [3][ldh][ldw] (vec0, vec1, mask logit; the padded output, whose top-left H x W region is used) -> det [H][W];
- * logits: [32][ldh][ldw] of one mark head -> marks [H][W][32] (16-byte aligned), softmax over the 32 classes.
- * Each is its window form (mpp_*_win below) with the window equal to the crop and a dense destination. */
-int mpp_posnet_epilogue(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *pos_out, double div_w,
-                        double div_b, float *det);
-int mpp_shapenet_epilogue(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *logits, float *marks);
+ * pos_out: [3][ldh][ldw] (vec0, vec1, mask logit; the padded output, whose top-left H x W region, the crop, is used) -> det;
+ * logits: [32][ldh][ldw] of one mark head -> marks [..][32] (16-byte aligned), softmax over the 32 classes.
+ * Every epilogue has one entry point, a window form, for a forward that walks a large image in crops: H x W is the crop's
+ * extent (it decides where the divergence is one-sided), (wx0, wy0, wh x ww) the window in crop coordinates; det / marks point
+ * to the window's first pixel in a map whose rows are ld_det / ld_marks pixels apart.  The whole crop is the window
+ * (0, 0, H x W), into a dense map with ld = W.  A pixel's result does not depend on the window, bit for bit; nothing outside it
+ * is written.  A window outside the crop or ld < ww: -1 and a message. */
+int mpp_posnet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
+                            int wx0, int wy0, int wh, int ww, float *det, int ld_det);
+int mpp_shapenet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0, int wh, int ww,
+                              float *marks, int ld_marks);
 /* epilogue of one convolution of a DoubleConv block (model_parts/unet/unet_parts.py:12-31), in place on the
  * convolution's output x [planes][hw] (NCHW, plane p = channel p % C; float32 or bfloat16, device pointers):
  * x <- max(0, x * scale[c] + shift[c]) with scale = gamma / sqrt(var + eps) and
@@ -265,12 +270,12 @@ int mpp_affine_relu(mpp_ctx *ctx, void *x, int planes, int C, int64_t hw, int el
                     const float *shift);
 
 /* The two epilogues above on channels-last network outputs: pos_out [ldh][ldw][3], logits [ldh][ldw][32], elements
- * float32 (elem_bytes 4) or bfloat16 (2), device pointers; same arithmetic and outputs (det [H][W], marks [H][W][32]
- * float32).  A pixel's 32 logits are contiguous here, so the softmax is one coalesced pass with no transpose.
- * Each is its window form (mpp_*_nhwc_win below) with the window equal to the crop and a dense destination. */
-int mpp_posnet_epilogue_nhwc(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
-                             double div_b, float *det);
-int mpp_shapenet_epilogue_nhwc(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, float *marks);
+ * float32 (elem_bytes 4) or bfloat16 (2), device pointers; same arithmetic, windows and outputs (det, marks float32).  A
+ * pixel's 32 logits are contiguous here, so the softmax is one coalesced pass with no transpose. */
+int mpp_posnet_epilogue_nhwc_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
+                                 double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det);
+int mpp_shapenet_epilogue_nhwc_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, int wx0, int wy0,
+                                   int wh, int ww, float *marks, int ld_marks);
 
 /* Channels-last (NHWC) glue between two convolutions of the U-Nets, ONE pass over the activation (device pointers,
  * float32 or bfloat16 elements; in_bytes / out_bytes = 4 or 2):
@@ -301,25 +306,10 @@ int mpp_conv3x3_stem(mpp_ctx *ctx, const float *x, int H, int W, const float *wp
 
 /* ShapeNet's three 1x1 heads, their biases and the softmax in one pass (model_parts/shape_net.py:12-46,
  * shape_net_model.py's inference softmax): h [ldh][ldw][32] float32 channels-last (the backbone's output) ->
- * marks_* [H][W][32] = softmax_c(sum_i w[k][c][i] * h[i] + b[k][c]), k = size, ratio, angle; w [3][32 classes][32 in],
- * b [3][32].  Replaces three library convolutions + bias adds + mpp_shapenet_epilogue_nhwc (same values up to float32
- * summation order).  All device pointers, 16-byte aligned; the ctx's stream.
- * It is mpp_shapenet_heads_win below with the window equal to the crop and a dense destination. */
-int mpp_shapenet_heads(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b,
-                       float *marks_size, float *marks_ratio, float *marks_angle);
-
-/* The general (window) forms of the five epilogues above, one kernel each, for a forward that walks a large image in crops:
- * H x W is the crop's extent (it decides where the divergence is one-sided), (wx0, wy0, wh x ww) the window in crop coordinates;
- * det / marks point to the window's first pixel in a map whose rows are ld_det / ld_marks pixels apart.  A pixel's result does not
- * depend on the window, bit for bit; nothing outside it is written.  A window outside the crop or ld < ww: -1 and a message. */
-int mpp_posnet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
-                            int wx0, int wy0, int wh, int ww, float *det, int ld_det);
-int mpp_shapenet_epilogue_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0, int wh, int ww,
-                              float *marks, int ld_marks);
-int mpp_posnet_epilogue_nhwc_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
-                                 double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det);
-int mpp_shapenet_epilogue_nhwc_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, int wx0, int wy0,
-                                   int wh, int ww, float *marks, int ld_marks);
+ * marks_* [..][32] = softmax_c(sum_i w[k][c][i] * h[i] + b[k][c]), k = size, ratio, angle; w [3][32 classes][32 in],
+ * b [3][32].  Replaces three library convolutions + bias adds + mpp_shapenet_epilogue_nhwc_win (same values up to float32
+ * summation order).  All device pointers, 16-byte aligned; the ctx's stream.  The window (wx0, wy0, wh x ww) of the H x W crop
+ * and the three destinations' common row pitch ld_marks are those of the epilogues above. */
 int mpp_shapenet_heads_win(mpp_ctx *ctx, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b, int wx0, int wy0,
                            int wh, int ww, float *marks_size, float *marks_ratio, float *marks_angle, int ld_marks);
 

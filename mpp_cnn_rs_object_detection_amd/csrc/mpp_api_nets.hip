@@ -1,6 +1,6 @@
 // mpp_api_nets.hip -- the C ABI around the U-Nets, thin wrappers that check their arguments: inference (mpp_maps.hip,
-// mpp_conv.hip), detection (mpp_detect.hip), training (mpp_train.hip, mpp_resample.hip), rescale (mpp_rescale.hip), and the
-// result pictures (mpp_figures.hip).
+// mpp_conv.hip; one entry point per score-map epilogue, its window form mpp_*_win), detection (mpp_detect.hip), training
+// (mpp_train.hip, mpp_resample.hip), rescale (mpp_rescale.hip), and the result pictures (mpp_figures.hip).
 #include "mpp_ctx.hpp"
 
 extern "C" int mpp_affine_relu(mpp_ctx *c, void *x, int planes, int C, int64_t hw, int elem_bytes, const float *scale,
@@ -217,9 +217,8 @@ extern "C" int mpp_shapenet_loss(mpp_ctx *c, int B, int P, int n_classes, const 
   return 0;
 }
 
-// ---- the U-Net epilogues: the window (wx0, wy0, wh x ww) of an H x W crop into a full-image map.  One implementation per epilogue
-// (`what`: the entry point's name, for its messages); a full form is its window form with the window equal to the crop and a
-// dense destination -----------------------------------------------------------------------------------------------------------
+// ---- the U-Net epilogues: the window (wx0, wy0, wh x ww) of an H x W crop into a full-image map, one entry point and one kernel
+// per epilogue; the whole crop is the window (0, 0, H x W) with a dense destination (ld = W) ------------------------------------
 static int bad_window(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, int wx0, int wy0, int wh, int ww, int ld_dst) {
   if (H <= 0 || W <= 0 || ldh < H || ldw < W) return fail(c, -1, "%s: bad crop extent", what);
   if (wx0 < 0 || wy0 < 0 || wh <= 0 || ww <= 0 || wx0 > H - wh || wy0 > W - ww)
@@ -227,95 +226,55 @@ static int bad_window(mpp_ctx *c, const char *what, int H, int W, int ldh, int l
   if (ld_dst < ww) return fail(c, -1, "%s: destination pitch %d smaller than the window width %d", what, ld_dst, ww);
   return 0;
 }
-static int posnet_epilogue(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, const float *pos_out, double div_w,
-                           double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
+extern "C" int mpp_posnet_epilogue_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
+                                       int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
   if (!c || !pos_out || !det) return fail(c, -1, "bad epilogue arguments");
-  if (bad_window(c, what, H, W, ldh, ldw, wx0, wy0, wh, ww, ld_det)) return -1;
+  if (bad_window(c, "posnet_epilogue_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_det)) return -1;
   HIPCHK(c, hipSetDevice(c->device));
   mpp_launch_posnet_epilogue(c->stream, pos_out, H, W, ldh, ldw, (float)div_w, (float)div_b, wx0, wy0, wh, ww, det, ld_det);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
-static int shapenet_epilogue(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0,
-                             int wh, int ww, float *marks, int ld_marks) {
-  if (!c || !logits || !marks) return fail(c, -1, "bad epilogue arguments");
-  if (bad_window(c, what, H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (mpp_launch_shapenet_epilogue(c->stream, logits, ldh, ldw, wx0, wy0, wh, ww, marks, ld_marks))
-    return fail(c, -1, "%s: marks must be 16-byte aligned", what);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-static int posnet_epilogue_nhwc(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes,
-                                double div_w, double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
-  if (!c || !pos_out || !det) return fail(c, -1, "bad epilogue arguments");
-  if (bad_window(c, what, H, W, ldh, ldw, wx0, wy0, wh, ww, ld_det)) return -1;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (mpp_launch_posnet_epilogue_nhwc(c->stream, pos_out, elem_bytes, H, W, ldw, (float)div_w, (float)div_b, wx0, wy0, wh, ww, det,
-                                      ld_det))
-    return fail(c, -1, "%s: element type must be float32 or bfloat16", what);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-static int shapenet_epilogue_nhwc(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes,
-                                  int wx0, int wy0, int wh, int ww, float *marks, int ld_marks) {
-  if (!c || !logits || !marks) return fail(c, -1, "bad epilogue arguments");
-  if (bad_window(c, what, H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int e = mpp_launch_shapenet_epilogue_nhwc(c->stream, logits, elem_bytes, ldw, wx0, wy0, wh, ww, marks, ld_marks);
-  if (e == -1) return fail(c, -1, "%s: element type must be float32 or bfloat16", what);
-  if (e == -2) return fail(c, -1, "%s: logits and marks must be 16-byte aligned", what);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-static int shapenet_heads(mpp_ctx *c, const char *what, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b,
-                          int wx0, int wy0, int wh, int ww, float *marks_size, float *marks_ratio, float *marks_angle, int ld_marks) {
-  if (!c || !h || !w || !b || !marks_size || !marks_ratio || !marks_angle) return fail(c, -1, "bad shapenet_heads arguments");
-  if (bad_window(c, what, H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int rc = mpp_launch_shapenet_heads(c->stream, h, ldw, w, b, wx0, wy0, wh, ww, marks_size, marks_ratio, marks_angle, ld_marks);
-  if (rc == -2 && (((uintptr_t)h | (uintptr_t)marks_size | (uintptr_t)marks_ratio | (uintptr_t)marks_angle) & 15))
-    return fail(c, -1, "%s: the activations and the mark maps must be 16-byte aligned", what);
-  if (rc) return fail(c, -2, "%s launch failed: %s", what, hipGetErrorString(hipGetLastError()));
-  return 0;
-}
-extern "C" int mpp_posnet_epilogue(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
-                                   float *det) {
-  return posnet_epilogue(c, "posnet_epilogue", H, W, ldh, ldw, pos_out, div_w, div_b, 0, 0, H, W, det, W);
-}
-extern "C" int mpp_posnet_epilogue_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *pos_out, double div_w, double div_b,
-                                       int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
-  return posnet_epilogue(c, "posnet_epilogue_win", H, W, ldh, ldw, pos_out, div_w, div_b, wx0, wy0, wh, ww, det, ld_det);
-}
-extern "C" int mpp_shapenet_epilogue(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *logits, float *marks) {
-  return shapenet_epilogue(c, "shapenet_epilogue", H, W, ldh, ldw, logits, 0, 0, H, W, marks, W);
-}
 extern "C" int mpp_shapenet_epilogue_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *logits, int wx0, int wy0, int wh, int ww,
                                          float *marks, int ld_marks) {
-  return shapenet_epilogue(c, "shapenet_epilogue_win", H, W, ldh, ldw, logits, wx0, wy0, wh, ww, marks, ld_marks);
-}
-extern "C" int mpp_posnet_epilogue_nhwc(mpp_ctx *c, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
-                                        double div_b, float *det) {
-  return posnet_epilogue_nhwc(c, "posnet_epilogue_nhwc", H, W, ldh, ldw, pos_out, elem_bytes, div_w, div_b, 0, 0, H, W, det, W);
+  if (!c || !logits || !marks) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "shapenet_epilogue_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (mpp_launch_shapenet_epilogue(c->stream, logits, ldh, ldw, wx0, wy0, wh, ww, marks, ld_marks))
+    return fail(c, -1, "shapenet_epilogue_win: marks must be 16-byte aligned");
+  HIPCHK(c, hipGetLastError());
+  return 0;
 }
 extern "C" int mpp_posnet_epilogue_nhwc_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const void *pos_out, int elem_bytes, double div_w,
                                             double div_b, int wx0, int wy0, int wh, int ww, float *det, int ld_det) {
-  return posnet_epilogue_nhwc(c, "posnet_epilogue_nhwc_win", H, W, ldh, ldw, pos_out, elem_bytes, div_w, div_b, wx0, wy0, wh, ww, det,
-                              ld_det);
-}
-extern "C" int mpp_shapenet_epilogue_nhwc(mpp_ctx *c, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, float *marks) {
-  return shapenet_epilogue_nhwc(c, "shapenet_epilogue_nhwc", H, W, ldh, ldw, logits, elem_bytes, 0, 0, H, W, marks, W);
+  if (!c || !pos_out || !det) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "posnet_epilogue_nhwc_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_det)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (mpp_launch_posnet_epilogue_nhwc(c->stream, pos_out, elem_bytes, H, W, ldw, (float)div_w, (float)div_b, wx0, wy0, wh, ww, det,
+                                      ld_det))
+    return fail(c, -1, "posnet_epilogue_nhwc_win: element type must be float32 or bfloat16");
+  HIPCHK(c, hipGetLastError());
+  return 0;
 }
 extern "C" int mpp_shapenet_epilogue_nhwc_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const void *logits, int elem_bytes, int wx0,
                                               int wy0, int wh, int ww, float *marks, int ld_marks) {
-  return shapenet_epilogue_nhwc(c, "shapenet_epilogue_nhwc_win", H, W, ldh, ldw, logits, elem_bytes, wx0, wy0, wh, ww, marks, ld_marks);
-}
-extern "C" int mpp_shapenet_heads(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b,
-                                  float *marks_size, float *marks_ratio, float *marks_angle) {
-  return shapenet_heads(c, "shapenet_heads", H, W, ldh, ldw, h, w, b, 0, 0, H, W, marks_size, marks_ratio, marks_angle, W);
+  if (!c || !logits || !marks) return fail(c, -1, "bad epilogue arguments");
+  if (bad_window(c, "shapenet_epilogue_nhwc_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int e = mpp_launch_shapenet_epilogue_nhwc(c->stream, logits, elem_bytes, ldw, wx0, wy0, wh, ww, marks, ld_marks);
+  if (e == -1) return fail(c, -1, "shapenet_epilogue_nhwc_win: element type must be float32 or bfloat16");
+  if (e == -2) return fail(c, -1, "shapenet_epilogue_nhwc_win: logits and marks must be 16-byte aligned");
+  HIPCHK(c, hipGetLastError());
+  return 0;
 }
 extern "C" int mpp_shapenet_heads_win(mpp_ctx *c, int H, int W, int ldh, int ldw, const float *h, const float *w, const float *b, int wx0,
                                       int wy0, int wh, int ww, float *marks_size, float *marks_ratio, float *marks_angle, int ld_marks) {
-  return shapenet_heads(c, "shapenet_heads_win", H, W, ldh, ldw, h, w, b, wx0, wy0, wh, ww, marks_size, marks_ratio, marks_angle,
-                        ld_marks);
+  if (!c || !h || !w || !b || !marks_size || !marks_ratio || !marks_angle) return fail(c, -1, "bad shapenet_heads arguments");
+  if (bad_window(c, "shapenet_heads_win", H, W, ldh, ldw, wx0, wy0, wh, ww, ld_marks)) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = mpp_launch_shapenet_heads(c->stream, h, ldw, w, b, wx0, wy0, wh, ww, marks_size, marks_ratio, marks_angle, ld_marks);
+  if (rc == -2 && (((uintptr_t)h | (uintptr_t)marks_size | (uintptr_t)marks_ratio | (uintptr_t)marks_angle) & 15))
+    return fail(c, -1, "shapenet_heads_win: the activations and the mark maps must be 16-byte aligned");
+  if (rc) return fail(c, -2, "shapenet_heads_win launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
 }

@@ -10,6 +10,7 @@
 //    contiguous) are fully coalesced (shape_net_model.py:139-141 + data_loaders.py:54).
 #include "mpp_device.hpp"
 #include "mpp_launch.hpp"
+#include "mpp_unet_math.hpp"
 
 // ---- birth CDF ---------------------------------------------------------------------------------
 // (all tiles of a context in one launch: blockIdx.y / blockIdx.x / blockIdx.z = tile)
@@ -137,25 +138,10 @@ extern "C" void mpp_launch_naive_init(hipStream_t st, const DevParams *P, const 
 // Both epilogues take a window (wx0, wy0, wh x ww) of the crop's H x W extent (the tiled forward: unet.py, chunk_plan; the
 // whole crop is the window (0, 0, H x W)): H x W still decides where the differences are one-sided; the window's pixels go to
 // dst (the window's first pixel in a full-image map) with a row pitch of ld_dst pixels.  Per pixel the arithmetic and its order
-// do not depend on the window (the build forms no FMA: -ffp-contract=off), so a window is the whole-crop map restricted to it
-// bit for bit; nothing outside it is written.
-__device__ __forceinline__ float posnet_pixel(const float *v0, const float *v1, const float *mk, int x, int y, int H,
-                                              int W, int ldw, float w, float b) {
-  float g0, g1;
-  if (H == 1) g0 = 0.f;
-  else if (x == 0) g0 = v0[(size_t)1 * ldw + y] - v0[y];
-  else if (x == H - 1) g0 = v0[(size_t)x * ldw + y] - v0[(size_t)(x - 1) * ldw + y];
-  else g0 = (v0[(size_t)(x + 1) * ldw + y] - v0[(size_t)(x - 1) * ldw + y]) / 2.0f;
-  if (W == 1) g1 = 0.f;
-  else if (y == 0) g1 = v1[(size_t)x * ldw + 1] - v1[(size_t)x * ldw];
-  else if (y == W - 1) g1 = v1[(size_t)x * ldw + y] - v1[(size_t)x * ldw + y - 1];
-  else g1 = (v1[(size_t)x * ldw + y + 1] - v1[(size_t)x * ldw + y - 1]) / 2.0f;
-  float mask = 1.0f / (1.0f + expf(-mk[(size_t)x * ldw + y]));
-  float score = w * ((g0 + g1) * mask) + b;
-  return 1.0f / (1.0f + expf(-score));
-}
+// do not depend on the window (div_at / div_score, mpp_unet_math.hpp; the build forms no FMA: -ffp-contract=off), so a window is
+// the whole-crop map restricted to it bit for bit; nothing outside it is written.
 // each thread produces 4 consecutive pixels of a row: 16-byte loads of the rows above/below, of the row
-// itself (plus its two neighbours) and of the mask, one 16-byte store
+// itself (plus its two neighbours) and of the mask, one 16-byte store (interior pixels only: grad1's central differences)
 __global__ __launch_bounds__(256) void k_posnet_epilogue(const float *out, int H, int W, int ldh, int ldw, float w, float b,
                                                          int wx0, int wy0, int wh, int ww, float *dst, int ld_dst, int vec_ok) {
   const int j4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, r = blockIdx.y;
@@ -163,6 +149,7 @@ __global__ __launch_bounds__(256) void k_posnet_epilogue(const float *out, int H
   const int x = wx0 + r, y4 = wy0 + j4;
   const size_t plane = (size_t)ldh * ldw;
   const float *v0 = out, *v1 = out + plane, *mk = out + 2 * plane;
+  auto px = [&](int i, int j, int ch) -> float { return out[ch * plane + (size_t)i * ldw + j]; };
   float *drow = dst + (size_t)r * ld_dst;
   if (vec_ok && x > 0 && x < H - 1 && y4 > 0 && y4 + 4 < W && j4 + 4 <= ww) {
     const float4 up = *(const float4 *)(v0 + (size_t)(x - 1) * ldw + y4), dn = *(const float4 *)(v0 + (size_t)(x + 1) * ldw + y4);
@@ -173,14 +160,10 @@ __global__ __launch_bounds__(256) void k_posnet_epilogue(const float *out, int H
     const float mm[4] = {m4.x, m4.y, m4.z, m4.w};
     float res[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float mask = 1.0f / (1.0f + expf(-mm[i]));
-      float score = w * ((g0[i] + g1[i]) * mask) + b;
-      res[i] = 1.0f / (1.0f + expf(-score));
-    }
+    for (int i = 0; i < 4; ++i) res[i] = div_score(g0[i], g1[i], mm[i], w, b).q;
     *(float4 *)(drow + j4) = make_float4(res[0], res[1], res[2], res[3]);
   } else {
-    for (int j = j4; j < min(j4 + 4, ww); ++j) drow[j] = posnet_pixel(v0, v1, mk, x, wy0 + j, H, W, ldw, w, b);
+    for (int j = j4; j < min(j4 + 4, ww); ++j) drow[j] = div_at(px, x, wy0 + j, H, W, w, b).q;
   }
 }
 extern "C" void mpp_launch_posnet_epilogue(hipStream_t st, const float *out, int H, int W, int ldh, int ldw, float w, float b,
@@ -215,18 +198,14 @@ __global__ __launch_bounds__(256) void k_shapenet_epilogue(const float *logits, 
   }
   __syncthreads();
   const int p = threadIdx.x >> 2, q = threadIdx.x & 3;
-  float v[8], m = -INFINITY;
+  float v[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = tile[q * 8 + i][p]; m = fmaxf(m, v[i]); }
-  m = fmaxf(m, __shfl_xor(m, 1, WAVE)); m = fmaxf(m, __shfl_xor(m, 2, WAVE));
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = expf(v[i] - m); s += v[i]; }
-  s += __shfl_xor(s, 1, WAVE); s += __shfl_xor(s, 2, WAVE);
+  for (int i = 0; i < 8; ++i) v[i] = tile[q * 8 + i][p];
+  softmax_quad(v);
   if (j0 + p < ww) {
     float4 *d = (float4 *)(dst + ((size_t)r * ld_dst + j0 + p) * MPP_NCLASS + q * 8);
-    d[0] = make_float4(v[0] / s, v[1] / s, v[2] / s, v[3] / s);
-    d[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
+    d[0] = make_float4(v[0], v[1], v[2], v[3]);
+    d[1] = make_float4(v[4], v[5], v[6], v[7]);
   }
 }
 extern "C" int mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits, int ldh, int ldw, int wx0, int wy0, int wh, int ww,
@@ -243,13 +222,6 @@ extern "C" int mpp_launch_shapenet_epilogue(hipStream_t st, const float *logits,
 // BatchNorm(eval) folded with the convolution bias, plus the ReLU, in ONE pass over the activation instead of the
 // three (bias add, batch norm, ReLU) PyTorch runs after each MIOpen convolution (unet_parts.py:12-31).
 // 16-byte accesses: 4 floats or 8 bf16 per lane (hw is a multiple of 8: the image is padded to 2^depth).
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned int)h << 16); }
-__device__ __forceinline__ unsigned short f32_to_bf16(float f) {          // round to nearest even, as torch does
-  unsigned int u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 __global__ __launch_bounds__(256) void k_affine_relu_f32(float *x, int C, size_t hw, size_t total4, const float *scale,
                                                          const float *shift) {
   const size_t i4 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -266,15 +238,11 @@ __global__ __launch_bounds__(256) void k_affine_relu_bf16(unsigned short *x, int
   if (i8 >= total8) return;
   const int ch = (int)((i8 * 8 / hw) % (size_t)C);
   const float s = scale[ch], t = shift[ch];
-  uint4 v = ((uint4 *)x)[i8];
-  unsigned int w[4] = {v.x, v.y, v.z, v.w};
+  float v[8];
+  unpack_bf16x8(((uint4 *)x)[i8], v);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float lo = fmaxf(0.f, bf16_to_f32((unsigned short)(w[k] & 0xffffu)) * s + t);
-    float hi = fmaxf(0.f, bf16_to_f32((unsigned short)(w[k] >> 16)) * s + t);
-    w[k] = (unsigned int)f32_to_bf16(lo) | ((unsigned int)f32_to_bf16(hi) << 16);
-  }
-  ((uint4 *)x)[i8] = make_uint4(w[0], w[1], w[2], w[3]);
+  for (int k = 0; k < 8; ++k) v[k] = fmaxf(0.f, v[k] * s + t);
+  ((uint4 *)x)[i8] = pack_bf16x8(v);
 }
 // planes whose size is not a multiple of the vector width (the deepest levels of small images): one element per lane
 __global__ __launch_bounds__(256) void k_affine_relu_any(void *x, int C, size_t hw, size_t total, int elem_bytes,
@@ -323,18 +291,8 @@ template <> struct NhwcVec<4> {
 };
 template <> struct NhwcVec<2> {
   static constexpr int N = 8;
-  __device__ static void load(const void *p, size_t i, float *v) {
-    uint4 t = *(const uint4 *)((const unsigned short *)p + i);
-    unsigned int w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[2 * k] = bf16_to_f32((unsigned short)(w[k] & 0xffffu)); v[2 * k + 1] = bf16_to_f32((unsigned short)(w[k] >> 16)); }
-  }
-  __device__ static void store(void *p, size_t i, const float *v) {
-    unsigned int w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = (unsigned int)f32_to_bf16(v[2 * k]) | ((unsigned int)f32_to_bf16(v[2 * k + 1]) << 16);
-    *(uint4 *)((unsigned short *)p + i) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
+  __device__ static void load(const void *p, size_t i, float *v) { unpack_bf16x8(*(const uint4 *)((const unsigned short *)p + i), v); }
+  __device__ static void store(void *p, size_t i, const float *v) { *(uint4 *)((unsigned short *)p + i) = pack_bf16x8(v); }
 };
 __device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
@@ -425,7 +383,7 @@ extern "C" int mpp_launch_nhwc_glue(hipStream_t st, const void *x0, const void *
 }
 
 // ---- the two epilogues on channels-last network outputs (float32 or bfloat16) ----------------------------------------
-// Same arithmetic, in the same order, as k_posnet_epilogue / k_shapenet_epilogue; only the addressing differs:
+// The arithmetic of k_posnet_epilogue / k_shapenet_epilogue (div_at and softmax_quad, mpp_unet_math.hpp); only the addressing differs:
 // out [ldh][ldw][3] and logits [ldh][ldw][32].  A pixel's 32 logits are contiguous, so the softmax needs no transpose:
 // 4 lanes per pixel, 8 classes each (one or two 16-byte loads), two 16-byte stores.
 // The window (wx0, wy0, wh x ww) of the H x W crop goes to dst with a row pitch of ld_dst pixels, as above.
@@ -438,19 +396,9 @@ __global__ __launch_bounds__(256) void k_posnet_epilogue_nhwc(const void *out, i
   const int j = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
   if (j >= ww || r >= wh) return;
   const int x = wx0 + r, y = wy0 + j;
-  auto at = [&](int i, int jj, int ch) -> float { return ld_elem<EB>(out, ((size_t)i * ldw + jj) * 3 + ch); };
-  float g0, g1;
-  if (H == 1) g0 = 0.f;
-  else if (x == 0) g0 = at(1, y, 0) - at(0, y, 0);
-  else if (x == H - 1) g0 = at(x, y, 0) - at(x - 1, y, 0);
-  else g0 = (at(x + 1, y, 0) - at(x - 1, y, 0)) / 2.0f;
-  if (W == 1) g1 = 0.f;
-  else if (y == 0) g1 = at(x, 1, 1) - at(x, 0, 1);
-  else if (y == W - 1) g1 = at(x, y, 1) - at(x, y - 1, 1);
-  else g1 = (at(x, y + 1, 1) - at(x, y - 1, 1)) / 2.0f;
-  float mask = 1.0f / (1.0f + expf(-at(x, y, 2)));
-  float score = w * ((g0 + g1) * mask) + b;
-  dst[(size_t)r * ld_dst + j] = 1.0f / (1.0f + expf(-score));
+  const size_t pitch = (size_t)ldw * 3;             // elements per row
+  auto px = [&](int i, int jj, int ch) -> float { return ld_elem<EB>(out, i * pitch + (size_t)jj * 3 + ch); };
+  dst[(size_t)r * ld_dst + j] = div_at(px, x, y, H, W, w, b).q;
 }
 template <int EB>
 __global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc(const void *logits, int ldw, int wx0, int wy0, int wh, int ww,
@@ -461,27 +409,18 @@ __global__ __launch_bounds__(256) void k_shapenet_epilogue_nhwc(const void *logi
   const bool live = pix < (size_t)wh * ww;         // the 4 lanes of a pixel are live together; dead lanes still shuffle
   const int r = live ? (int)(pix / (size_t)ww) : 0, j = live ? (int)(pix % (size_t)ww) : 0;
   const size_t src = ((size_t)(wx0 + r) * ldw + wy0 + j) * MPP_NCLASS + q * 8;
-  float v[8], m = -INFINITY;
+  float v[8];
   if (EB == 4) {
     const float4 a = *(const float4 *)((const float *)logits + src), c = *(const float4 *)((const float *)logits + src + 4);
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
   } else {
-    const uint4 a = *(const uint4 *)((const unsigned short *)logits + src);
-    const unsigned int wd[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[2 * k] = bf16_to_f32((unsigned short)(wd[k] & 0xffffu)); v[2 * k + 1] = bf16_to_f32((unsigned short)(wd[k] >> 16)); }
+    unpack_bf16x8(*(const uint4 *)((const unsigned short *)logits + src), v);
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) m = fmaxf(m, v[i]);
-  m = fmaxf(m, __shfl_xor(m, 1, WAVE)); m = fmaxf(m, __shfl_xor(m, 2, WAVE));
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { v[i] = expf(v[i] - m); s += v[i]; }
-  s += __shfl_xor(s, 1, WAVE); s += __shfl_xor(s, 2, WAVE);
+  softmax_quad(v);
   if (live) {
     float4 *d = (float4 *)(dst + ((size_t)r * ld_dst + j) * MPP_NCLASS + q * 8);
-    d[0] = make_float4(v[0] / s, v[1] / s, v[2] / s, v[3] / s);
-    d[1] = make_float4(v[4] / s, v[5] / s, v[6] / s, v[7] / s);
+    d[0] = make_float4(v[0], v[1], v[2], v[3]);
+    d[1] = make_float4(v[4], v[5], v[6], v[7]);
   }
 }
 extern "C" int mpp_launch_posnet_epilogue_nhwc(hipStream_t st, const void *out, int elem_bytes, int H, int W, int ldw, float w,

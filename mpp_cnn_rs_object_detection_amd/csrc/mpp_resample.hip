@@ -15,6 +15,7 @@
 
 #include "mpp_device.hpp"
 #include "mpp_train.hpp"
+#include "mpp_unet_math.hpp"
 
 namespace {
 
@@ -45,8 +46,6 @@ __global__ __launch_bounds__(TB) void k_image_hist(mpp_train_data data, uint32_t
     if (c) atomicAdd(&hist[((size_t)img * 3 + ch) * 256 + threadIdx.x], c);
   }
 }
-
-__device__ __forceinline__ float sigmf(float x) { return 1.0f / (1.0f + expf(-x)); }   // as torch forms it (mpp_train.hip)
 
 // thread t: cell t / 4 of the tile (row-major), rows 2 (t % 4) and 2 (t % 4) + 1 of that cell: 16 pixels
 __global__ __launch_bounds__(TB) void k_error_map(int H, int W, int ldh, int ldw, const float *out, int cx0, int cy0, int x0,

@@ -31,6 +31,7 @@
 
 #include "mpp_device.hpp"
 #include "mpp_train.hpp"
+#include "mpp_unet_math.hpp"
 
 namespace {
 
@@ -909,25 +910,8 @@ __device__ void batch_sums(const double *sums, int nrows, double *red, double &s
 
 // The reference runs these losses in float32, and where a sigmoid saturates its value is float32 arithmetic: 1 - sigmoid(x)
 // is exactly 0 above x ~ 17, so log(1 - q + eps) is log(eps) and the sigmoid's backward (1 - y) * y is 0.  So the sigmoids,
-// the divergence and the arguments of the logs are formed in float32 as torch forms them; the rest, and every sum, is float64.
-__device__ __forceinline__ float sigmf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// the divergence classifier at (i, j): div = d(out0)/drow + d(out1)/dcol (torch.gradient: one-sided at the edges, central
-// inside), x = div * sigmoid(out2), z = w x + b, q = sigmoid(z)
-struct DivAt { float div, s, x, q; };
-__device__ __forceinline__ float grad1(const float *f, int n, int stride, int i) {
-  if (i == 0) return f[stride] - f[0];
-  if (i == n - 1) return f[(size_t)(n - 1) * stride] - f[(size_t)(n - 2) * stride];
-  return (f[(size_t)(i + 1) * stride] - f[(size_t)(i - 1) * stride]) / 2.0f;
-}
-__device__ __forceinline__ DivAt div_at(const float *o, size_t PP, int P, int i, int j, float w, float bias) {
-  DivAt d;
-  d.div = grad1(o + j, P, P, i) + grad1(o + PP + (size_t)i * P, P, 1, j);
-  d.s = sigmf(o[2 * PP + (size_t)i * P + j]);
-  d.x = d.div * d.s;
-  d.q = sigmf(w * d.x + bias);
-  return d;
-}
+// the divergence and the arguments of the logs are formed in float32 as torch forms them (sigmf, div_at: mpp_unet_math.hpp, the
+// functions of the inference epilogues); the rest, and every sum, is float64.
 // balanced BCE of a float32 sigmoid output y against target t: the loss term and dL/dy
 __device__ __forceinline__ void bce(float y, double t, double beta, double &loss, double &dy) {
   const double la = (double)(y + 1e-5f), lb = (double)((1.0f - y) + 1e-5f);
@@ -955,6 +939,8 @@ __global__ __launch_bounds__(TB) void k_posnet_loss(int B, int P, int nb, const 
   const float w = with_div ? wp[0] : 0.f, bias = with_div ? bp[0] : 0.f;
   const float *o = out + (size_t)b * 3 * PP;
   const float *t = vec + (size_t)b * 2 * PP;
+  __builtin_assume(P >= 3);                 // (mpp_posnet_loss checks it: grad1's one-element case is never reached)
+  auto px = [&](int i, int j, int ch) -> float { return o[ch * PP + (size_t)i * P + j]; };   // the patch's [3][P][P] output
   double acc[5] = {0, 0, 0, 0, 0};          // vec, mask, div losses (sums), dL/dw, dL/db
   const int r0 = band * BAND, r1 = min(P, r0 + BAND);
   for (int idx = threadIdx.x; idx < (r1 - r0) * P; idx += TB) {
@@ -971,7 +957,7 @@ __global__ __launch_bounds__(TB) void k_posnet_loss(int B, int P, int nb, const 
     double ds = (e0 * o0 + e1 * o1) * invN + dsm * invN;                  // vec_loss = mean over B*2*P*P
     double g0 = e0 * s * invN, g1 = e1 * s * invN;
     if (with_div) {
-      const DivAt d = div_at(o, PP, P, i, j, w, bias);
+      const DivAt d = div_at(px, i, j, P, P, w, bias);
       const double y = dil[(size_t)b * PP + pix];
       double ld, dq;
       bce(d.q, y, beta_d, ld, dq);
@@ -982,7 +968,7 @@ __global__ __launch_bounds__(TB) void k_posnet_loss(int B, int P, int nb, const 
       ds += dz * (double)w * (double)d.div;
       // adjoint of the stencils: h = dL/d(div) = dz * w * s at the pixels whose divergence reads this one
       auto h = [&](int ii, int jj) {
-        const DivAt e = div_at(o, PP, P, ii, jj, w, bias);
+        const DivAt e = div_at(px, ii, jj, P, P, w, bias);
         return dz_at(e, dil[(size_t)b * PP + (size_t)ii * P + jj], beta_d, invN) * (double)w * (double)e.s;
       };
       // rows (channel 0): g[0] = f1 - f0, g[n-1] = f[n-1] - f[n-2], g[k] = (f[k+1] - f[k-1]) / 2

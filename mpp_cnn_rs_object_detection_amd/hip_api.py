@@ -20,19 +20,6 @@ LIB_PATH = os.environ.get("MPP_LIB_PATH") or os.path.join(_HERE, "libmppgpu.so")
 
 MAX_UNIT, MAX_PAIR, NCLASS, NKERNEL = 8, 2, 32, 10
 
-#: every symbol include/mpp_hip.h declares (tests check that the library exports all of them)
-ABI_SYMBOLS = [
-    "mpp_create", "mpp_destroy", "mpp_last_error", "mpp_set_stream", "mpp_synchronize", "mpp_set_option",
-    "mpp_get_option", "mpp_set_maps", "mpp_set_image", "mpp_set_model", "mpp_set_kernels", "mpp_set_points", "mpp_get_points",
-    "mpp_count", "mpp_get_points_all", "mpp_pack_detections", "mpp_total_energy", "mpp_total_energy_all", "mpp_delta_batch", "mpp_delta_vectors", "mpp_papangelou", "mpp_merge_score", "mpp_naive_init", "mpp_set_schedule",
-    "mpp_replay", "mpp_run", "mpp_set_chain_keys", "mpp_step_index", "mpp_last_kernel_ms", "mpp_posnet_epilogue",
-    "mpp_shapenet_epilogue", "mpp_posnet_epilogue_nhwc", "mpp_shapenet_epilogue_nhwc", "mpp_affine_relu", "mpp_nhwc_glue", "mpp_conv3x3_c32", "mpp_conv3x3_stem", "mpp_shapenet_heads", "mpp_posnet_epilogue_win", "mpp_shapenet_epilogue_win",
-    "mpp_posnet_epilogue_nhwc_win", "mpp_shapenet_epilogue_nhwc_win", "mpp_shapenet_heads_win", "mpp_quad_iou", "mpp_detect_centers", "mpp_mark_classes", "mpp_train_batch", "mpp_posnet_loss", "mpp_shapenet_loss", "mpp_philox4x32",
-    "mpp_image_histograms", "mpp_train_set_histograms", "mpp_posnet_error_map", "mpp_density_prefix", "mpp_density_anchors",
-    "mpp_train_aug_params", "mpp_rescale", "mpp_draw_outlines", "mpp_abi_version",
-]
-
-
 class UnitTermC(C.Structure):
     _fields_ = [("kind", C.c_int32), ("gated", C.c_int32), ("coef", C.c_double), ("p", C.c_double * 8)]
 
@@ -100,6 +87,69 @@ STEPOUT_DTYPE = np.dtype([("dE", "<f8"), ("fwd", "<f8"), ("bwd", "<f8"), ("log_a
                           ("accepted", "<i4"), ("n_after", "<i4")], align=True)
 
 
+_vp, _i32, _i64, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_double
+#: (result, arguments) of every function include/mpp_hip.h declares
+PROTOTYPES = {
+    "mpp_create": (_i32, [_i32, C.POINTER(_vp)]),
+    "mpp_destroy": (_i32, [_vp]),
+    "mpp_last_error": (C.c_char_p, [_vp]),
+    "mpp_set_stream": (_i32, [_vp, _vp]),
+    "mpp_synchronize": (_i32, [_vp]),
+    "mpp_set_option": (_i32, [_vp, C.c_char_p, _i64]),
+    "mpp_get_option": (_i64, [_vp, C.c_char_p]),
+    "mpp_set_maps": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
+    "mpp_set_image": (_i32, [_vp, _i32, _i32, _vp, _i32]),
+    "mpp_set_model": (_i32, [_vp, C.POINTER(ModelC), C.POINTER(MappingsC)]),
+    "mpp_set_kernels": (_i32, [_vp, C.POINTER(KernelsC), _vp]),
+    "mpp_set_points": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mpp_get_points": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_int32), _vp, _vp]),
+    "mpp_count": (_i32, [_vp, _i32, C.POINTER(C.c_int32)]),
+    "mpp_get_points_all": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "mpp_pack_detections": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, C.POINTER(C.c_int32)]),
+    "mpp_total_energy": (_i32, [_vp, _i32, C.POINTER(_dbl), _vp]),
+    "mpp_total_energy_all": (_i32, [_vp, _vp]),
+    "mpp_delta_batch": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mpp_delta_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "mpp_papangelou": (_i32, [_vp, _i32, _vp]),
+    "mpp_conv3x3_c32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "mpp_conv3x3_stem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mpp_merge_score": (_i32, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mpp_naive_init": (_i32, [_vp, _dbl, _dbl]),
+    "mpp_set_schedule": (_i32, [_vp, _dbl, _dbl, _dbl]),
+    "mpp_replay": (_i32, [_vp, _i32, _i32, _vp, _vp]),
+    "mpp_run": (_i32, [_vp, _i64, C.c_uint64, C.c_uint32, _i32, _vp, _vp]),
+    "mpp_set_chain_keys": (_i32, [_vp, _i32, _vp, _vp]),
+    "mpp_step_index": (_i32, [_vp, _i32, C.POINTER(C.c_int64)]),
+    "mpp_last_kernel_ms": (_i32, [_vp, C.POINTER(_dbl)]),
+    "mpp_affine_relu": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp]),
+    "mpp_posnet_epilogue_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _dbl, _dbl, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "mpp_shapenet_epilogue_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "mpp_posnet_epilogue_nhwc_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _dbl, _dbl, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "mpp_shapenet_epilogue_nhwc_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "mpp_shapenet_heads_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32]),
+    "mpp_nhwc_glue": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "mpp_quad_iou": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32]),
+    "mpp_detect_centers": (_i32, [_vp, _i32, _i32, _i32, _vp, _dbl, _i32, _dbl, _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mpp_mark_classes": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "mpp_train_batch": (_i32, [_vp, C.POINTER(TrainDataC), C.POINTER(TrainLabelsC), _i32, _i32, _vp, _i32, C.c_uint32, C.c_uint32,
+                               C.c_uint32, C.POINTER(TrainOutC)]),
+    "mpp_posnet_loss": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "mpp_shapenet_loss": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mpp_philox4x32": (None, [_vp, _vp, _vp]),
+    "mpp_image_histograms": (_i32, [_vp, C.POINTER(TrainDataC), _vp]),
+    "mpp_train_set_histograms": (_i32, [_vp, _vp, _i32]),
+    "mpp_train_aug_params": (_i32, [_vp, _i32, C.c_uint32, C.c_uint32, C.c_uint32, _i32, _i32, _i32, _vp]),
+    "mpp_posnet_error_map": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _dbl, _vp, _vp, _vp]),
+    "mpp_density_prefix": (_i32, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mpp_density_anchors": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "mpp_rescale": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i64]),
+    "mpp_draw_outlines": (_i32, [_vp, _i32, _i32, _vp, _vp, _dbl, _dbl, _vp, _i32, _vp, _vp, _vp]),
+    "mpp_abi_version": (_i32, []),
+}
+#: every symbol include/mpp_hip.h declares (tests check that the header agrees and that the library exports all of them)
+ABI_SYMBOLS = list(PROTOTYPES)
+
+
 class MppError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libmppgpu error {code}: {message}")
@@ -122,7 +172,7 @@ def _torch_runtime_first():
 
 
 def load_library(path: Optional[str] = None):
-    """Load libmppgpu.so and declare the prototypes.  Raises if it was not built."""
+    """Load libmppgpu.so and declare the prototypes (``PROTOTYPES``).  Raises if it was not built."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -132,70 +182,7 @@ def load_library(path: Optional[str] = None):
                           "(hipcc --offload-arch=gfx950); there is no CPU fallback for the sampler")
     _torch_runtime_first()
     L = C.CDLL(path)
-    vp, i32, i64, dbl = C.c_void_p, C.c_int, C.c_int64, C.c_double
-    protos = {
-        "mpp_create": (i32, [i32, C.POINTER(vp)]),
-        "mpp_destroy": (i32, [vp]),
-        "mpp_last_error": (C.c_char_p, [vp]),
-        "mpp_set_stream": (i32, [vp, vp]),
-        "mpp_synchronize": (i32, [vp]),
-        "mpp_set_option": (i32, [vp, C.c_char_p, i64]),
-        "mpp_get_option": (i64, [vp, C.c_char_p]),
-        "mpp_set_maps": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32]),
-        "mpp_set_image": (i32, [vp, i32, i32, vp, i32]),
-        "mpp_set_model": (i32, [vp, C.POINTER(ModelC), C.POINTER(MappingsC)]),
-        "mpp_set_kernels": (i32, [vp, C.POINTER(KernelsC), vp]),
-        "mpp_set_points": (i32, [vp, i32, i32, vp, vp]),
-        "mpp_get_points": (i32, [vp, i32, i32, C.POINTER(C.c_int32), vp, vp]),
-        "mpp_count": (i32, [vp, i32, C.POINTER(C.c_int32)]),
-        "mpp_get_points_all": (i32, [vp, i32, vp, vp, vp]),
-        "mpp_pack_detections": (i32, [vp, i32, vp, vp, i32, vp, C.POINTER(C.c_int32)]),
-        "mpp_total_energy": (i32, [vp, i32, C.POINTER(dbl), vp]),
-        "mpp_total_energy_all": (i32, [vp, vp]),
-        "mpp_delta_batch": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]),
-        "mpp_delta_vectors": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
-        "mpp_papangelou": (i32, [vp, i32, vp]),
-        "mpp_conv3x3_c32": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]),
-        "mpp_shapenet_heads": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
-        "mpp_conv3x3_stem": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
-        "mpp_merge_score": (i32, [vp, C.c_double, i32, vp, vp, vp, vp, vp]),
-        "mpp_naive_init": (i32, [vp, dbl, dbl]),
-        "mpp_set_schedule": (i32, [vp, dbl, dbl, dbl]),
-        "mpp_replay": (i32, [vp, i32, i32, vp, vp]),
-        "mpp_run": (i32, [vp, i64, C.c_uint64, C.c_uint32, i32, vp, vp]),
-        "mpp_set_chain_keys": (i32, [vp, i32, vp, vp]),
-        "mpp_step_index": (i32, [vp, i32, C.POINTER(C.c_int64)]),
-        "mpp_last_kernel_ms": (i32, [vp, C.POINTER(dbl)]),
-        "mpp_posnet_epilogue": (i32, [vp, i32, i32, i32, i32, vp, dbl, dbl, vp]),
-        "mpp_shapenet_epilogue": (i32, [vp, i32, i32, i32, i32, vp, vp]),
-        "mpp_affine_relu": (i32, [vp, vp, i32, i32, i64, i32, vp, vp]),
-        "mpp_posnet_epilogue_nhwc": (i32, [vp, i32, i32, i32, i32, vp, i32, dbl, dbl, vp]),
-        "mpp_shapenet_epilogue_nhwc": (i32, [vp, i32, i32, i32, i32, vp, i32, vp]),
-        "mpp_posnet_epilogue_win": (i32, [vp, i32, i32, i32, i32, vp, dbl, dbl, i32, i32, i32, i32, vp, i32]),
-        "mpp_shapenet_epilogue_win": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32]),
-        "mpp_posnet_epilogue_nhwc_win": (i32, [vp, i32, i32, i32, i32, vp, i32, dbl, dbl, i32, i32, i32, i32, vp, i32]),
-        "mpp_shapenet_epilogue_nhwc_win": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32]),
-        "mpp_shapenet_heads_win": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32]),
-        "mpp_nhwc_glue": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
-        "mpp_quad_iou": (i32, [vp, i32, vp, i32, vp, vp, i32]),
-        "mpp_detect_centers": (i32, [vp, i32, i32, i32, vp, dbl, i32, dbl, i32, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
-        "mpp_mark_classes": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
-        "mpp_train_batch": (i32, [vp, C.POINTER(TrainDataC), C.POINTER(TrainLabelsC), i32, i32, vp, i32, C.c_uint32, C.c_uint32,
-                                  C.c_uint32, C.POINTER(TrainOutC)]),
-        "mpp_posnet_loss": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
-        "mpp_shapenet_loss": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "mpp_philox4x32": (None, [vp, vp, vp]),
-        "mpp_image_histograms": (i32, [vp, C.POINTER(TrainDataC), vp]),
-        "mpp_train_set_histograms": (i32, [vp, vp, i32]),
-        "mpp_train_aug_params": (i32, [vp, i32, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, i32, vp]),
-        "mpp_posnet_error_map": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, dbl, vp, vp, vp]),
-        "mpp_density_prefix": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp]),
-        "mpp_density_anchors": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, C.c_uint32, vp]),
-        "mpp_rescale": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i64]),
-        "mpp_draw_outlines": (i32, [vp, i32, i32, vp, vp, dbl, dbl, vp, i32, vp, vp, vp]),
-        "mpp_abi_version": (i32, []),
-    }
-    for name, (res, args) in protos.items():
+    for name, (res, args) in PROTOTYPES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     if path == LIB_PATH:
@@ -546,31 +533,41 @@ class MppContext:
         self._check(self._L.mpp_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
-    # -- U-Net epilogues (device tensors) ---------------------------------------------------------
-    def posnet_epilogue(self, pos_out, H: int, W: int, div_w: float, div_b: float, det_out):
-        ldh, ldw = int(pos_out.shape[-2]), int(pos_out.shape[-1])
-        self._check(self._L.mpp_posnet_epilogue(self._h, H, W, ldh, ldw, _ptr(pos_out), float(div_w), float(div_b),
-                                                _ptr(det_out)))
+    # -- U-Net epilogues (device tensors).  Each writes the window at (wx0, wy0) of the H x W crop whose size is the destination's:
+    # a view of a larger map, e.g. ``det[a:a+h, b:b+w]``, or, at (0, 0), a dense [H,W] / [H,W,32] tensor for the whole crop ------
+    def posnet_epilogue(self, pos_out, H: int, W: int, div_w: float, div_b: float, det, *, wx0: int = 0, wy0: int = 0):
+        """``mpp_posnet_epilogue_win``: pos_out the crop's [3,ldh,ldw] float32 network output (contiguous); det an [h,w] float32
+        view with unit column stride."""
+        ldh, ldw = _planar_shape(pos_out, 3)
+        h, w, ld = _window_view(det, 1)
+        self._check(self._L.mpp_posnet_epilogue_win(self._h, H, W, ldh, ldw, _ptr(pos_out), float(div_w), float(div_b), int(wx0),
+                                                    int(wy0), h, w, _ptr(det), ld))
 
-    def shapenet_epilogue(self, logits, H: int, W: int, marks_out):
-        ldh, ldw = int(logits.shape[-2]), int(logits.shape[-1])
-        self._check(self._L.mpp_shapenet_epilogue(self._h, H, W, ldh, ldw, _ptr(logits), _ptr(marks_out)))
+    def shapenet_epilogue(self, logits, H: int, W: int, marks, *, wx0: int = 0, wy0: int = 0):
+        """``mpp_shapenet_epilogue_win``: logits one head's [32,ldh,ldw] float32 crop output (contiguous); marks an [h,w,32]
+        float32 view of a mark map with contiguous pixels."""
+        ldh, ldw = _planar_shape(logits, NCLASS)
+        h, w, ld = _window_view(marks, NCLASS)
+        self._check(self._L.mpp_shapenet_epilogue_win(self._h, H, W, ldh, ldw, _ptr(logits), int(wx0), int(wy0), h, w,
+                                                      _ptr(marks), ld))
 
-    def posnet_epilogue_nhwc(self, pos_out, H: int, W: int, div_w: float, div_b: float, det_out):
-        """``posnet_epilogue`` on a [1,3,Hp,Wp] channels-last (NHWC memory) float32 / bfloat16 network output"""
+    def posnet_epilogue_nhwc(self, pos_out, H: int, W: int, div_w: float, div_b: float, det, *, wx0: int = 0, wy0: int = 0):
+        """``posnet_epilogue`` on a [1,3,ldh,ldw] channels-last (NHWC memory) float32 / bfloat16 network output"""
         ldh, ldw, ch = nhwc_shape(pos_out)
         if ch != 3:
             raise ValueError("posnet output must have 3 channels")
-        self._check(self._L.mpp_posnet_epilogue_nhwc(self._h, H, W, ldh, ldw, _ptr(pos_out), int(pos_out.element_size()),
-                                                     float(div_w), float(div_b), _ptr(det_out)))
+        h, w, ld = _window_view(det, 1)
+        self._check(self._L.mpp_posnet_epilogue_nhwc_win(self._h, H, W, ldh, ldw, _ptr(pos_out), int(pos_out.element_size()),
+                                                         float(div_w), float(div_b), int(wx0), int(wy0), h, w, _ptr(det), ld))
 
-    def shapenet_epilogue_nhwc(self, logits, H: int, W: int, marks_out):
-        """``shapenet_epilogue`` on a [1,32,Hp,Wp] channels-last (NHWC memory) float32 / bfloat16 head output"""
+    def shapenet_epilogue_nhwc(self, logits, H: int, W: int, marks, *, wx0: int = 0, wy0: int = 0):
+        """``shapenet_epilogue`` on a [1,32,ldh,ldw] channels-last (NHWC memory) float32 / bfloat16 head output"""
         ldh, ldw, ch = nhwc_shape(logits)
         if ch != NCLASS:
             raise ValueError(f"a shapenet head must have {NCLASS} channels")
-        self._check(self._L.mpp_shapenet_epilogue_nhwc(self._h, H, W, ldh, ldw, _ptr(logits), int(logits.element_size()),
-                                                       _ptr(marks_out)))
+        h, w, ld = _window_view(marks, NCLASS)
+        self._check(self._L.mpp_shapenet_epilogue_nhwc_win(self._h, H, W, ldh, ldw, _ptr(logits), int(logits.element_size()),
+                                                           int(wx0), int(wy0), h, w, _ptr(marks), ld))
 
     def affine_relu(self, x, scale, shift):
         """x <- max(0, x * scale[c] + shift[c]) in place; x: contiguous NCHW float32 / bfloat16 CUDA tensor"""
@@ -623,68 +620,22 @@ class MppContext:
         self._check(self._L.mpp_conv3x3_stem(self._h, _ptr(x), h, w, _ptr(wp), _ptr(scale), _ptr(shift), _ptr(out)))
         return out
 
-    def shapenet_heads(self, h, w, b, H: int, W: int, marks):
-        """ShapeNet's three 1x1 heads + biases + softmax in one pass (``mpp_shapenet_heads``): h [1,32,ldh,ldw] float32
-        channels_last, w [3,32,32] (head, class, input channel), b [3,32]; marks: three [H,W,32] float32 CUDA tensors."""
+    def shapenet_heads(self, h, w, b, H: int, W: int, marks, *, wx0: int = 0, wy0: int = 0):
+        """ShapeNet's three 1x1 heads + biases + softmax in one pass (``mpp_shapenet_heads_win``): h [1,32,ldh,ldw] float32
+        channels_last, w [3,32,32] (head, class, input channel), b [3,32]; marks: three [h,w,32] float32 views of the mark maps
+        with the same shape and strides (the window at (wx0, wy0), as for the epilogues above)."""
         import torch
         ldh, ldw, c = nhwc_shape(h)
         if c != 32 or h.dtype != torch.float32 or tuple(w.shape) != (3, 32, 32) or tuple(b.shape) != (3, 32) or len(marks) != 3:
             raise ValueError("shapenet_heads: float32 channels-last activations of 32 channels, w [3,32,32], b [3,32]")
-        if not (w.is_contiguous() and b.is_contiguous() and all(m.is_contiguous() and tuple(m.shape) == (H, W, 32) for m in marks)):
-            raise ValueError("shapenet_heads: contiguous weights and [H,W,32] mark maps")
-        self._check(self._L.mpp_shapenet_heads(self._h, H, W, ldh, ldw, _ptr(h), _ptr(w), _ptr(b), _ptr(marks[0]), _ptr(marks[1]),
-                                               _ptr(marks[2])))
-
-    # -- window forms: the window (wx0, wy0, h x w) of an H x W crop, written through a view of a larger map --------------
-    def posnet_epilogue_win(self, pos_out, H: int, W: int, wx0: int, wy0: int, div_w: float, div_b: float, det_win):
-        """``posnet_epilogue`` of the crop ``pos_out`` ([3,ldh,ldw] float32, contiguous), restricted to the window at (wx0, wy0)
-        whose size is ``det_win``'s: det_win is an [h,w] float32 view with unit column stride, e.g. ``det[a:a+h, b:b+w]``."""
-        ldh, ldw = _planar_shape(pos_out, 3)
-        h, w, ld = _window_view(det_win, 1)
-        self._check(self._L.mpp_posnet_epilogue_win(self._h, H, W, ldh, ldw, _ptr(pos_out), float(div_w), float(div_b), int(wx0),
-                                                    int(wy0), h, w, _ptr(det_win), ld))
-
-    def shapenet_epilogue_win(self, logits, H: int, W: int, wx0: int, wy0: int, marks_win):
-        """``shapenet_epilogue`` of one head's crop logits ([32,ldh,ldw] float32, contiguous) into the window ``marks_win``:
-        an [h,w,32] float32 view of a mark map with contiguous pixels, e.g. ``marks[a:a+h, b:b+w]``."""
-        ldh, ldw = _planar_shape(logits, NCLASS)
-        h, w, ld = _window_view(marks_win, NCLASS)
-        self._check(self._L.mpp_shapenet_epilogue_win(self._h, H, W, ldh, ldw, _ptr(logits), int(wx0), int(wy0), h, w,
-                                                      _ptr(marks_win), ld))
-
-    def posnet_epilogue_nhwc_win(self, pos_out, H: int, W: int, wx0: int, wy0: int, div_w: float, div_b: float, det_win):
-        """``posnet_epilogue_win`` on a [1,3,ldh,ldw] channels-last float32 / bfloat16 network output"""
-        ldh, ldw, ch = nhwc_shape(pos_out)
-        if ch != 3:
-            raise ValueError("posnet output must have 3 channels")
-        h, w, ld = _window_view(det_win, 1)
-        self._check(self._L.mpp_posnet_epilogue_nhwc_win(self._h, H, W, ldh, ldw, _ptr(pos_out), int(pos_out.element_size()),
-                                                         float(div_w), float(div_b), int(wx0), int(wy0), h, w, _ptr(det_win), ld))
-
-    def shapenet_epilogue_nhwc_win(self, logits, H: int, W: int, wx0: int, wy0: int, marks_win):
-        """``shapenet_epilogue_win`` on a [1,32,ldh,ldw] channels-last float32 / bfloat16 head output"""
-        ldh, ldw, ch = nhwc_shape(logits)
-        if ch != NCLASS:
-            raise ValueError(f"a shapenet head must have {NCLASS} channels")
-        h, w, ld = _window_view(marks_win, NCLASS)
-        self._check(self._L.mpp_shapenet_epilogue_nhwc_win(self._h, H, W, ldh, ldw, _ptr(logits), int(logits.element_size()),
-                                                           int(wx0), int(wy0), h, w, _ptr(marks_win), ld))
-
-    def shapenet_heads_win(self, hid, w, b, H: int, W: int, wx0: int, wy0: int, marks_win):
-        """``shapenet_heads`` of the crop activations ``hid`` restricted to the window at (wx0, wy0); marks_win: three
-        [h,w,32] float32 views of the mark maps with the same shape and strides"""
-        import torch
-        ldh, ldw, c = nhwc_shape(hid)
-        if c != 32 or hid.dtype != torch.float32 or tuple(w.shape) != (3, 32, 32) or tuple(b.shape) != (3, 32) or len(marks_win) != 3:
-            raise ValueError("shapenet_heads_win: float32 channels-last activations of 32 channels, w [3,32,32], b [3,32]")
         if not (w.is_contiguous() and b.is_contiguous()):
-            raise ValueError("shapenet_heads_win: contiguous weights")
-        views = [_window_view(m, NCLASS) for m in marks_win]
+            raise ValueError("shapenet_heads: contiguous weights")
+        views = [_window_view(m, NCLASS) for m in marks]
         if len(set(views)) != 1:
-            raise ValueError("shapenet_heads_win: the three mark windows differ in shape or pitch")
-        h, wd, ld = views[0]
-        self._check(self._L.mpp_shapenet_heads_win(self._h, H, W, ldh, ldw, _ptr(hid), _ptr(w), _ptr(b), int(wx0), int(wy0), h, wd,
-                                                   _ptr(marks_win[0]), _ptr(marks_win[1]), _ptr(marks_win[2]), ld))
+            raise ValueError("shapenet_heads: the three mark windows differ in shape or pitch")
+        wh, ww, ld = views[0]
+        self._check(self._L.mpp_shapenet_heads_win(self._h, H, W, ldh, ldw, _ptr(h), _ptr(w), _ptr(b), int(wx0), int(wy0), wh, ww,
+                                                   _ptr(marks[0]), _ptr(marks[1]), _ptr(marks[2]), ld))
 
     # -- training the U-Nets (device tensors; asynchronous on the ctx's stream) -----------------------------------------
     def train_batch(self, data: TrainDataC, labels: TrainLabelsC, desc, P: int, flags: int, seed: int, epoch: int, batch: int,

@@ -323,7 +323,7 @@ class ScoreMapNets:
         return self._fold_cache[key][0]
 
     def _packed_heads(self):
-        """ShapeNet's heads as one [3,32,32] weight block and one [3,32] bias block for ``mpp_shapenet_heads`` (None unless
+        """ShapeNet's heads as one [3,32,32] weight block and one [3,32] bias block for ``mpp_shapenet_heads_win`` (None unless
         the heads are the reference's three Conv2d(32, 32, 1x1) and the MFMA kernels are on)."""
         key = (id(self.shp), "heads")
         if key not in self._fold_cache:
@@ -474,7 +474,7 @@ class ScoreMapNets:
 
             def pos_part():
                 pos_out = self._cl(self._head(self.pos.final_layer, self._backbone_nhwc(self.pos.backbone, xi)))
-                self.ctx.posnet_epilogue_nhwc_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
+                self.ctx.posnet_epilogue_nhwc(pos_out, H, W, self.div_w, self.div_b, det, wx0=wx0, wy0=wy0)
                 return pos_out
 
             def shp_part():
@@ -484,11 +484,11 @@ class ScoreMapNets:
                     # the three 1x1 heads, their biases and the softmax in ONE pass over h (csrc/mpp_conv.hip): 8.6 GB of
                     # traffic on a 4096 x 4096 image instead of 38 GB
                     h = self._cl(h)
-                    self.ctx.shapenet_heads_win(h, heads[0], heads[1], H, W, wx0, wy0, marks)
+                    self.ctx.shapenet_heads(h, heads[0], heads[1], H, W, marks, wx0=wx0, wy0=wy0)
                     return h
                 logits = [self._cl(self._head(fl[0], h)) for fl in self.shp.final_layers]
                 for k in range(3):
-                    self.ctx.shapenet_epilogue_nhwc_win(logits[k], H, W, wx0, wy0, marks[k])
+                    self.ctx.shapenet_epilogue_nhwc(logits[k], H, W, marks[k], wx0=wx0, wy0=wy0)
                 return logits
 
             if self.two_streams:
@@ -550,8 +550,8 @@ class ScoreMapNets:
         logits = [t[0].float().contiguous() for t in logits]
         wx0, wy0, det, marks = win or self._whole_window(H, W)
         self.ctx.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-        self.ctx.posnet_epilogue_win(pos_out, H, W, wx0, wy0, self.div_w, self.div_b, det)
+        self.ctx.posnet_epilogue(pos_out, H, W, self.div_w, self.div_b, det, wx0=wx0, wy0=wy0)
         for k in range(3):
-            self.ctx.shapenet_epilogue_win(logits[k], H, W, wx0, wy0, marks[k])
+            self.ctx.shapenet_epilogue(logits[k], H, W, marks[k], wx0=wx0, wy0=wy0)
         self._keep = (pos_out, logits)        # alive until the kernels on this stream have consumed them
         return det, marks

@@ -1,30 +1,31 @@
 #!/bin/bash
-# Did a change of the host plumbing or of a header reach the chain kernels?  Compiles the four chain-kernel files of two trees
-# to gfx950 assembly with build.py's flags, side by side, and prints per kernel the number of differing assembly lines and the
-# register / scratch / LDS figures of its metadata (parent -> this where they differ):
-#   bash profiles/tools/codeobj_diff.sh PARENT_TREE THIS_TREE [OUT_DIR]
+# Did a change of the host plumbing or of a header reach the kernels?  Compiles kernel files of two trees (default: the four
+# chain-kernel files; FILES: names without .hip, e.g. "mpp_maps mpp_train mpp_resample") to gfx950 assembly with build.py's flags,
+# side by side, and prints per kernel the number of differing assembly lines and the register / scratch / LDS figures of its
+# metadata (parent -> this where they differ):
+#   bash profiles/tools/codeobj_diff.sh PARENT_TREE THIS_TREE [OUT_DIR [FILES]]
 # PARENT_TREE: a checkout of the parent commit (git worktree add --detach ../parent HEAD~1).  The trees' paths enter the
 # assembly through the __hip_cuid_* symbols only: lines containing __hip_cuid are dropped.  With OUT_DIR the .s files are
 # kept there (and an existing OUT_DIR/parent is reused, not compiled again).  Exit status 1 when any line differs.
 set -e
-[ $# -ge 2 ] || { echo "usage: $0 PARENT_TREE THIS_TREE [OUT_DIR]" >&2; exit 2; }
+[ $# -ge 2 ] || { echo "usage: $0 PARENT_TREE THIS_TREE [OUT_DIR [FILES]]" >&2; exit 2; }
 parent=$(cd "$1" && pwd); this=$(cd "$2" && pwd)
 out=${3:-$(mktemp -d)}
 mkdir -p "$out"
 out=$(cd "$out" && pwd)
-files="mpp_sampler mpp_sampler_hbm mpp_deep mpp_hot"
+files=${4:-mpp_sampler mpp_sampler_hbm mpp_deep mpp_hot}
 pkg=mpp_cnn_rs_object_detection_amd
-flags=$(cd "$this/$pkg" && python3 -c 'import build; print(" ".join(build.FLAGS + build._CHAIN_FLAGS))')
+flags() { (cd "$this/$pkg" && python3 -c 'import build, sys; print(" ".join(build.FLAGS + build.EXTRA.get(sys.argv[1], [])))' $1.hip); }
 hipcc=${HIPCC:-/opt/rocm/bin/hipcc}
 compile() {   # tree, directory of the .s files
   mkdir -p "$2"
   for f in $files; do
-    ( cd "$1/$pkg/csrc" && $hipcc $flags --cuda-device-only -S $f.hip -o "$2/$f.s" 2> "$2/$f.log" ) &
+    ( cd "$1/$pkg/csrc" && $hipcc $(flags $f) --cuda-device-only -S $f.hip -o "$2/$f.s" 2> "$2/$f.log" ) &
   done
   wait
   for f in $files; do [ -s "$2/$f.s" ] || { echo "compiling $f.hip of $1 failed:" >&2; cat "$2/$f.log" >&2; exit 2; }; done
 }
-[ -n "$3" ] && [ -s "$out/parent/mpp_deep.s" ] || compile "$parent" "$out/parent"
+[ -n "$3" ] && [ -s "$out/parent/${files%% *}.s" ] || compile "$parent" "$out/parent"
 compile "$this" "$out/this"
 python3 - "$out" $files <<'EOF'
 import os, re, subprocess, sys, tempfile

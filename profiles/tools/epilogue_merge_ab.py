@@ -63,19 +63,19 @@ def digests(ctx):
                 ctx.posnet_epilogue(pos_out, H, W, *DIV, det)
                 ctx.shapenet_epilogue(logits, H, W, marks[0])
                 if win:
-                    ctx.posnet_epilogue_win(pos_out, H, W, wx0, wy0, *DIV, dw[1])
-                    ctx.shapenet_epilogue_win(logits, H, W, wx0, wy0, mw[0][1])
+                    ctx.posnet_epilogue(pos_out, H, W, *DIV, dw[1], wx0=wx0, wy0=wy0)
+                    ctx.shapenet_epilogue(logits, H, W, mw[0][1], wx0=wx0, wy0=wy0)
             elif form == "nhwc":
                 po, lg = cl(pos_out, dt), cl(logits, dt)
                 ctx.posnet_epilogue_nhwc(po, H, W, *DIV, det)
                 ctx.shapenet_epilogue_nhwc(lg, H, W, marks[0])
                 if win:
-                    ctx.posnet_epilogue_nhwc_win(po, H, W, wx0, wy0, *DIV, dw[1])
-                    ctx.shapenet_epilogue_nhwc_win(lg, H, W, wx0, wy0, mw[0][1])
+                    ctx.posnet_epilogue_nhwc(po, H, W, *DIV, dw[1], wx0=wx0, wy0=wy0)
+                    ctx.shapenet_epilogue_nhwc(lg, H, W, mw[0][1], wx0=wx0, wy0=wy0)
             else:
                 ctx.shapenet_heads(hid, wh, bh, H, W, marks)
                 if win:
-                    ctx.shapenet_heads_win(hid, wh, bh, H, W, wx0, wy0, [v for _, v in mw])
+                    ctx.shapenet_heads(hid, wh, bh, H, W, [v for _, v in mw], wx0=wx0, wy0=wy0)
             torch.cuda.synchronize()
             n = 3 if form == "heads" else 1
             if form != "heads":

@@ -232,7 +232,7 @@ def test_heads_window_form_equals_the_full_form_and_stays_inside_its_window(ctx,
     full = run_heads(ctx, hd, wd, bd, H, W)
     ox, oy = 3, 5
     dests = [torch.full((wh + 7, ww + 11, 32), SENTINEL, device="cuda") for _ in range(3)]
-    ctx.shapenet_heads_win(hd, wd, bd, H, W, wx0, wy0, [t[ox:ox + wh, oy:oy + ww] for t in dests])
+    ctx.shapenet_heads(hd, wd, bd, H, W, [t[ox:ox + wh, oy:oy + ww] for t in dests], wx0=wx0, wy0=wy0)
     torch.cuda.synchronize()
     for k, t in enumerate(dests):
         assert torch.equal(bits(t[ox:ox + wh, oy:oy + ww]), bits(full[k, wx0:wx0 + wh, wy0:wy0 + ww])), k

@@ -95,26 +95,26 @@ def test_window_epilogues_equal_the_full_crop_epilogue_bit_for_bit(modules, H, W
             t = t.clone(); t[ox:ox + h, oy:oy + w] = SENTINEL
             assert bool((t == SENTINEL).all()), (what, win, "written outside the window")
 
-        t, v = dest(1); ctx.posnet_epilogue_win(pos_out, H, W, wx0, wy0, -10.8, -2.1, v); check(ref["planar"][0], t, "posnet")
-        t, v = dest(32); ctx.shapenet_epilogue_win(logits, H, W, wx0, wy0, v); check(ref["planar"][1][0], t, "shapenet")
+        t, v = dest(1); ctx.posnet_epilogue(pos_out, H, W, -10.8, -2.1, v, wx0=wx0, wy0=wy0); check(ref["planar"][0], t, "posnet")
+        t, v = dest(32); ctx.shapenet_epilogue(logits, H, W, v, wx0=wx0, wy0=wy0); check(ref["planar"][1][0], t, "shapenet")
         for dt in (torch.float32, torch.bfloat16):
             full_d, full_m, po, lg = ref[dt]
-            t, v = dest(1); ctx.posnet_epilogue_nhwc_win(po, H, W, wx0, wy0, -10.8, -2.1, v); check(full_d, t, f"posnet nhwc {dt}")
-            t, v = dest(32); ctx.shapenet_epilogue_nhwc_win(lg, H, W, wx0, wy0, v); check(full_m[0], t, f"shapenet nhwc {dt}")
+            t, v = dest(1); ctx.posnet_epilogue_nhwc(po, H, W, -10.8, -2.1, v, wx0=wx0, wy0=wy0); check(full_d, t, f"posnet nhwc {dt}")
+            t, v = dest(32); ctx.shapenet_epilogue_nhwc(lg, H, W, v, wx0=wx0, wy0=wy0); check(full_m[0], t, f"shapenet nhwc {dt}")
         dests = [dest(32) for _ in range(3)]
-        ctx.shapenet_heads_win(hid, wh, bh, H, W, wx0, wy0, [v for _, v in dests])
+        ctx.shapenet_heads(hid, wh, bh, H, W, [v for _, v in dests], wx0=wx0, wy0=wy0)
         for k in range(3):
             check(hm[k], dests[k][0], f"heads {k}")
     # a window outside the crop is refused by the library, a destination that is not a window view by the binding
     t = torch.zeros((H + 1, W), device="cuda")
     with pytest.raises(hip_api.MppError, match="outside"):
-        ctx.posnet_epilogue_win(pos_out, H, W, 1, 0, -10.8, -2.1, t[:H])
+        ctx.posnet_epilogue(pos_out, H, W, -10.8, -2.1, t[:H], wx0=1, wy0=0)
     with pytest.raises(ValueError):
-        ctx.shapenet_epilogue_win(logits, H, W, 0, 0, torch.zeros((H, W, 16, 2), device="cuda"))
+        ctx.shapenet_epilogue(logits, H, W, torch.zeros((H, W, 16, 2), device="cuda"), wx0=0, wy0=0)
 
 
 def test_the_full_shapenet_epilogue_refuses_marks_off_a_16_byte_boundary():
-    """The full form runs the window kernel, whose float4 stores need aligned marks: a map 4 bytes into its storage is refused
+    """The whole-crop call runs the window kernel, whose float4 stores need aligned marks: a map 4 bytes into its storage is refused
     before any launch.  2 x 69: one full 64-pixel block (the 16-byte loads) plus a 5-pixel tail (the scalar loads)."""
     ctx = hip_api.MppContext(0)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)

@@ -286,7 +286,7 @@ def test_mfma_conv3x3_c32_equals_the_library_convolution(cin, H, W):
 @pytest.mark.gpu
 @pytest.mark.parametrize("H,W,ldh,ldw", [(64, 128, 64, 128), (37, 75, 48, 80), (5, 31, 16, 32), (130, 33, 144, 48)])
 def test_fused_shapenet_heads_equal_convolutions_and_softmax(H, W, ldh, ldw):
-    """``mpp_shapenet_heads`` (csrc/mpp_conv.hip): the three Conv2d(32, 32, 1x1) heads of shape_net.py:12-46 with their
+    """``mpp_shapenet_heads_win`` (csrc/mpp_conv.hip): the three Conv2d(32, 32, 1x1) heads of shape_net.py:12-46 with their
     biases and the softmax over the 32 classes in one pass, cropped from the padded activations [ldh][ldw] to [H][W] --
     against F.conv2d + torch.softmax in float32 (row lengths that are not multiples of the 32-pixel groups included)."""
     import torch.nn.functional as F

@@ -1,5 +1,5 @@
 """Float64 references of the three kernels of csrc/mpp_conv.hip (``k_conv3x3_c32``, ``k_conv3x3_stem``, ``k_shapenet_heads``,
-whose full form is its whole-crop window) with an error bound per output that is derived from the float32 format, not measured.  Plain torch
+the whole crop and windows of it) with an error bound per output that is derived from the float32 format, not measured.  Plain torch
 on the CPU; nothing of the library is imported.  tests/test_unet_conv_ref_host.py shows that the bounds hold for a
 float32 stand-in and that wrong kernels break them; tests/test_gpu_unet_conv_float64.py holds the kernels to them.
 
@@ -140,7 +140,7 @@ HEADS_C = 48
 
 
 def heads_ref(h, w, b, H, W):
-    """ShapeNet's three 1x1 heads + bias + softmax over the 32 classes as ``mpp_shapenet_heads`` defines them.
+    """ShapeNet's three 1x1 heads + bias + softmax over the 32 classes as ``mpp_shapenet_heads_win`` defines them.
 
     h [1, 32, ldh, ldw] (cropped to [H, W]), w [3, 32 class, 32 in], b [3, 32], float32 values.  Returns (logits, prob, bound),
     float64 [3, H, W, 32].  Derivation of the bound on a float32 kernel's probabilities:
