@@ -15,7 +15,8 @@
 //   C  every wave takes the same commit decision from those reports: steps commit in order; a committed change
 //      invalidates the later steps that could have seen it (same slot, same cell, within 2 * max_inter) and the round ends
 //      at the first invalid step; an accepted step that writes the bits that are already there changes nothing and ends
-//      nothing;
+//      nothing.  The decision needs no order (mpp_commit.hpp): the changing steps are dealt to the waves, each wave tests
+//      its steps against the later reports, and the first conflict any wave found ends the round;
 //   D  the few lanes whose step commits with a change evaluate it a second time, writing the cached reductions of the
 //      neighbours directly (no stash), and after a barrier move the point between cell lists and re-write its slot.
 // The depth of a round follows the number of steps the last rounds committed.  Temperatures are a function of the step
@@ -23,6 +24,7 @@
 #include <cstdlib>
 
 #include "mpp_chain.hpp"
+#include "mpp_commit.hpp"
 #include "mpp_prepass.hpp"
 #include "mpp_launch.hpp"
 
@@ -41,18 +43,7 @@
 #define DPH_ARGS
 #define DPH_PASS
 #endif
-// info word 0: bits 0..15 slot, then flags
-#define DI_VALID (1 << 16)
-#define DI_CHG (1 << 17)
-#define DI_HR (1 << 18)
-#define DI_HA (1 << 19)
-#define DI_BAD (1 << 20)     // the proposal could not be formed (reported when the commit reaches it)
-#define DI_ACC (1 << 21)
-#define DI_FULL (1 << 22)    // the cell the step adds to is full (capacity check, made against the round's start state)
-#define DI_NB (1 << 23)      // the step changes cached reductions of neighbours: committing it needs the second pass
-#define DI_NBOV (1 << 24)    // ... of more than two neighbours (their positions are not all reported)
-#define DI_NB2 (1 << 26)     // ... of at least two neighbours
-#define DI_RESC (1 << 25)    // the evaluation re-reduced a neighbour: it looked two interaction ranges away
+// (the bits of a step report, DI_*, and the pair test of the commit decision: mpp_commit.hpp)
 
 // ---- state mutation by ONE lane (energy_point_set.py:118-154); two steps that commit in the same round touch different
 // cells and slots
@@ -962,125 +953,123 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     __syncthreads();                            // (3)
     DPH(7);
 
-    // ---- C: which steps commit (every wave takes the same decision from the same reports).  Steps commit in order.  A
-    //      committed move / transform q makes a later report o untrustworthy when o read something q writes:
-    //      the slot itself; a rectangle within the interaction range of o's points, before or after (q's slot);
-    //      a neighbour whose cached reductions q changes and o used (q reports up to two of them; more: twice the range);
-    //      a cell list of o's 3 x 3 blocks (q crosses a cell border: the order of that cell's entries changes);
-    //      and, when o re-reduced a neighbour, anything within twice the range.  A birth / death ends the round.
+    // ---- C: which steps commit (every wave takes the same decision from the same reports; the rule and the pair test:
+    //      mpp_commit.hpp).  Steps commit in order; a committed move / transform q makes a later report o untrustworthy
+    //      when o read something q writes (commit_conflict).  The round ends at the first report that is invalid or that
+    //      a changing step before it conflicts with (s_end) -- or before that, at the first changing step that is a birth /
+    //      death or finds its cell full (t_end).  No pair test depends on the outcome of another: the changing steps that
+    //      can move s_end are dealt to the waves, each wave keeps the first report ITS steps conflict with, and the
+    //      minimum over the waves is s_end.
     uint4 o_[NCH];
     int or_[NCH];                               // reach radius of the report's rectangles
-    bool ok_[NCH];
-    unsigned long long am_[NCH], cm_[NCH];
+    unsigned long long am_[NCH];                // the changing steps
     const int nch = (lim + 63) >> 6;            // chunks in use
+    int first_inv = lim, t_end = lim;           // the first invalid report, the first changing step that ends the round
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-      o_[ch] = make_uint4(0u, 0u, 0u, 0u); or_[ch] = 0; ok_[ch] = false; am_[ch] = 0ull; cm_[ch] = 0ull;
+    for (int ch = NCH - 1; ch >= 0; --ch) {
+      o_[ch] = make_uint4(0u, 0u, 0u, 0u); or_[ch] = 0; am_[ch] = 0ull;
       if (ch < nch) {
         const int idx = ch * 64 + c.lane;
         const bool in = idx < lim;
         if (in) { o_[ch] = D.info[idx]; or_[ch] = (int)D.nb[idx].w; }
-        ok_[ch] = in && (o_[ch].x & DI_VALID);
-        am_[ch] = __ballot(in && (o_[ch].x & DI_CHG));
+        const unsigned f = o_[ch].x;
+        am_[ch] = __ballot(in && (f & DI_CHG));
+        const unsigned long long bm = __ballot(in && !(f & DI_VALID)), tm = __ballot(in && commit_terminal(f));
+        if (bm) first_inv = ch * 64 + __ffsll((long long)bm) - 1;
+        if (tm) t_end = ch * 64 + __ffsll((long long)tm) - 1;
       }
     }
-    int cur = 0;
     committed = 0; cur_n = n;
-    bool any_commit = false, any_apply = false;     // a step commits with a change; ... and changes reductions of neighbours
     const int range2 = c.pr0.maxd2 > c.pr1.maxd2 ? c.pr0.maxd2 : c.pr1.maxd2, far2 = P->conflict_d2;
-    while (true) {
-      int first_bad = lim;
+    // report i's flags (i < lim), from the chunk registers
+    auto flags_at = [&](int i) {
+      unsigned f = 0u;
 #pragma unroll
-      for (int ch = NCH - 1; ch >= 0; --ch)
-        if (ch < nch) {
-          const unsigned long long bm = ~__ballot(ok_[ch]) & low_mask(lim - ch * 64);
-          if (bm) first_bad = ch * 64 + __ffsll((long long)bm) - 1;
-        }
-      int wq = -1;
+      for (int ch = 0; ch < NCH; ++ch) if ((i >> 6) == ch) f = (unsigned)__builtin_amdgcn_readlane((int)o_[ch].x, i & 63);
+      return f;
+    };
+    // the changing steps that can move s_end: those below both ends (a conflict found by a later one lies beyond them)
+    const int bound = t_end < first_inv ? t_end : first_inv;
+    int nrel = 0;
 #pragma unroll
-      for (int ch = NCH - 1; ch >= 0; --ch)
-        if (ch < nch) {
-          const unsigned long long t = am_[ch] & ~low_mask(cur - ch * 64) & low_mask(first_bad - ch * 64);
+    for (int ch = 0; ch < NCH; ++ch) nrel += __popcll(am_[ch] & low_mask(bound - ch * 64));
+    int s_end = first_inv;
+    if (nrel > 0) {
+      // the k-th of them goes to wave k % WAVES.  (Also a single one: letting every wave test it itself saves the barrier,
+      // but measures no faster on the bench tile -- profiles/commit_split.md -- and costs the two-wave instantiation a
+      // dword of scratch.)
+      const bool deal = WAVES > 1;
+      int cur = 0;
+      for (int k = 0; k < nrel; ++k) {
+        int wq = -1;
+#pragma unroll
+        for (int ch = NCH - 1; ch >= 0; --ch) {
+          const unsigned long long t = am_[ch] & ~low_mask(cur - ch * 64) & low_mask(bound - ch * 64);
           if (t) wq = ch * 64 + __ffsll((long long)t) - 1;
         }
-      if (wq < 0) {
-        committed = first_bad;
-        if (first_bad < lim && (D.info[first_bad].x & DI_BAD)) err = ERR_BAD_TARGET;
-        // otherwise: invalidated by an earlier commit of this round -> evaluated again next round
-        break;
-      }
-      const uint4 q = D.info[wq];                          // (one address for the wave: a broadcast read)
-      const int qf = (int)q.x;
-      const bool q_hr = qf & DI_HR, q_ha = qf & DI_HA;
-      // capacity checks BEFORE anything of the step is applied: the chain stops in the state before it (see mpp_sampler.hip)
-      // (the evaluating lane looked at the cell's count: no state is read here, see "stage")
-      if (qf & DI_FULL) { err = ERR_CELL_OVERFLOW; committed = wq; break; }
-      if (!(q_hr && q_ha)) {                               // death / birth: ends the round (n and order[] change)
-        if (q_hr) cur_n -= 1;
-        else if (cur_n >= cap) { err = ERR_POINT_OVERFLOW; committed = wq; break; }
-        else cur_n += 1;
+        cur = wq + 1;
+        if (deal && (k & (WAVES - 1)) != c.wave) continue;
+        // q's report from the lane that holds it (no LDS read whose address waits for the ballots); its neighbour word
+        // is in no register: one broadcast read
+        uint4 q = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) if ((wq >> 6) == ch) cm_[ch] |= 1ull << (wq & 63);
-        any_commit = true;
-        if (qf & DI_NBOV) any_apply = true;
-        committed = wq + 1;
-        break;
-      }
+        for (int ch = 0; ch < NCH; ++ch)
+          if ((wq >> 6) == ch)
+            q = make_uint4((unsigned)__builtin_amdgcn_readlane((int)o_[ch].x, wq & 63), (unsigned)__builtin_amdgcn_readlane((int)o_[ch].y, wq & 63),
+                           (unsigned)__builtin_amdgcn_readlane((int)o_[ch].z, wq & 63), (unsigned)__builtin_amdgcn_readlane((int)o_[ch].w, wq & 63));
+        const uint4 qn = D.nb[wq];
 #pragma unroll
-      for (int ch = 0; ch < NCH; ++ch) if ((wq >> 6) == ch) cm_[ch] |= 1ull << (wq & 63);
-      any_commit = true;
-      if (qf & DI_NBOV) any_apply = true;
-      // is a later report still trustworthy after this move / transform?
-      const int q_ts = qf & 0xffff;
-      const int qx[2] = {(int)(q.y & 0xffffu), (int)(q.z & 0xffffu)}, qy[2] = {(int)(q.y >> 16), (int)(q.z >> 16)};
-      const int qci[2] = {(int)(q.w & 0xffu), (int)((q.w >> 16) & 0xffu)}, qcj[2] = {(int)((q.w >> 8) & 0xffu), (int)(q.w >> 24)};
-      const bool q_cross = qci[0] != qci[1] || qcj[0] != qcj[1];
-      const bool q_far = (qf & DI_NBOV) != 0;
-      int qnx[2] = {0, 0}, qny[2] = {0, 0}, qnr[2] = {0, 0}, q_nnb = 0;
-      const uint4 qn = D.nb[wq];
-      const int q_r = (int)qn.w;
-      if (qf & DI_NB) {
-        qnx[0] = (int)(qn.x & 0xffffu); qny[0] = (int)(qn.x >> 16); qnx[1] = (int)(qn.y & 0xffffu); qny[1] = (int)(qn.y >> 16);
-        qnr[0] = (int)(qn.z & 0xffu); qnr[1] = (int)((qn.z >> 8) & 0xffu);
-        q_nnb = 1;
-      }
-      const bool q_nb2 = (qf & DI_NB2) != 0;
-#pragma unroll
-      for (int ch = 0; ch < NCH; ++ch) {
-        const int idx = ch * 64 + c.lane;
-        if (ch < nch && ch * 64 + 63 > wq && idx > wq && ok_[ch]) {
-          const uint4 o = o_[ch];
-          const int of = (int)o.x;
-          const bool oh[2] = {(of & DI_HR) != 0, (of & DI_HA) != 0};
-          const int ox[2] = {(int)(o.y & 0xffffu), (int)(o.z & 0xffffu)}, oy[2] = {(int)(o.y >> 16), (int)(o.z >> 16)};
-          const int oci[2] = {(int)(o.w & 0xffu), (int)((o.w >> 16) & 0xffu)}, ocj[2] = {(int)((o.w >> 8) & 0xffu), (int)(o.w >> 24)};
-          // how far two rectangles can see each other: the alignment term its range, the overlap term as far as the
-          // circumscribed circles meet (radii rounded up, + 1 px for the rounding and the 1e-7 of the circle test), neither
-          // beyond the terms' cut-off
-          const int o_r = or_[ch];
-          auto reach2 = [&](int ra, int rb) { const int t = (ra + rb + 1) * (ra + rb + 1), a2 = c.pr1.maxd2; const int m = t > a2 ? t : a2; return m < range2 ? m : range2; };
-          const int lim2 = ((of & (DI_RESC | DI_NBOV)) || q_far) ? far2 : reach2(o_r, q_r);
-          bool bad = oh[0] && (of & 0xffff) == q_ts;
-#pragma unroll
-          for (int a = 0; a < 2; ++a)
-            if (oh[a]) {
-#pragma unroll
-              for (int b = 0; b < 2; ++b) {
-                const int dx = ox[a] - qx[b], dy = oy[a] - qy[b];
-                if (dx * dx + dy * dy <= lim2) bad = true;
-                if (q_cross && abs(oci[a] - qci[b]) <= 1 && abs(ocj[a] - qcj[b]) <= 1) bad = true;
-              }
-              if (q_nnb > 0) {
-                const int dx0 = ox[a] - qnx[0], dy0 = oy[a] - qny[0];
-                if (dx0 * dx0 + dy0 * dy0 <= reach2(o_r, qnr[0])) bad = true;
-                const int dx1 = ox[a] - qnx[1], dy1 = oy[a] - qny[1];
-                if (q_nb2 && dx1 * dx1 + dy1 * dy1 <= reach2(o_r, qnr[1])) bad = true;
-              }
-            }
-          if (bad) ok_[ch] = false;
+        for (int ch = 0; ch < NCH; ++ch) {
+          // (the chunks behind q, and not beyond what is known to end the round)
+          if (ch < nch && ch * 64 + 63 > wq && ch * 64 < s_end && ch * 64 <= bound) {
+            const int idx = ch * 64 + c.lane;
+            bool bad = false;
+            if (idx > wq && (o_[ch].x & DI_VALID)) bad = commit_conflict(q, qn, o_[ch], or_[ch], range2, far2, c.pr1.maxd2);
+            const unsigned long long b = __ballot(bad);
+            if (b) { const int o = ch * 64 + __ffsll((long long)b) - 1; s_end = o < s_end ? o : s_end; }
+          }
         }
       }
-      cur = wq + 1;
+      if constexpr (WAVES > 1) {
+        if (deal) {
+          // The waves' minima meet in L.sh[8 + wave].  The round loop has no other use for L.sh (the kernel reads sh[1]
+          // once, before the loop), so the only writer of these words is this line, and between two of its executions
+          // every wave passes the barrier below and then (1) and (3) of the next round: a wave cannot write its word for the
+          // next round while a slow one still reads this round's -- whichever way the fast one leaves C, into the next
+          // round's A or into stage 0.  nrel is the same in every wave: they all take the barrier or none does.
+          DPH(18);
+          if (c.lane == 0) L.sh[8 + c.wave] = s_end;
+          __syncthreads();                      // (5)
+          DPH(19);
+#pragma unroll
+          for (int w = 0; w < WAVES; ++w) {
+            const int v = __builtin_amdgcn_readfirstlane(L.sh[8 + w]);
+            s_end = v < s_end ? v : s_end;
+          }
+        }
+      }
+    }
+    if (t_end < s_end) {                        // the commit reaches step t_end: it decides
+      // capacity checks BEFORE anything of the step is applied: the chain stops in the state before it (see mpp_sampler.hip)
+      // (the evaluating lane looked at the cell's count: no state is read here, see "stage")
+      const unsigned tf = flags_at(t_end);
+      if (tf & DI_FULL) { err = ERR_CELL_OVERFLOW; committed = t_end; }
+      else if (tf & DI_HR) { cur_n -= 1; committed = t_end + 1; }             // death / birth: ends the round (n and order[] change)
+      else if (cur_n >= cap) { err = ERR_POINT_OVERFLOW; committed = t_end; }
+      else { cur_n += 1; committed = t_end + 1; }
+    } else {
+      committed = s_end;
+      if (s_end < lim && (flags_at(s_end) & DI_BAD)) err = ERR_BAD_TARGET;
+      // otherwise: invalidated by an earlier commit of this round -> evaluated again next round
+    }
+    bool any_commit = false, any_apply = false;     // a step commits with a change; ... and changes reductions of neighbours
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const unsigned long long cm = am_[ch] & low_mask(committed - ch * 64);      // the changing steps that commit
+      if (cm) {
+        any_commit = true;
+        if (__ballot((o_[ch].x & DI_NBOV) != 0u) & cm) any_apply = true;
+      }
     }
 
     if constexpr (QUE) {                        // the entries the round committed leave the queues
@@ -1094,7 +1083,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     my_commit = false;
     if (mine) {
 #pragma unroll
-      for (int ch = 0; ch < NCH; ++ch) if ((myoff >> 6) == ch) my_commit = (cm_[ch] >> (myoff & 63)) & 1ull;
+      for (int ch = 0; ch < NCH; ++ch) if ((myoff >> 6) == ch) my_commit = myoff < committed && ((am_[ch] >> (myoff & 63)) & 1ull);
     }
     if (DIAG && tracing && mine && myoff < committed) {
       const long long idx = tr0 + done + myoff;
