@@ -671,6 +671,59 @@ def make_classics_golden():
     print("classics_golden.npz:", len(R), "rectangles;", {k: v.shape for k, v in out.items() if hasattr(v, "shape")})
 
 
+def make_classics_edge_golden():
+    """The classic image energies run by the reference on the rectangles of tests/classics_cases.py: long thin ones whose
+    pixel grid steps through 64 rows / columns, pushed over the borders and into the corners of a 150 x 200 noise picture,
+    under every mask recipe (dilation, gap, erode) of ``classics_cases.RECIPES``.  The picture is handed over as float64
+    (exactly the float32 values the tests build), so the reference computes in float64.  Recorded: the values of the six
+    contrast measures for every recipe, rgb and grey; the gradient values, rgb and grey; outlines and normals; the fill
+    and rim masks of ``classics_cases.MASK_RECIPES``."""
+    from models.mpp.energies.classics import ContrastEnergy, GradientEnergy
+    sys.path.insert(3, os.path.join(REPO, "tests"))
+    import classics_cases as CC
+
+    img64 = CC.picture().astype(np.float64)
+    grey64 = np.repeat(CC.grey_picture().astype(np.float64)[..., None], 3, axis=-1)   # rgb=False: its channel mean is the grey picture
+    assert np.array_equal(np.mean(grey64, axis=-1), CC.grey_picture().astype(np.float64))
+    R = [Rectangle(x, y, size=s, ratio=r, angle=a) for x, y, s, r, a in CC.ALL_CASES]
+    out = {"rects": np.array([[u.x, u.y, u.size, u.ratio, u.angle] for u in R], dtype=np.float64),
+           "n_cases32": np.array(len(CC.CASES)), "recipes": np.array(CC.RECIPES, dtype=np.int32)}
+    assert np.array_equal(out["rects"], CC.rect_array(CC.ALL_CASES))
+    for tag, image, rgb in (("rgb", img64, True), ("grey", grey64, False)):
+        for t in CC.MEASURES:
+            vals = np.zeros((len(CC.RECIPES), len(R)))
+            for k, (dil, gap, ero) in enumerate(CC.RECIPES):
+                e = ContrastEnergy(name="c", image=image, dilation=dil, gap=gap, erode=ero, contrast_measure_type=t, rgb=rgb,
+                                   thresh=0.25)
+                with np.errstate(all="ignore"):
+                    vals[k] = [float(e.compute(u)) for u in R]
+            out[f"values_{tag}_{t}"] = vals
+        g = GradientEnergy(name="g", image=image, dilation=1, rgb=rgb, thresh=0.1)
+        with np.errstate(all="ignore"):
+            out[f"gradient_{tag}"] = np.array([g.compute(u) for u in R])
+    for dil, gap, ero in CC.MASK_RECIPES:
+        e = ContrastEnergy(name="c", image=img64, dilation=dil, gap=gap, erode=ero, contrast_measure_type="mean", rgb=True)
+        fills, rims = [], []
+        for u in R:
+            f, r = e.compute_masks(u)
+            f = np.asarray(f).T.astype(np.int16).reshape(-1, 2)
+            r = np.asarray(r).T.astype(np.int16).reshape(-1, 2) if len(f) else np.zeros((0, 2), np.int16)
+            fills.append(f[np.lexsort((f[:, 1], f[:, 0]))]); rims.append(r[np.lexsort((r[:, 1], r[:, 0]))])
+        key = f"{dil}{gap}{ero}"
+        out[f"fill_{key}"] = np.concatenate(fills); out[f"fill_off_{key}"] = np.cumsum([0] + [len(f) for f in fills])
+        out[f"rim_{key}"] = np.concatenate(rims); out[f"rim_off_{key}"] = np.cumsum([0] + [len(r) for r in rims])
+    g = GradientEnergy(name="g", image=img64, dilation=1, rgb=True, thresh=0.1)
+    outl, nrm = [], []
+    for u in R:
+        per, n3 = g.compute_outline_and_normal(u)
+        outl.append(np.asarray(per).T.astype(np.int16).reshape(-1, 2)); nrm.append(np.asarray(n3, dtype=np.float64).reshape(-1, 2))
+    out["outline"] = np.concatenate(outl); out["normals"] = np.concatenate(nrm)
+    out["outline_off"] = np.cumsum([0] + [len(o) for o in outl])
+    path = os.path.join(HERE, "classics_edge_golden.npz")
+    np.savez_compressed(path, **out)
+    print("classics_edge_golden.npz:", len(R), "rectangles,", os.path.getsize(path) // 1024, "KiB")
+
+
 def make_contrast_tape():
     """A chain of the reference sampler under the CONTRAST energy setup (energy_setup_contrast.py:29-105, craciun2 measure,
     manual hierarchical combinator with the contrast term gating the priors) on a 96x96 tile whose picture shows the
@@ -726,7 +779,7 @@ def make_tapes_256():
 
 
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["tapes", "delta", "unet", "pert", "dota", "host", "tapes256", "classics"]
+    what = sys.argv[1:] or ["tapes", "delta", "unet", "pert", "dota", "host", "tapes256", "classics", "classics_edges"]
     if "pert" in what:
         make_perturbation_golden()
     if "tapes" in what:
@@ -747,3 +800,5 @@ if __name__ == "__main__":
         make_classics_golden()
     if "contrast_tape" in what or "classics" in what:
         make_contrast_tape()
+    if "classics_edges" in what:
+        make_classics_edge_golden()
