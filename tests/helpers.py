@@ -255,3 +255,20 @@ def lockstep_vs_oracle(ctx, o, total_steps: int, seed: int, chain: int, alpha: f
             start = s + 1
         done += n
     return ties
+
+
+def worst_differences(ctx, o, total_steps: int, seed: int, chain: int) -> dict:
+    """One traced run of ``ctx`` followed by the oracle ``o`` (both at the same start): the largest relative difference of
+    fwd and of bwd, the largest absolute difference of dE and the largest one in units of max(1, |dE|) -- the figures behind
+    the bars of ``lockstep_vs_oracle``, for a report; asserts nothing.  Only for runs that lockstep passed without a tie."""
+    gout, gprops = ctx.run(total_steps, seed=seed, chain0=chain, trace_tile=0)
+    oout, _ = o.follow(gprops, seed, chain)
+    worst = {}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for f in ("fwd", "bwd"):
+            rel = np.abs(gout[f] - oout[f]) / np.abs(oout[f])
+            worst[f] = float(np.nanmax(np.where(gout[f] == oout[f], 0.0, rel)))
+        d = np.abs(gout["dE"] - oout["dE"])
+        worst["dE abs"] = float(np.nanmax(np.append(d, 0.0)))
+        worst["dE / max(1, |dE|)"] = float(np.nanmax(np.append(d / np.maximum(1.0, np.abs(oout["dE"])), 0.0)))
+    return worst
