@@ -86,6 +86,9 @@ def rescale_tables(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
 def rescale_image_tables(H: int, W: int, scale: float):
     """(oh, ow) and the (row_idx, row_w, col_idx, col_w) of ``MppContext.rescale`` for an H x W image"""
     oh, ow = rescale_output_shape(H, W, scale)
+    if not (0 < oh <= H and 0 < ow <= W):
+        raise ValueError(f"rescale: a {H} x {W} picture at scale {scale:.6g} would become {oh} x {ow}: "
+                         + ("it is too small for that scale" if oh <= 0 or ow <= 0 else "only reductions are built"))
     return (oh, ow), rescale_tables(H, oh) + rescale_tables(W, ow)
 
 
