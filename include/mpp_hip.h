@@ -228,7 +228,10 @@ int mpp_papangelou(mpp_ctx *ctx, int tile, double *dE);
  * points than the device walk takes (8192): merge that image on the host. */
 int mpp_merge_score(mpp_ctx *ctx, double distance, int cap, int32_t *n_out, int32_t *xy, double *marks, double *dE,
                     int32_t *n_removed);
-/* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points */
+/* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points.  Candidates are
+ * det >= (float)threshold (float32, as NumPy compares); rank and NMS rule as mpp_detect_centers below.  A tile that keeps more
+ * than point_capacity points: -12 ("naive init, tile t"), its first point_capacity picks stay stored; every call replaces
+ * the tiles' configurations and error codes, so a later call that fits succeeds. */
 int mpp_naive_init(mpp_ctx *ctx, double threshold, double nms_distance);
 
 /* RJMCMC (rjmcmc_sampler/rjmcmc.py:52-187, sample_rjmcmc.py:38-102) ------------- */
@@ -326,7 +329,7 @@ int mpp_quad_iou(mpp_ctx *ctx, int n, const double *a, int m, const double *b, d
  * are device pointers; n_candidates / n_kept are host pointers; the ctx's stream, synchronous up to the last kernel.
  *  - candidates: det > (float)threshold when strict (PosNet), det >= (float)threshold otherwise (ShapeNet's PosNet call,
  *    naive_detection) -- a float32 compare against the threshold rounded to float32, as NumPy compares a float32 array
- *    with a Python float (k_naive_init's compare is in double and is not this one);
+ *    with a Python float (mpp_naive_init's compare is the same one);
  *  - rank: value descending, ties toward the larger row-major flat index r*W + c (-0 ties with +0);
  *  - NMS: in rank order a candidate is kept iff every kept candidate ranked above it lies at sqrt(dx^2+dy^2) > nms_distance
  *    (double; utils/nms.py:68-110), 0 <= nms_distance <= 32 (else -1);

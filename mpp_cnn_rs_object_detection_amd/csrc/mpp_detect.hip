@@ -20,19 +20,13 @@
 #include <cstdio>
 
 #include "mpp_detect.hpp"
+#include "mpp_rank_key.hpp"
 
 namespace {
 
 enum : uint8_t { ST_NONE = 0, ST_UNDEC = 1, ST_KEPT = 2, ST_REMOVED = 3 };
 constexpr int TILE = 64;
 constexpr int RES_THREADS = 256;
-
-// float -> uint32 that orders like the value for every finite float (and +-inf); -0 is folded onto +0 so that equal
-// values tie on the index alone
-__device__ __forceinline__ uint32_t ordered_bits(float v) {
-  const uint32_t b = __float_as_uint(v == 0.f ? 0.f : v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 // state of every pixel, the candidate count, and a flag per 64 x 64 tile that holds a candidate
 __global__ __launch_bounds__(256) void k_detect_init(const float *det, int H, int W, int ld, float thr, int strict, uint8_t *state,

@@ -10,6 +10,7 @@
 //    contiguous) are fully coalesced (shape_net_model.py:139-141 + data_loaders.py:54).
 #include "mpp_device.hpp"
 #include "mpp_launch.hpp"
+#include "mpp_rank_key.hpp"
 #include "mpp_unet_math.hpp"
 
 // ---- birth CDF ---------------------------------------------------------------------------------
@@ -69,8 +70,11 @@ extern "C" void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, in
 }
 
 // ---- naive detection ------------------------------------------------------------------------------
-// keys: (float bits << 32) | flat index ; det >= 0 so the bit pattern orders like the value; ties go to
-// the larger index (the convention of the CPU oracle)
+// candidates: det >= (float)threshold, compared in float32 -- what NumPy does for a float32 map against a Python float
+// (a pixel equal to float32(thr) is a candidate even where float32(thr) < thr), as k_detect_init does.
+// keys: (ordered_bits(value) << 32) | flat index (mpp_rank_key.hpp): orders like the value for negative values and -0.0
+// too; ties go to the larger index (the convention of the CPU oracle).  No live candidate has key 0: 0 marks a suppressed
+// entry, and a maximum of 0 means that none is left.
 __global__ __launch_bounds__(256) void k_naive_init(const DevParams *P, const TileRef *tiles, double threshold,
                                                     double nms_dist, unsigned long long *cand_all, int cand_cap) {
   __shared__ unsigned long long best[256];
@@ -78,13 +82,14 @@ __global__ __launch_bounds__(256) void k_naive_init(const DevParams *P, const Ti
   TileRef t = tiles[blockIdx.x];
   unsigned long long *cand = cand_all + (size_t)blockIdx.x * cand_cap;
   const int hw = P->H * P->W;
+  const float thr = (float)threshold;
   if (threadIdx.x == 0) s_count = 0;
   __syncthreads();
   for (int i = threadIdx.x; i < hw; i += blockDim.x) {
     float v = t.det[i];
-    if ((double)v >= threshold) {
+    if (v >= thr) {
       int k = atomicAdd(&s_count, 1);
-      if (k < cand_cap) cand[k] = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned int)i;
+      if (k < cand_cap) cand[k] = ((unsigned long long)ordered_bits(v) << 32) | (unsigned int)i;
     }
   }
   __syncthreads();
@@ -124,7 +129,8 @@ __global__ __launch_bounds__(256) void k_naive_init(const DevParams *P, const Ti
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) { *t.n = min(n_out, P->cap); if (err) *t.err = err; }
+  // (the configuration is replaced: a code left by an earlier overflow or chain stop has no meaning for the new one)
+  if (threadIdx.x == 0) { *t.n = min(n_out, P->cap); *t.err = err; }
 }
 extern "C" void mpp_launch_naive_init(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles,
                                       double threshold, double nms_dist, unsigned long long *cand, int cand_cap) {

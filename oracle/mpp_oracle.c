@@ -1082,7 +1082,9 @@ int orc_run(orc_ctx *c, int64_t n_steps, uint64_t seed, uint32_t chain, orc_step
   return 0;
 }
 
-/* sample_rjmcmc.py:23-35 + utils/nms.py:68-110.  Ties broken towards the larger flat index. */
+/* sample_rjmcmc.py:23-35 + utils/nms.py:68-110.  Ties broken towards the larger flat index.  The threshold compare is
+   in float32: the reference compares a float32 map with a Python float, which NumPy does in float32, so a pixel equal
+   to float32(thr) is a candidate even where float32(thr) < thr (0.7, the shipped 0.6464646464646465). */
 typedef struct { float s; int idx; } cand_t;
 static int cand_cmp(const void *a, const void *b) {
   const cand_t *p = (const cand_t *)a, *q = (const cand_t *)b;
@@ -1092,9 +1094,10 @@ static int cand_cmp(const void *a, const void *b) {
 int orc_naive_detection(orc_ctx *c, double threshold, double nms_dist, int cap, int32_t *xy, double *marks) {
   size_t hw = (size_t)c->H * c->W;
   int nc = 0;
+  const float thr = (float)threshold;
   cand_t *cand = (cand_t *)malloc(sizeof(cand_t) * hw);
   for (size_t i = 0; i < hw; ++i)
-    if ((double)c->det[i] >= threshold) { cand[nc].s = c->det[i]; cand[nc].idx = (int)i; ++nc; }
+    if (c->det[i] >= thr) { cand[nc].s = c->det[i]; cand[nc].idx = (int)i; ++nc; }
   qsort(cand, nc, sizeof(cand_t), cand_cmp);
   int n_out = 0;
   while (nc > 0) {
