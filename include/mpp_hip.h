@@ -228,6 +228,34 @@ int mpp_papangelou(mpp_ctx *ctx, int tile, double *dE);
  * points than the device walk takes (8192): merge that image on the host. */
 int mpp_merge_score(mpp_ctx *ctx, double distance, int cap, int32_t *n_out, int32_t *xy, double *marks, double *dE,
                     int32_t *n_removed);
+/* The birth-energy map: for every pixel c = (x, y) of every chain t of the ctx, the energy change of adding the rectangle
+ * ShapeNet proposes there, dE(c) = E(X + u_c) - E(X) -- the conditional (Papangelou) intensity surface exp(-dE) of the
+ * point process, evaluated where there is NO detection (the reference's utils/figures/ show_papangelou).  X is the state
+ * mpp_get_points_all reads (after mpp_set_points or mpp_run), on the maps of tile t % n_tiles.
+ *   candidate  u_c = (x, y, edges[0][c0], edges[1][c1], edges[2][c2]) with ck the argmax class of mark map k at c by the rule of
+ *              mpp_mark_classes (first maximum, a NaN wins) and edges the lower bin edges of mpp_mappings
+ *              (ValueMapping.class_to_value, cnn_detection.mark_values);
+ *   value      dE(c) = e(u_c | X + u_c) + sum over the slots v with d(v, c) <= max_inter of [ e(v | X + u_c) - e(v | X) ],
+ *              every e(. | .) the point energy of mpp_total_energy / mpp_delta_batch for that point in that configuration;
+ *   order      the neighbour differences are added in ASCENDING SLOT ORDER to a float64 that starts at 0.0, then e(u_c | .)
+ *              is added: a pixel's value does not depend on launch shape, number of tiles or replicas, bit for bit;
+ *   a point already on c is a neighbour like any other (d = 0).
+ * The pair reductions are max / min, so red_v(X + u_c) = reduce(red_v(X), pair(v, u_c)) is the from-scratch reduction bit for
+ * bit: a pre-pass caches every point's unit part, reductions and energy in X (workspace of the ctx, grown on demand; it
+ * honours "scratch_grid_min_points"), the map kernel stages the cached points near a block of pixels in LDS,
+ * MPP_BIRTH_CHUNK at a time, and walks them in slot order.
+ * dE [n_chains][H][W] float64 and marks_or_null [n_chains][H][W][3] float64 (the candidates' size, ratio, angle): DEVICE
+ * pointers, borrowed; summary_or_null [n_chains]: HOST.  Runs on the ctx's stream; returns when summary (if given) is filled,
+ * otherwise asynchronous.  Summary of a chain: min_dE the smallest non-NaN value (finite or infinite), (x, y) its pixel, ties
+ * to the smallest row-major index x * W + y; n_negative the pixels with dE < 0; n_nan the pixels whose value is NaN; all
+ * values NaN: min_dE = +inf, (x, y) = (-1, -1).
+ * -1 with a message: no maps or no model; a model with a classic image energy (MPP_U_CONTRAST, MPP_U_GRADIENT: a candidate per
+ * pixel would need a rasterised footprint per pixel); more than 65535 chains.  The kernel mixture is not read.
+ * Read-only option "birth_map_grid": the last call's pre-pass built candidate grids (its chains of at least
+ * "scratch_grid_min_points" points took their neighbours from them, the others scanned). */
+#define MPP_BIRTH_CHUNK 256        /* points staged per pass of a block */
+typedef struct { double min_dE; int32_t x, y; int64_t n_negative, n_nan; } mpp_birth_summary;
+int mpp_birth_energy_map(mpp_ctx *ctx, double *dE, double *marks_or_null, mpp_birth_summary *summary_or_null);
 /* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points.  Candidates are
  * det >= (float)threshold (float32, as NumPy compares); rank and NMS rule as mpp_detect_centers below.  A tile that keeps more
  * than point_capacity points: -12 ("naive init, tile t"), its first point_capacity picks stay stored; every call replaces

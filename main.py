@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Command-line entry, same flags as the reference's ``main.py:11-109``:
 
-    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures]
-    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures]
+    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map]
+    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
 hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the CNN-only baseline's detections (DOTA hbb /
@@ -61,6 +61,10 @@ def build_parser():
     parser.add_argument("--figures", action="store_true",
                         help="(-m mpp, infer / infereval / detect) write the result pictures composed on the GPU: NNNN_detection.png, "
                              "NNNN_gt.png (and NNNN_detection_map.png) beside NNNN_results.pkl; same as inference.figures in the config")
+    parser.add_argument("--birth-map", action="store_true",
+                        help="(-m mpp, infer / infereval / detect) per image the birth-energy map under its detections -- the energy "
+                             "change of a new object at every pixel: NNNN_birth_energy.png, the key birth_summary of the pickle and "
+                             "one log line; same as inference.birth_map in the config")
     parser.add_argument("--images", nargs="+", default=None, metavar="PATH",
                         help="(-p detect) image files, or directories whose image files are taken in sorted order")
     parser.add_argument("--out", default=None, metavar="DIR", help="(-p detect) where the results go")
@@ -103,6 +107,8 @@ def main():
         detect.resolve_scale(args.gsd, args.model_gsd)          # (a coarser picture is refused before anything is loaded)
         if args.restarts is not None:
             config.setdefault("inference", {})["restarts"] = args.restarts
+        if args.birth_map:
+            config.setdefault("inference", {})["birth_map"] = True
         model = MPPModel(config, phase="val", load=True, device=local_rank,
                          nets=load_nets(config, local_rank, args.unet_max_pixels), spec_waves=args.spec_waves)
         detect.detect_files(model, args.images, args.out, gsd=args.gsd, model_gsd=args.model_gsd, min_score=args.min_score,
@@ -116,6 +122,8 @@ def main():
             config.setdefault("inference", {})["restarts"] = args.restarts
         if args.figures:
             config.setdefault("inference", {})["figures"] = True
+        if args.birth_map and args.procedure in ("infer", "infereval"):
+            config.setdefault("inference", {})["birth_map"] = True
         nets = None
         if args.unet:
             nets = load_nets(config, local_rank, args.unet_max_pixels)

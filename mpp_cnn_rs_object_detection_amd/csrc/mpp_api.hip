@@ -178,6 +178,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
+  if (!strcmp(name, "birth_map_grid")) return c->birth_grid;                    // the last birth map's pre-pass built grids
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)
   if (!strcmp(name, "grid_ny")) return c->hp.ny;

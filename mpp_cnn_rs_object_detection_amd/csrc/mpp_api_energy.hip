@@ -96,6 +96,49 @@ extern "C" int mpp_total_energy_all(mpp_ctx *c, double *energy) {
   return 0;
 }
 
+// The birth-energy map of every chain (mpp_birth_map.hip): grids as mpp_total_energy_all builds them, the pre-pass that
+// caches every point's record, the map, and -- when asked for -- the summary, whose copy back is the call's only wait.
+extern "C" int mpp_birth_energy_map(mpp_ctx *c, double *dE, double *marks, mpp_birth_summary *summary) {
+  if (!c) return -1;
+  if (!c->have_maps || !c->have_model) return fail(c, -1, "birth_energy_map: mpp_set_maps / mpp_set_model have not been called");
+  if (!dE) return fail(c, -1, "birth_energy_map: dE is NULL");
+  if (model_class(c->hp).classic)
+    return fail(c, -1, "birth_energy_map: the model has a classic image energy (a candidate per pixel would need a rasterised "
+                       "footprint per pixel)");
+  int rc = push_state(c);
+  if (rc) return rc;
+  const int T = c->n_tiles, ncell = c->hp.nx * c->hp.ny;
+  if (T > 65535) return fail(c, -1, "birth_energy_map: %d chains, at most 65535", T);
+  const bool grid = c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points;
+  const size_t TC = (size_t)T * c->cap;
+  // doubles: lin, r0, r1, e [T][cap]; the summary's parts and results; ints: gate [T][cap], then the grids
+  const size_t part_bytes = (size_t)T * MPP_BIRTH_PARTS * sizeof(BirthPart), sum_bytes = (size_t)T * sizeof(mpp_birth_summary);
+  const size_t n_int = TC + (grid ? (size_t)T * (2 * (size_t)ncell + 1) + TC : 0);
+  if (c->birth_ws.reserve(c->stream, 4 * TC * sizeof(double) + part_bytes + sum_bytes + n_int * sizeof(int32_t)) != hipSuccess)
+    return fail(c, -2, "no device memory for the point cache of %d chains", T);
+  double *d0 = (double *)c->birth_ws.p;
+  BirthPart *part = (BirthPart *)(d0 + 4 * TC);
+  mpp_birth_summary *d_sum = (mpp_birth_summary *)(part + (size_t)T * MPP_BIRTH_PARTS);
+  int32_t *gate = (int32_t *)(d_sum + T);
+  const BirthCache bc{d0, d0 + TC, d0 + 2 * TC, d0 + 3 * TC, gate};
+  int32_t *gs = grid ? gate + TC : nullptr, *gc = grid ? gs + (size_t)T * (ncell + 1) : nullptr;
+  int32_t *gi = grid ? gc + (size_t)T * ncell : nullptr;
+  c->birth_grid = grid ? 1 : 0;
+  if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, gs, gc, gi);
+  mpp_launch_birth_prepass(c->stream, c->dp, c->d_tiles, T, c->cap, bc, gs, gi, ncell + 1, c->grid_min_points);
+  mpp_launch_birth_map(c->stream, c->dp, c->d_tiles, T, c->cap, c->H, c->W, bc, dE, marks);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && summary) {
+    mpp_launch_birth_summary(c->stream, T, c->H, c->W, dE, part, d_sum);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_sum, sum_bytes, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e2);
+  }
+  HIPCHK(c, e);
+  return 0;
+}
+
 // shared body of mpp_delta_batch (dE != NULL) and mpp_delta_vectors (before/after/mask != NULL)
 static int delta_cases(mpp_ctx *c, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
                        const int32_t *add_off, const int32_t *add_xy, const double *add_marks, double *dE, int stride,

@@ -117,6 +117,8 @@ struct mpp_ctx : TileMem {
   DevWs g_cells, g_items;            // cell starts [ncell + 1] then cursors [ncell]; the points by cell [cap]
   int grid_min_points = 256;
   DevWs energy_ws;                   // mpp_total_energy_all: every chain's point energies, their sums, the chains' grids
+  DevWs birth_ws;                    // mpp_birth_energy_map: the per-point cache, the chains' grids, the summary's parts
+  int birth_grid = 0;                // ... its last pre-pass built candidate grids
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
   RescaleWs rescale;                 // workspace of mpp_rescale (mpp_rescale.hip)

@@ -45,6 +45,12 @@ static inline ModelClass model_class(const DevParams &P) {
   return m;
 }
 
+// What the pre-pass of the birth-energy map keeps per point of a chain, [n_chains][cap] each: the unit part of its energy,
+// its gate, its two pair reductions and its energy in the chain's configuration.
+struct BirthCache { double *lin, *r0, *r1, *e; int32_t *gate; };
+#define MPP_BIRTH_PARTS 256                        // partial summaries per chain (one per workgroup of the first pass)
+struct BirthPart { double v; long long idx, n_neg, n_nan; };   // smallest non-NaN value and its row-major index (-1: none)
+
 extern "C" {
 size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 size_t mpp_chain_static_lds_bytes(int waves);      // the staged parameter block: the same for every chain kernel
@@ -96,6 +102,15 @@ void mpp_launch_chain_energies(hipStream_t st, const DevParams *P, const TileRef
 void mpp_launch_delta_batch(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile, int n_cases,
                             const int32_t *rem_off, const int32_t *rem, const int32_t *add_off, const int32_t *add_xy,
                             const double *add_marks, double *dE, const int32_t *grid_start, const int32_t *grid_items);
+// the birth-energy map (mpp_birth_map.hip).  bc: the per-point cache, [n_chains][cap] each, filled by the pre-pass from the
+// chains' grids (those of mpp_launch_grid_build_all; nullptr: every chain scans); dE [n_chains][H][W], marks the same x 3 or
+// nullptr.  The summary: part [n_chains][MPP_BIRTH_PARTS] scratch, out [n_chains], all device.
+void mpp_launch_birth_prepass(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_chains, int cap, BirthCache bc,
+                              const int32_t *grid_start, const int32_t *grid_items, int sstride, int grid_min);
+void mpp_launch_birth_map(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_chains, int cap, int H, int W,
+                          BirthCache bc, double *dE, double *marks);
+void mpp_launch_birth_summary(hipStream_t st, int n_chains, int H, int W, const double *dE, BirthPart *part,
+                              mpp_birth_summary *out);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);

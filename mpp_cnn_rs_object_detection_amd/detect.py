@@ -5,7 +5,8 @@ ground sampling distance when it is finer (the float64 anti-aliased rescale of t
 handed to ``MPPModel.infer_image`` as an ``ImageWMaps`` that carries only ``image`` (the U-Nets compute the score maps on the
 device), and the detections are mapped back to the pixels of the file.  Per image ``<stem>_detections.csv`` (source pixels),
 ``<stem>_results.pkl`` (the keys of ``infer``'s pickle, in the pixels the model saw, plus ``scale`` and ``source_shape``) and,
-with ``figures``, ``<stem>_detection.png`` drawn on the picture the model saw.
+with ``figures``, ``<stem>_detection.png`` drawn on the picture the model saw.  With ``inference.birth_map`` of the model's
+config (``--birth-map``) also ``<stem>_birth_energy.png`` and the key ``birth_summary`` of the pickle (``MPPModel.birth_map``).
 """
 from __future__ import annotations
 
@@ -69,6 +70,7 @@ class DetectResult:
     image: np.ndarray                 # the picture the model saw, float32 [h,w,3] in 0..1
     scale: float
     source_shape: Tuple[int, int]
+    birth: Any = None                 # ``inference.birth_map``: (dE [h,w] float64 device tensor, summary dict) of ``MPPModel.birth_map``
 
     def polygons(self) -> np.ndarray:
         """[n,4,2] corners in the pixels the model saw (``rect_to_poly`` of (a, b, angle), as ``infer`` stores them)"""
@@ -109,9 +111,10 @@ def detect_image(model, rgb_uint8: np.ndarray, gsd: Optional[float] = None, mode
     data = ImageWMaps(name=name, shape=tuple(image.shape[:2]), image=image, detection_map=None, param_dist_maps=None,
                       mappings=default_mappings(),
                       param_names=Rectangle.PARAMETERS, labels=None, gt_config=[])
+    model.last_birth = None
     detections, scores = model.infer_image(data, seed=seed)
     return DetectResult(detections=detections, scores=np.asarray(scores, dtype=np.float64), image=image, scale=scale,
-                        source_shape=(H, W))
+                        source_shape=(H, W), birth=getattr(model, "last_birth", None))
 
 
 def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Optional[float] = None, figures: bool = False,
@@ -124,15 +127,21 @@ def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Opti
         f.write(",".join(CSV_COLUMNS) + "\n")
         for r in rows:
             f.write(",".join(repr(float(v)) for v in r) + "\n")
+    record = {"detection": result.polygons(), "detection_points": [p.as_row() for p in pts], "detection_type": "poly",
+              "detection_center": np.array([[p.x, p.y] for p in pts]).reshape(-1, 2),
+              "detection_score": list(map(float, result.scores)),
+              "detection_params": [sra_to_wla(p.size, p.ratio, p.angle) for p in pts],
+              "scale": result.scale, "source_shape": tuple(result.source_shape)}
+    if result.birth is not None:
+        record["birth_summary"] = result.birth[1]
     with open(os.path.join(out_dir, f"{stem}_results.pkl"), "wb") as f:
-        pickle.dump({"detection": result.polygons(), "detection_points": [p.as_row() for p in pts], "detection_type": "poly",
-                     "detection_center": np.array([[p.x, p.y] for p in pts]).reshape(-1, 2),
-                     "detection_score": list(map(float, result.scores)),
-                     "detection_params": [sra_to_wla(p.size, p.ratio, p.angle) for p in pts],
-                     "scale": result.scale, "source_shape": tuple(result.source_shape)}, f)
+        pickle.dump(record, f)
     if figures:
         from . import figures as F
         F.save_png(os.path.join(out_dir, f"{stem}_detection.png"), F.detection_picture(result.image, pts, result.scores, ctx))
+    if result.birth is not None:
+        from . import figures as F
+        F.save_png(os.path.join(out_dir, f"{stem}_birth_energy.png"), F.birth_energy_picture(result.birth[0], pts, ctx))
 
 
 def detect_files(model, paths: Sequence[str], out_dir: str, gsd: Optional[float] = None, model_gsd: float = 0.5,
@@ -144,6 +153,7 @@ def detect_files(model, paths: Sequence[str], out_dir: str, gsd: Optional[float]
     for path in files:
         stem = os.path.splitext(os.path.basename(path))[0]
         result = detect_image(model, read_rgb(path), gsd=gsd, model_gsd=model_gsd, name=stem)
-        write_results(result, out_dir, stem, min_score=min_score, figures=figures, ctx=model._figure_ctx() if figures else None)
+        write_results(result, out_dir, stem, min_score=min_score, figures=figures,
+                      ctx=model._figure_ctx() if figures or result.birth is not None else None)
         print(f"{path}: {len(result.scores)} detection(s)")
     return files

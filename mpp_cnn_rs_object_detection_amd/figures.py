@@ -83,6 +83,42 @@ def map_picture(det_map, ctx, cmap: str = "plasma", vmin: float = 0.0, vmax: flo
     return ctx.draw_outlines(m, lut=cmap_table(cmap), vmin=vmin, vmax=vmax).cpu().numpy()
 
 
+#: outline colour of the detections on the birth-energy picture (the diverging table runs blue - grey - red)
+BIRTH_OUTLINE_COLOR = (0.0, 0.0, 0.0)
+
+
+def birth_vmax(dE) -> float:
+    """colour range of a birth-energy map: the 0.9 quantile of |dE| over its finite values, as the reference's
+    ``show_papangelou`` scales its deltas (utils/figures/analyse_mpp.py:25-29); 1.0 when there are none (or when that
+    quantile is 0: a range needs a width)"""
+    a = np.asarray(dE.detach().cpu().numpy() if hasattr(dE, "data_ptr") else dE, dtype=np.float64).reshape(-1)
+    a = np.abs(a[np.isfinite(a)])
+    if a.size == 0:
+        return 1.0
+    q = float(np.quantile(a, 0.9))
+    return q if q > 0.0 else 1.0
+
+
+def birth_energy_picture(dE, detections, ctx, vmax: float = None) -> np.ndarray:
+    """``NNNN_birth_energy.png``: the birth-energy map dE [H,W] (``EPointsSet.birth_energy_map``; numpy, or a tensor on the
+    ctx's GPU) clipped to [-vmax, vmax] through the 256 colours of ``coolwarm`` -- blue where a birth would lower the energy,
+    red where the energy rejects it -- under the outlines of ``detections``.  ``vmax``: ``birth_vmax(dE)`` by default.  The
+    scalar path of ``draw_outlines`` does all of it on float32 values; a NaN pixel takes the table's first colour, as that
+    path clips it to the lower bound.  Returns uint8 [H,W,3]."""
+    if vmax is None:
+        vmax = birth_vmax(dE)
+    if not (vmax > 0.0 and np.isfinite(vmax)):
+        raise ValueError(f"birth_energy_picture: vmax must be positive and finite, got {vmax!r}")
+    m = _on_device(dE, ctx)
+    if m.dim() != 2:
+        raise ValueError(f"expected an [H,W] map, got {tuple(m.shape)}")
+    pts = list(detections)
+    params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
+    corners = rect_corners([(p.x, p.y) for p in pts], params)
+    colors = np.tile(np.asarray(BIRTH_OUTLINE_COLOR, dtype=np.float32), (len(corners), 1))
+    return ctx.draw_outlines(m, corners, colors, lut=cmap_table("coolwarm"), vmin=-float(vmax), vmax=float(vmax)).cpu().numpy()
+
+
 def save_png(path: str, rgb: np.ndarray) -> None:
     """uint8 [H,W,3] -> PNG, with whichever of matplotlib or PIL the process has imported already"""
     rgb = np.ascontiguousarray(rgb)

@@ -85,6 +85,9 @@ PROPOSAL_DTYPE = np.dtype([("kernel", "<i4"), ("target", "<i4"), ("ax", "<i4"), 
                            ("param_id", "<i4"), ("new_class", "<i4"), ("u_accept", "<f8")], align=True)
 STEPOUT_DTYPE = np.dtype([("dE", "<f8"), ("fwd", "<f8"), ("bwd", "<f8"), ("log_alpha", "<f8"), ("T", "<f8"),
                           ("accepted", "<i4"), ("n_after", "<i4")], align=True)
+#: mpp_birth_summary, one per chain, and MPP_BIRTH_CHUNK: the points a block of the birth-energy map stages per pass
+BIRTH_SUMMARY_DTYPE = np.dtype([("min_dE", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_negative", "<i8"), ("n_nan", "<i8")], align=True)
+BIRTH_CHUNK = 256
 
 
 _vp, _i32, _i64, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -111,6 +114,7 @@ PROTOTYPES = {
     "mpp_delta_batch": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpp_delta_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "mpp_papangelou": (_i32, [_vp, _i32, _vp]),
+    "mpp_birth_energy_map": (_i32, [_vp, _vp, _vp, _vp]),
     "mpp_conv3x3_c32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpp_conv3x3_stem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mpp_merge_score": (_i32, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -478,6 +482,36 @@ class MppContext:
         out = np.zeros(max(self.count(tile), 1), np.float64)
         self._check(self._L.mpp_papangelou(self._h, tile, _ptr(out)))
         return out[:self.count(tile)]
+
+    def birth_energy_map(self, out=None, marks=False, summary: bool = True):
+        """``mpp_birth_energy_map``: dE(c) = E(X + u_c) - E(X) for every pixel c of every chain, u_c the rectangle ShapeNet
+        proposes at c.  Returns ``(dE, marks, summary)``: dE a float64 CUDA tensor [n_chains,H,W] on the ctx's GPU (``out``:
+        written there), marks [n_chains,H,W,3] (size, ratio, angle of the candidates) when ``marks`` is True or a tensor to
+        write, else None; summary a structured array of ``BIRTH_SUMMARY_DTYPE`` per chain, or None -- then the call does not
+        wait for the device."""
+        import torch
+        T, (H, W) = self.get_option("n_chains"), self.shape
+        if not self.n_tiles:
+            self._check(self._L.mpp_birth_energy_map(self._h, None, None, None))       # (no maps: the library's message)
+        dev = torch.device("cuda", self.device)
+
+        def dev_out(name, t, shape):
+            if not (_is_torch(t) and t.is_cuda and t.device.index == self.device and t.dtype == torch.float64
+                    and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"birth_energy_map: {name} must be a contiguous float64 tensor of shape {shape} on GPU {self.device}")
+            return t
+        out = torch.empty((T, H, W), dtype=torch.float64, device=dev) if out is None else dev_out("out", out, (T, H, W))
+        if marks is True:
+            marks = torch.empty((T, H, W, 3), dtype=torch.float64, device=dev)
+        elif marks is False or marks is None:
+            marks = None
+        else:
+            marks = dev_out("marks", marks, (T, H, W, 3))
+        # (the ctx's stream reads and writes tensors torch made: what torch has queued on them is complete first)
+        torch.cuda.current_stream(dev).synchronize()
+        s = np.zeros(T, BIRTH_SUMMARY_DTYPE) if summary else None
+        self._check(self._L.mpp_birth_energy_map(self._h, _ptr(out), _ptr(marks), _ptr(s)))
+        return out, marks, s
 
     # -- the chain -----------------------------------------------------------------------------
     def merge_score(self, distance: float):

@@ -142,6 +142,26 @@ def check_restarts(config: Dict, world_size: int = 1) -> int:
     return int(r)
 
 
+def check_birth_map(config: Dict, world_size: int = 1) -> bool:
+    """``inference.birth_map`` of a config (default off): the birth-energy map of every image, computed on ONE context that
+    holds the image as its single tile with the merged detections.  Ranks that share one image hold a region of its maps
+    each, so they refuse the option -- before any collective, every rank alike; ranks that shard a dataset by image each
+    map their own images."""
+    on = (config.get("inference") or {}).get("birth_map", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"inference.birth_map must be true or false, got {on!r}")
+    if on and world_size > 1:
+        raise ValueError(f"inference.birth_map needs an image held by one GPU; {world_size} ranks share this one "
+                         f"(set inference.birth_map to false)")
+    return bool(on)
+
+
+def format_birth_summary(summary: Dict) -> str:
+    """the log line of one image's birth map"""
+    return (f"birth map: min dE {summary['min_dE']:.2f} at ({summary['argmin'][0]}, {summary['argmin'][1]}), "
+            f"{summary['n_negative']} pixel(s) below 0")
+
+
 class MPPModel:
     def __init__(self, config: Dict, phase: str = "val", overwrite: bool = False, load: bool = False,
                  dataset: str = None, device: int = 0, nets=None, spec_waves: Optional[int] = None):
@@ -313,8 +333,39 @@ class MPPModel:
         score maps of its own region, the sampled configurations are packed on the device and all-gathered once,
         every rank scores the gathered points of ITS tiles on its own maps (their neighbours lie inside the region by
         construction), one all-reduce shares the scores, every rank takes the same ``distance_merge`` decision, and a
-        second scoring + all-reduce gives the final Papangelou scores of the survivors."""
+        second scoring + all-reduce gives the final Papangelou scores of the survivors.
+
+        ``inference.birth_map``: the birth-energy map of the image under the returned detections is left in
+        ``self.last_birth`` = (dE [H,W] float64 device tensor, summary dict), see ``birth_map``."""
         check_restarts(self.config, world_size)               # (before any collective: every rank raises alike)
+        if not check_birth_map(self.config, world_size):
+            return self._infer_image(image_data, rank, world_size, region_data, seed)
+        if region_data is None:
+            region_data = self.region_maps(image_data, rank, world_size)
+        merged, scores = self._infer_image(image_data, rank, world_size, region_data, seed)
+        self.last_birth = self.birth_map(region_data, merged)
+        return merged, scores
+
+    def birth_map(self, region_data: ImageWMaps, merged):
+        """The birth-energy map of one image (``EPointsSet.birth_energy_map``): one context with the image as its single
+        tile and ``merged`` as its configuration, as ``merge_patches`` builds its ``EPointsSet``.  Returns (dE, summary):
+        dE [H,W] float64 on the device, summary = {"min_dE", "argmin": (x, y), "n_negative", "n_nan"}; logs one line."""
+        pts = list(merged)
+        unit, pair = self.energy_setup.make_energies(region_data)
+        agg = EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
+                         device=self.device, point_capacity=max(1024, len(pts) + 64))
+        dE, s = agg.birth_energy_map(energy_combinator=self.energy_model)
+        summary = {"min_dE": float(s["min_dE"]), "argmin": (int(s["x"]), int(s["y"])), "n_negative": int(s["n_negative"]),
+                   "n_nan": int(s["n_nan"])}
+        logging.info(format_birth_summary(summary))
+        return dE, summary
+
+    def _write_birth_figure(self, path: str, dE, merged):
+        from . import figures as F
+        F.save_png(path, F.birth_energy_picture(dE, merged, self._figure_ctx()))
+
+    def _infer_image(self, image_data: ImageWMaps, rank: int, world_size: int, region_data: ImageWMaps, seed: int):
+        """the body of ``infer_image``"""
         shape = tuple(int(v) for v in image_data.shape[:2])
         patch, anchors = self.tile_layout(shape)
         n_tiles = len(anchors)
@@ -608,9 +659,10 @@ class MPPModel:
     #: one GPU runs chains at a time; every other image of a dataset belongs to one rank (``infer``)
     TILE_SHARD_MIN = 2048
 
-    def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores) -> dict:
+    def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None) -> dict:
         """Write ``NNNN_results.pkl`` of one image (mpp_model.py:333-366) and return what the two DOTA translators need
-        of it (plain arrays: the records of all ranks travel to rank 0 in one gather)."""
+        of it (plain arrays: the records of all ranks travel to rank 0 in one gather).  ``birth_summary``
+        (``inference.birth_map``): one more key of the pickle."""
         pts = list(merged)
         pred_params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
         pred_centers = np.array([[p.x, p.y] for p in pts]).reshape(-1, 2)
@@ -624,10 +676,13 @@ class MPPModel:
         score01 = np.asarray(scores) / max_score
         if len(score01) > 0 and np.max(score01) > 1.0:
             logging.warning(f"pred score higher than max, effective score is {np.max(scores)} while param says {max_score}")
+        record = {"detection": det_poly, "detection_points": [p.as_row() for p in pts],
+                  "detection_type": "poly", "detection_center": pred_centers,
+                  "detection_score": list(map(float, scores)), "detection_params": pred_params}
+        if birth_summary is not None:
+            record["birth_summary"] = birth_summary
         with open(out_file, "wb") as f:
-            pickle.dump({"detection": det_poly, "detection_points": [p.as_row() for p in pts],
-                         "detection_type": "poly", "detection_center": pred_centers,
-                         "detection_score": list(map(float, scores)), "detection_params": pred_params}, f)
+            pickle.dump(record, f)
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
                 "det_poly": det_poly}
 
@@ -659,7 +714,8 @@ class MPPModel:
         """Reference ``mpp_model.py:202-370``.  ``figures`` (default: ``inference.figures`` of the config, off): the two
         pictures the reference writes per image, ``NNNN_detection.png`` and ``NNNN_gt.png``, beside ``NNNN_results.pkl``, by the
         rank that writes the pickle (``_write_figures``; without the score text).  Off, nothing of
-        it runs.
+        it runs.  ``inference.birth_map`` (off): per image the birth-energy map under its merged detections (``birth_map``):
+        ``NNNN_birth_energy.png``, the key ``birth_summary`` of the pickle and one log line.
 
         Several ranks (one per GPU): the DATASET is sharded by image -- the reference's own loop is serial over images
         (``mpp_model.py:220``) with a process pool inside each; here rank r takes the r-th block of the images and runs them
@@ -670,6 +726,8 @@ class MPPModel:
         rank, world = mdist.init_process_group()
         if figures is None:
             figures = bool(self.config["inference"].get("figures", False))
+        # (an image shared by all ranks refuses the option in ``infer_image``, before its first collective)
+        birth_map = check_birth_map(self.config)
         dataset = self.config["dataset"]["dataset"]
         results_dir = get_inference_path(os.path.split(self.save_path)[1], dataset, subset)
         os.makedirs(results_dir, exist_ok=True)
@@ -729,7 +787,12 @@ class MPPModel:
 
         try:
             for k, image_data, region_data, merged, scores in inferred():
-                records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores))
+                birth = None
+                if birth_map:                       # (the image's own maps and its merged detections: one context, one tile)
+                    dE, birth = self.birth_map(region_data, merged)
+                    self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
+                    del dE
+                records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth))
                 if figures:
                     self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all

@@ -213,6 +213,15 @@ class EPointsSet:
         d = self._ctx.papangelou(0)
         return d if return_energy_delta else np.exp(-d)
 
+    def birth_energy_map(self, energy_combinator=None, return_marks: bool = False):
+        """dE(c) = E(X + u_c) - E(X) for every pixel c of the support, u_c the rectangle ShapeNet proposes there (the argmax
+        class of each mark map at its lower bin edge): the Papangelou surface exp(-dE) where there is no detection
+        (``mpp_birth_energy_map``).  Returns ``(dE, summary)`` or ``(dE, marks, summary)``: dE [H,W] float64 and marks
+        [H,W,3] tensors on the set's GPU, summary the record of ``hip_api.BIRTH_SUMMARY_DTYPE`` of this one tile."""
+        self._use(energy_combinator)
+        dE, marks, s = self._ctx.birth_energy_map(marks=return_marks)
+        return (dE[0], marks[0], s[0]) if return_marks else (dE[0], s[0])
+
     # -- mutation ------------------------------------------------------------------------------------
     def apply_perturbation(self, p: Perturbation, inplace: bool = False) -> "EPointsSet":
         """Reference ``energy_point_set.py:118-154``."""
