@@ -447,10 +447,12 @@ __device__ double rescan_lane(const Chain &c, int p, int u, const Geo2 &gu, int 
 // Everything but c.lane and ag is wave-uniform.  us, bu: the neighbour's slot and rectangle; skip: the removed slot;
 // need0 / need1: which pair to re-reduce.  The added rectangle (has_add) is lane glane's ag, broadcast only inside the
 // branch that uses it (broadcast at the call it slows the deep round down: profiles/shared_rereduce.md); as_, ar_, aa_:
-// its marks.  *out0 / *out1: the new reductions (0.0 for a pair that was not asked for).
+// its marks: wave-uniform with mlane < 0; with mlane >= 0 they are lane mlane's and are read at the one place that uses
+// them, slot_first behind pair_needs_clip (the deep round: three broadcasts fewer per call, profiles/deep_share.md).
+// *out0 / *out1: the new reductions (0.0 for a pair that was not asked for).
 __device__ __forceinline__ void rereduce_wave(const Chain &c, int us, const Geo2 &bu, int skip, bool need0, bool need1,
                                               int maxd2_0, int maxd2_1, double rew, bool has_add, const Geo2 &ag, double as_,
-                                              double ar_, double aa_, int glane, double *out0, double *out1) {
+                                              double ar_, double aa_, int glane, double *out0, double *out1, int mlane = -1) {
   const Lds &L = c.L;
   const int ck = c.lane / 3, ce = c.lane - 3 * ck;
   int uci, ucj;
@@ -540,6 +542,7 @@ __device__ __forceinline__ void rereduce_wave(const Chain &c, int us, const Geo2
     if (need0 && d2a2 <= maxd2_0) {
       double mn;
       if (pair_needs_clip(Au, geo_area(ba.g), bu.rad + ba.rad, (double)d2a2, &mn)) {
+        if (mlane >= 0) { as_ = readlane_d(as_, mlane); ar_ = readlane_d(ar_, mlane); aa_ = readlane_d(aa_, mlane); }
         const bool u_first = slot_first(L, us, bu.g, ba.g.x, ba.g.y, as_, ar_, aa_);
         double sx[4], sy[4], cx[4], cy[4];
         ordered_corners(u_first, bu.g, ba.g, sx, sy, cx, cy);

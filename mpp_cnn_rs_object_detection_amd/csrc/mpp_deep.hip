@@ -376,8 +376,7 @@ __device__ __forceinline__ void deep_delta(const Chain &c, const DeepLds &D, boo
           const bool ha_s = __builtin_amdgcn_readlane((int)s_ha, src) != 0;
           const Geo2 bu = readlane_geo2(gu, src);              // the neighbour, wave-uniform
           double acc0, acc1;
-          rereduce_wave(c, us, bu, rem_s, need0, need1, maxd2_0, maxd2_1, rew, ha_s, ag, readlane_d(a_s, is), readlane_d(a_r, is),
-                        readlane_d(a_a, is), src, &acc0, &acc1);
+          rereduce_wave(c, us, bu, rem_s, need0, need1, maxd2_0, maxd2_1, rew, ha_s, ag, a_s, a_r, a_a, src, &acc0, &acc1, is);
           if (c.lane == src) {
             if (need0) nv0 = acc0;
             if (need1) nv1 = acc1;
