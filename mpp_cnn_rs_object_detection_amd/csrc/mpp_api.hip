@@ -20,6 +20,7 @@ extern "C" int mpp_create(int device_id, mpp_ctx **out) {
   c->device = device_id;
   memset(&c->hp, 0, sizeof(DevParams));
   c->hp.n_kernels = MPP_K_SPLIT;
+  c->hp.hot_past = 1;
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&c->own_stream) != hipSuccess ||
       hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
       c->dp.alloc(1) != hipSuccess) {
@@ -138,6 +139,10 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
   } else if (!strcmp(name, "hot_table")) {
     if (v < 0 || v > 1) return fail(c, -1, "hot_table must be 0 or 1");
     c->hot_table = (int)v;
+  } else if (!strcmp(name, "hot_past_births")) {
+    // the table form of the hot start keeps committing a round's steps past an accepted birth / death (0: the round ends there)
+    if (v < 0 || v > 1) return fail(c, -1, "hot_past_births must be 0 or 1");
+    c->hp.hot_past = (int)v; c->params_dirty = true;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -174,6 +179,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "prepass_queues_used")) return c->prepass_queues_used;
   if (!strcmp(name, "hot_table")) return c->hot_table;
   if (!strcmp(name, "hot_table_used")) return c->hot_table_used;
+  if (!strcmp(name, "hot_past_births")) return c->hp.hot_past;
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now

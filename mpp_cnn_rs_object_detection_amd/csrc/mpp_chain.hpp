@@ -141,6 +141,9 @@ __device__ __forceinline__ double finish_energy_c(const Chain &c, double lin) {
 #ifndef MPP_HOT_TABLE
 #define MPP_HOT_TABLE 0       // 1 in mpp_hot.hip: mpp_chain_body.inc takes every step's draw from the pre-pass table
 #endif
+#ifndef MPP_HOT_PAST
+#define MPP_HOT_PAST 0        // 1 in mpp_hot.hip (it needs MPP_HOT_TABLE): the commit wave goes on past an accepted birth / death
+#endif
 __device__ __forceinline__ void wave_lds_fence() {
 #if MPP_STATE_HBM
   // The state arrays are in device memory.  The argument below does not carry over: the LLVM AMDGPU memory model
@@ -1547,6 +1550,32 @@ __device__ __forceinline__ void accept_step(const DevParams *P, Rec &r, int n, d
   r.accepted = (P->force_accept || (r.u_acc + EPS_GREEN) < exp(-r.dE / T) * ratio) ? 1 : 0;
   if (tracing) { r.fwd = fwd; r.bwd = bwd; r.log_alpha = (-r.dE / T) + log(bwd + EPS_GREEN) - log(fwd + EPS_GREEN); }
 }
+#if MPP_HOT_PAST
+// accept_step() in two parts, for the kernel whose commit wave takes a record's test again after the population has changed
+// (mpp_chain_body.inc, MPP_HOT_PAST): of the test only the Green ratio depends on n, so the evaluation keeps the Boltzmann factor
+// exp(-dE / T) in the record -- in log_alpha, which an untraced kernel does not use -- and both the evaluation and the commit
+// wave finish with accept_again().  The operations on the values are accept_step()'s, in its order: the same bits.  (Taking the
+// whole of accept_step() again in the commit wave cost more than half of what the longer rounds gain, profiles/hot_past_births.md.)
+// green_terms() is restated with its four cases as selected operands of ONE division each for fwd and bwd: in the commit wave
+// every lane holds another record, and the cases one after the other would be seven divisions in a row on the round's
+// critical path.  Each case divides the values green_terms() divides (x / 1.0 is x): the same bits.
+__device__ __forceinline__ void accept_again(const DevParams *P, Rec &r, int n, double intensity) {
+  const double *pk = P->kern.p_kernel;
+  const int k = r.kernel;
+  const bool birth = k == MPP_K_UBIRTH || k == MPP_K_DBIRTH, death = k == MPP_K_UDEATH || k == MPP_K_DDEATH;
+  const bool noop = !birth && !r.has_rem;
+  const double pf = pk[k], pb = pk[birth ? k + 1 : (death && !noop ? k - 1 : k)], dn = (double)n;
+  const double fn = (death || noop) ? pf : pf * r.qf, fd = birth ? intensity : (noop ? 1.0 : dn);
+  const double bn = (birth || noop) ? pb : pb * r.qb, bd = birth ? (double)(n + 1) : (noop ? 1.0 : (death ? intensity : dn));
+  const double fwd = fn / fd, bwd = bn / bd;
+  double ratio = (bwd + EPS_GREEN) / (fwd + EPS_GREEN);
+  r.accepted = (P->force_accept || (r.u_acc + EPS_GREEN) < r.log_alpha * ratio) ? 1 : 0;
+}
+__device__ __forceinline__ void accept_step_keep(const DevParams *P, Rec &r, int n, double intensity, double T) {
+  r.log_alpha = exp(-r.dE / T);
+  accept_again(P, r, n, intensity);
+}
+#endif
 
 // ---- state mutation (energy_point_set.py:118-154), wave 0 only ----------------------------------
 __device__ void cell_remove(const Chain &c, int cell, int slot) {
@@ -1641,7 +1670,11 @@ __device__ void evaluate(const Chain &c, Rec &r, int ri, int keep, int n, double
                               &r.n_stash, apply);
     EPROF(7);
   }
+#if MPP_HOT_PAST
+  accept_step_keep(P, r, n, c.t.intensity, T);     // (untraced)
+#else
   accept_step(P, r, n, c.t.intensity, T, tracing);
+#endif
   EPROF(8);
 }
 
@@ -1654,5 +1687,9 @@ __device__ void evaluate_tab_birth(const Chain &c, Rec &r, int ri, int n, double
   Geo2 ag;
   ag.g.x = add.x; ag.g.y = add.y; ag.g.hl = r.hl; ag.g.hw = r.hw; ag.g.ca = r.ca; ag.g.sa = r.sa; ag.rad = r.rad;
   r.dE = eval_delta<FAST>(c, ri, -1, true, add, ag, r.lin_a, r.gate_a, &r.ra0, &r.ra1, &r.n_stash, apply);
+#if MPP_HOT_PAST
+  accept_step_keep(P, r, n, c.t.intensity, T);
+#else
   accept_step(P, r, n, c.t.intensity, T, false);
+#endif
 }

@@ -188,6 +188,9 @@
         } else {
           const QEnt e = pt.qent[pre_ent + (size_t)(wd >> 4)];
           draw_tail_q<false>(c, k, e, n, r, &keep, &pmv);
+#if MPP_HOT_PAST
+          r._pad2 = (int)e.w2;       // the target word travels in the record: the commit wave draws the target again when n changes
+#endif
         }
 #else
         uint32_t w[8];
@@ -275,7 +278,8 @@
     //      only), then every chosen record is applied by the wave that evaluated it, all at once.  Two records of one
     //      round that both commit neither share a slot, nor a cell, nor lie within 2*max_inter of each other, so they
     //      touch disjoint cell lists, slots and cached reductions; a birth / death (which also changes n and order[])
-    //      is always the last record of its round.
+    //      is always the last record of its round -- except with MPP_HOT_PAST (mpp_hot_kernel), where the commit wave makes
+    //      the changes of n and order[] itself and the round goes on under the same three conditions.
     const bool par_commit = !LANE && SPEC > 1 && !tracing;
     if (par_commit) {
       if (c.wave == 0) {
@@ -292,7 +296,16 @@
         const int m_rx = me.rx, m_ry = me.ry, m_ax = me.ax, m_ay = me.ay;
         int ci, cj;
         const int m_cr = m_hr ? cell_index(c, m_rx, m_ry, &ci, &cj) : -1, m_ca = m_ha ? cell_index(c, m_ax, m_ay, &ci, &cj) : -2;
+#if MPP_HOT_PAST
+        // (see the birth / death branch below) the accepted mask is formed again after every change of n; lane w's target
+        // index follows order[]; first_bd: steps of the round up to and including its first committed birth / death
+        unsigned long long acc_mask = __ballot(in && me.accepted && (m_hr || m_ha));
+        const uint32_t m_w2 = (uint32_t)me._pad2;
+        int m_tidx = me.tidx, first_bd = -1;
+        const bool past = P->hot_past != 0;
+#else
         const unsigned long long acc_mask = __ballot(in && me.accepted && (m_hr || m_ha));
+#endif
         unsigned int commit_mask = 0;
         int cur = 0;
         while (true) {
@@ -323,6 +336,62 @@
           // the round's start: an earlier commit of this round that touched the same cell has invalidated record w.)
           const int q_ca_w = __builtin_amdgcn_readlane(m_ca, w), q_cr_w = __builtin_amdgcn_readlane(m_cr, w);
           if (q_ha && q_ca_w != q_cr_w && (int)L.cell_cnt[q_ca_w] >= c.h.cell_cap) { err = ERR_CELL_OVERFLOW; committed = w; break; }
+#if MPP_HOT_PAST
+          if (!(q_hr && q_ha)) {
+            // death / birth.  The commit wave edits order[] itself, in commit order -- the waves that apply the records keep the
+            // cell lists, the slot and the stash -- and goes on: a later record is still the sequential chain's step when its
+            // target word draws the slot it was evaluated against from the new order[] and the new n (a birth has no target; a
+            // step drawn at n == 0 has lost the one it would have now), none of its points shares a cell with the born / killed
+            // rectangle or lies within conflict_d2 of it (the test of a committed move), and its accept test is taken again with
+            // the new n: of all a record holds, only green_terms() divides by n.
+            if (!q_hr && cur_n >= cap) { err = ERR_POINT_OVERFLOW; committed = w; break; }
+            commit_mask |= 1u << w;
+            if (q_hr) {                                                          // death: the last index takes the hole
+              const int q_ts = __builtin_amdgcn_readlane(m_ts, w), q_ti = __builtin_amdgcn_readlane(m_tidx, w);
+              if (c.lane == 0) {
+                const unsigned short last = L.order[cur_n - 1];
+                L.order[cur_n - 1] = (unsigned short)q_ts;
+                L.order[q_ti] = last;
+              }
+              cur_n -= 1;
+            } else {                                                             // birth: the next free slot, handed over in the record
+              if (c.lane == 0) L.rec[w].tslot = L.order[cur_n];
+              cur_n += 1;
+            }
+            wave_lds_fence();
+            if (first_bd < 0) first_bd = w + 1;
+            if (!past) { committed = w + 1; break; }                             // (hot_past_births 0: the round ends here)
+            if (!(__ballot(ok) & ~low(w + 1))) { cur = w + 1; continue; }        // (no record left to go on with)
+            const int q_c = q_hr ? q_cr_w : q_ca_w;
+            const int q_x = q_hr ? __builtin_amdgcn_readlane(m_rx, w) : __builtin_amdgcn_readlane(m_ax, w);
+            const int q_y = q_hr ? __builtin_amdgcn_readlane(m_ry, w) : __builtin_amdgcn_readlane(m_ay, w);
+            bool acc2 = false;
+            if (c.lane > w && ok) {
+              bool bad = !(m_hr || m_ha);
+              if (m_hr) {
+                const int ti = (int)mulhi32(m_w2, (uint32_t)cur_n);
+                if (cur_n == 0 || (int)L.order[ti] != m_ts) bad = true;
+                else m_tidx = ti;
+                const int dx = m_rx - q_x, dy = m_ry - q_y;
+                if (m_cr == q_c || dx * dx + dy * dy <= P->conflict_d2) bad = true;
+              }
+              if (m_ha) {
+                const int dx = m_ax - q_x, dy = m_ay - q_y;
+                if (m_ca == q_c || dx * dx + dy * dy <= P->conflict_d2) bad = true;
+              }
+              if (bad) ok = false;
+              else {                                                             // the accept test with the new n (accept_again)
+                Rec t;
+                t.kernel = m_kern; t.has_rem = m_hr; t.qf = me.qf; t.qb = me.qb; t.u_acc = me.u_acc; t.log_alpha = me.log_alpha;
+                accept_again(P, t, cur_n, c.t.intensity);
+                acc2 = t.accepted != 0;
+              }
+            }
+            acc_mask = (acc_mask & low(w + 1)) | __ballot(acc2);
+            cur = w + 1;
+            continue;
+          }
+#else
           if (!(q_hr && q_ha)) {                                                 // death / birth: ends the round
             if (q_hr) { commit_mask |= 1u << w; cur_n -= 1; }
             else if (cur_n >= cap) { err = ERR_POINT_OVERFLOW; committed = w; break; }
@@ -330,6 +399,7 @@
             committed = w + 1;
             break;
           }
+#endif
           commit_mask |= 1u << w;
           // lane w2 > w: is record w2 still trustworthy after this move / transform?
           const int q_ts = __builtin_amdgcn_readlane(m_ts, w), q_cr = __builtin_amdgcn_readlane(m_cr, w), q_ca = __builtin_amdgcn_readlane(m_ca, w);
@@ -354,7 +424,12 @@
         // changes the state with probability below ~0.12 -- the chain is handed to the deep-round kernel: this launch ends after the round's
         // commits, like a capacity stop, and the host continues with the very next step.
         if (P->handover && !apply_round) {
+#if MPP_HOT_PAST
+          // (handover_at was tuned on rounds that end with their first birth / death: the statistic keeps counting to there)
+          ho_ema += (((first_bd >= 0 ? first_bd : committed) << 8) - ho_ema) / 16;
+#else
           ho_ema += ((committed << 8) - ho_ema) / 16;
+#endif
           ++ho_rounds;
           if (err == 0 && ho_rounds >= 48 && ho_ema >= P->handover && done + committed < n_steps) err = ERR_HANDOVER;
         }
@@ -380,13 +455,19 @@
           write_slot(c, q.tslot, q);
         } else if (q.has_rem) {                            // death: last index takes the hole
           cell_remove(c, cell_index(c, q.rx, q.ry, &ci, &cj), q.tslot);
+#if !MPP_HOT_PAST                                          // (else the commit wave has edited order[], see above)
           if (c.lane == 0) {
             unsigned short last = L.order[n - 1];
             L.order[n - 1] = (unsigned short)q.tslot;
             L.order[q.tidx] = last;
           }
+#endif
         } else {                                           // birth: next free slot
+#if MPP_HOT_PAST
+          int slot = L.rec[c.wave].tslot;                  // (the one the commit wave took for it: n is the round's first)
+#else
           int slot = L.order[n];
+#endif
           cell_insert(c, cell_index(c, q.ax, q.ay, &ci, &cj), slot, &e2);
           write_slot(c, slot, q);
         }

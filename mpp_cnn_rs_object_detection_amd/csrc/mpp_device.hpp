@@ -40,6 +40,8 @@ struct DevParams {
   int32_t handover;     // (one wave per step, 8 waves) > 0: stop with ERR_HANDOVER once the smoothed number of steps committed
                         // per round reaches handover / 256 (~6 of 8): the host then continues the chain in deep rounds (set per
                         // launch by the host)
+  int32_t hot_past;     // (mpp_hot_kernel) a round's commits go on past an accepted birth / death (option hot_past_births; the
+                        // 18th int32 after the doubles: it takes what was padding, every other field stays where it was)
   double inv_step[3];   // 32 / (vmax - vmin)
 };
 

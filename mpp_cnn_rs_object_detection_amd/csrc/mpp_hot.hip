@@ -6,6 +6,9 @@
 // record and goes straight to the neighbour pass (evaluate_tab_birth), every other step loads its queue entry and finishes
 // the proposal against the configuration (draw_tail_q<false>).  Same values, same operations after them: the same chain.
 #define MPP_HOT_TABLE 1
+// ... and a round's commits go on past an accepted birth or death (DevParams::hot_past; mpp_chain_body.inc, phase B): the
+// later records are checked against the new population and order[], and take their accept test again
+#define MPP_HOT_PAST 1
 #include "mpp_chain.hpp"
 #include "mpp_split_merge.hpp"
 #include "mpp_launch.hpp"
