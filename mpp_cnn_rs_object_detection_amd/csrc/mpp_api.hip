@@ -2,6 +2,7 @@
 // given (model, kernels, maps, image), the per-tile pointer table and point I/O.  Chains: mpp_api_chain.hip; from-scratch
 // energies: mpp_api_energy.hip; U-Nets and training: mpp_api_nets.hip; the context they share: mpp_ctx.hpp.
 #include "mpp_ctx.hpp"
+#include "mpp_window.hpp"
 
 // 2: ten kernels (split, merge), mpp_kernels.split_*; 3: mpp_nhwc_glue, mpp_*_epilogue_nhwc; 4: mpp_pack_detections; 5: mpp_set_chain_keys, options auto_grow / remap_table
 extern "C" int mpp_abi_version(void) { return 10; }
@@ -143,6 +144,10 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     // the table form of the hot start keeps committing a round's steps past an accepted birth / death (0: the round ends there)
     if (v < 0 || v > 1) return fail(c, -1, "hot_past_births must be 0 or 1");
     c->hp.hot_past = (int)v; c->params_dirty = true;
+  } else if (!strcmp(name, "window_rows")) {
+    // the data-driven translation reads its window's row sums from the transposed table (0: it forms them from rowpart)
+    if (v < 0 || v > 1) return fail(c, -1, "window_rows must be 0 or 1");
+    c->window_rows = (int)v; c->tiles_dirty = true;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -180,6 +185,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "hot_table")) return c->hot_table;
   if (!strcmp(name, "hot_table_used")) return c->hot_table_used;
   if (!strcmp(name, "hot_past_births")) return c->hp.hot_past;
+  if (!strcmp(name, "window_rows")) return c->window_rows;
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now
@@ -286,7 +292,7 @@ extern "C" int mpp_set_kernels(mpp_ctx *c, const mpp_kernels *k, const double *i
   c->hp.n_kernels = (k->p_kernel[MPP_K_SPLIT] > 0.0 || k->p_kernel[MPP_K_MERGE] > 0.0) ? MPP_NKERNEL : MPP_K_SPLIT;
   if (c->hp.n_kernels == MPP_NKERNEL && !(k->split_radius > 0.0 && k->split_sigma > 0.0))
     return fail(c, -1, "split/merge kernels need split_radius > 0 and split_sigma > 0");
-  if (!c->have_kernels || c->hp.kern.max_delta != k->max_delta) c->box_dirty = true;
+  if (!c->have_kernels || c->hp.kern.max_delta != k->max_delta) c->box_dirty = c->win_dirty = true;
   c->hp.kern = *k;
   c->have_kernels = true;
   c->params_dirty = true;
@@ -324,7 +330,7 @@ extern "C" int mpp_set_maps(mpp_ctx *c, int n_tiles, int H, int W, const float *
   // (the cumulative tables of the birth kernels -- 16 B per pixel -- are made by the first chain launch: a context that only
   //  scores or merges, e.g. one whole 4096 x 4096 image, never needs them)
   c->cdf_ready = false;
-  c->box_dirty = true;
+  c->box_dirty = c->win_dirty = true;
   HIPCHK(c, c->px.alloc(T * c->cap)); HIPCHK(c, c->py.alloc(T * c->cap));
   HIPCHK(c, c->ps.alloc(T * c->cap)); HIPCHK(c, c->pr.alloc(T * c->cap)); HIPCHK(c, c->pa.alloc(T * c->cap));
   HIPCHK(c, c->n.alloc(T)); HIPCHK(c, c->errd.alloc(T)); HIPCHK(c, c->T.alloc(T * 3));
@@ -381,6 +387,11 @@ int push_state(mpp_ctx *c) {
     }
   }
   HIPCHK(c, hipSetDevice(c->device));
+  const bool win = c->window_rows && c->have_kernels && c->cdf_ready;
+  if (win && !c->rowwin.p) {
+    HIPCHK(c, c->rowwin.alloc(rowwin_count((size_t)c->n_maps, c->H, c->W)));
+    c->win_dirty = true; c->tiles_dirty = true;
+  }
   if (c->tiles_dirty) {
     const size_t hw = (size_t)c->H * c->W;
     c->h_tiles.resize(c->n_tiles);
@@ -392,6 +403,7 @@ int push_state(mpp_ctx *c) {
       r.rowpart = c->cdf_ready ? (const MPP_GLOBAL double *)(c->rowpart + m * hw) : nullptr;
       r.rowbase = c->cdf_ready ? (const MPP_GLOBAL double *)(c->rowbase + m * (c->H + 1)) : nullptr;
       r.boxsum = c->cdf_ready ? (const MPP_GLOBAL double *)(c->boxsum + m * hw) : nullptr;
+      r.rowwin = win ? (const MPP_GLOBAL double *)(c->rowwin + m * hw) : nullptr;
       for (int k = 0; k < 3; ++k)
         r.rm[k] = c->remap[k] ? (const MPP_GLOBAL double *)(c->remap[k] + m * hw * MPP_NCLASS) : nullptr;
       r.img = c->img ? (const MPP_GLOBAL float *)(c->img + m * hw * (size_t)c->img_c) : nullptr;
@@ -412,6 +424,11 @@ int push_state(mpp_ctx *c) {
     mpp_launch_boxsum(c->stream, c->n_maps, c->rowpart, c->H, c->W, c->hp.kern.max_delta, c->boxsum);
     HIPCHK(c, hipGetLastError());
     c->box_dirty = false;
+  }
+  if (c->win_dirty && win) {
+    mpp_launch_rowwin(c->stream, c->n_maps, c->rowpart, c->H, c->W, c->hp.kern.max_delta, c->rowwin);
+    HIPCHK(c, hipGetLastError());
+    c->win_dirty = false;
   }
   if (c->params_dirty) {
     c->hp.cap = c->cap; c->hp.cell_cap = c->cell_cap; c->hp.n_tiles = c->n_tiles;

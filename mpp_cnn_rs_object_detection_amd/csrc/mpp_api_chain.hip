@@ -72,7 +72,7 @@ static int ensure_birth_tables(mpp_ctx *c) {
   HIPCHK(c, c->rowtot.alloc(M * c->H)); HIPCHK(c, c->boxsum.alloc(M * hw));
   mpp_launch_cdf(c->stream, (int)M, c->det, c->H, c->W, c->rowpart, c->rowbase, c->rowtot);
   HIPCHK(c, hipGetLastError());
-  c->cdf_ready = true; c->box_dirty = true; c->tiles_dirty = true;
+  c->cdf_ready = true; c->box_dirty = c->win_dirty = true; c->tiles_dirty = true;
   return 0;
 }
 

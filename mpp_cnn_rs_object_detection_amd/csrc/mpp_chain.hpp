@@ -28,6 +28,7 @@
 #include "mpp_device.hpp"
 #include "mpp_layout.hpp"
 #include "mpp_prepass.hpp"
+#include "mpp_window.hpp"
 
 #define MPP_LDS_PARAMS_MIN_WAVES 4   // chains with at least this many waves read the parameter block from an LDS copy
 #define ERR_CELL_OVERFLOW 1
@@ -95,9 +96,11 @@ struct Chain {
   TileRef t;
   Lds L;
   int lane, wave;
-  int np, comb;
   PairRegs pr0, pr1;
   HotP h;
+  // (two shorts behind HotP's seven ints: the struct stays 536 bytes with TileRef::rowwin in it -- the split / merge
+  //  instantiations keep the whole Chain in private memory, and their frame is not to grow)
+  short np, comb;
 };
 __device__ __forceinline__ void load_hot(Chain &c) {
   const DevParams *Q = c.P;
@@ -112,7 +115,7 @@ __device__ __forceinline__ PairRegs load_pair_regs(const DevParams *P, int p) {
   return r;
 }
 __device__ __forceinline__ void load_model_regs(Chain &c) {
-  c.np = launder_s(c.P->model.n_pair); c.comb = launder_s(c.P->model.combinator);
+  c.np = (short)launder_s(c.P->model.n_pair); c.comb = (short)launder_s(c.P->model.combinator);
   c.pr0 = load_pair_regs(c.P, 0); c.pr1 = load_pair_regs(c.P, 1);
 }
 __device__ __forceinline__ PairRegs pair_regs(const Chain &c, int p) {
@@ -888,15 +891,15 @@ __device__ double birth_density(const Chain &c, const Rect &q, bool coop) {
 // around (x,y) with probability det/sum.  Lane i owns window row i (<= 31 rows): its segment sum comes
 // from the per-row prefix table, the row is found by an ordered readlane walk, the column by a ballot.
 __device__ void window_draw(const Chain &c, int x, int y, double u, int *ex, int *ey) {
-  const DevParams *P = c.P;
-  const int md = P->kern.max_delta;
-  const int x0 = max(0, x - md), x1 = min(x + md + 1, c.h.H), y0 = max(0, y - md), y1 = min(y + md + 1, c.h.W);
-  const int nrow = x1 - x0, wc = y1 - y0;
+  const WinBox b = window_box(x, y, c.P->kern.max_delta, c.h.H, c.h.W);
+  const int x0 = b.x0, y0 = b.y0, y1 = b.y1;
+  const int nrow = b.x1 - x0, wc = y1 - y0;
   const double tot = c.t.boxsum[(size_t)x * c.h.W + y];
   double seg = 0.0;
   if (c.lane < nrow) {
-    const double *rp = c.t.rowpart + (size_t)(x0 + c.lane) * c.h.W;
-    seg = rp[y1 - 1] - (y0 > 0 ? rp[y0 - 1] : 0.0);
+    // (with the table the rows' sums are consecutive entries: one coalesced read, mpp_window.hpp)
+    if (c.t.rowwin) seg = c.t.rowwin[rowwin_index(x0 + c.lane, y, c.h.H)];
+    else seg = window_row_seg(c.t.rowpart + (size_t)(x0 + c.lane) * c.h.W, y0, y1);
   }
   double before = 0.0;          // sum of the rows above the chosen one
   const double thr = u * tot;   // cdf <= u  <=>  partial sum <= u * total
@@ -1053,55 +1056,8 @@ __device__ int count_le_8ary(int n, F key_le) {
 }
 
 __device__ __forceinline__ void window_draw_lane(const Chain &c, int x, int y, double u, int *ex, int *ey) {
-  const DevParams *P = c.P;
-  const int md = P->kern.max_delta;
-  const int x0 = max(0, x - md), x1 = min(x + md + 1, c.h.H), y0 = max(0, y - md), y1 = min(y + md + 1, c.h.W);
-  const int nrow = x1 - x0, wc = y1 - y0;
-  const double tot = c.t.boxsum[(size_t)x * c.h.W + y];
-  double before = 0.0;
-  const double thr = u * tot;
-  int row = 0;
-  if (nrow <= 17 && wc <= 17) {
-    // the usual window (max_delta <= 8): the segment sums of all rows are requested together -- two memory latencies for
-    // the row, one for the column, instead of two per row walked -- and added in the order of the walk below
-    double seg[17];
-#pragma unroll
-    for (int i = 0; i < 17; ++i) {
-      const int xi = x0 + (i < nrow ? i : nrow - 1);
-      const MPP_GLOBAL double *rp = c.t.rowpart + (size_t)xi * c.h.W;
-      const double hi_ = rp[y1 - 1], lo_ = y0 > 0 ? rp[y0 - 1] : 0.0;
-      seg[i] = hi_ - lo_;
-    }
-    bool go = true;
-#pragma unroll
-    for (int i = 0; i < 17; ++i) {
-      const double nxt = before + seg[i];
-      go = go && i < nrow && nxt <= thr && i < nrow - 1;
-      if (go) { before = nxt; row = i + 1; }
-    }
-    const MPP_GLOBAL double *rp = c.t.rowpart + (size_t)(x0 + row) * c.h.W;
-    const double lead = y0 > 0 ? rp[y0 - 1] : 0.0;
-    double cv[17];
-#pragma unroll
-    for (int jj = 0; jj < 17; ++jj) cv[jj] = rp[y0 + (jj < wc ? jj : wc - 1)];
-    int col = 0;
-#pragma unroll
-    for (int jj = 0; jj < 17; ++jj) col += (jj < wc && (before + (cv[jj] - lead)) <= thr) ? 1 : 0;
-    if (col >= wc) col = wc - 1;
-    *ex = x0 + row; *ey = y0 + col;
-    return;
-  }
-  for (int i = 0; i < nrow; ++i) {
-    const double *rp = c.t.rowpart + (size_t)(x0 + i) * c.h.W;
-    double nxt = before + (rp[y1 - 1] - (y0 > 0 ? rp[y0 - 1] : 0.0));
-    if (nxt <= thr && i < nrow - 1) { before = nxt; row = i + 1; } else break;
-  }
-  const double *rp = c.t.rowpart + (size_t)(x0 + row) * c.h.W;
-  const double lead = y0 > 0 ? rp[y0 - 1] : 0.0;
-  int col = 0;
-  for (int jj = 0; jj < wc; ++jj) col += ((before + (rp[y0 + jj] - lead)) <= thr) ? 1 : 0;
-  if (col >= wc) col = wc - 1;
-  *ex = x0 + row; *ey = y0 + col;
+  // (the walk itself: mpp_window.hpp, shared with the host program that checks the table form against this one)
+  window_draw_rows(c.t.rowpart, c.t.boxsum, c.t.rowwin, c.h.H, c.h.W, c.P->kern.max_delta, x, y, u, ex, ey);
 }
 
 // which parts of the target's cached geometry survive the proposal

@@ -45,7 +45,7 @@ struct DevWs : DevBuf<unsigned char> {
 
 // the device arrays sized by mpp_set_maps: dropped together when the maps are replaced
 struct TileMem {
-  DevBuf<double> rowpart, rowbase, rowtot, boxsum, ps, pr, pa, T;
+  DevBuf<double> rowpart, rowbase, rowtot, boxsum, rowwin, ps, pr, pa, T;
   DevBuf<int32_t> px, py, n, errd;
   DevBuf<int64_t> step;
   DevBuf<long long> until;           // per tile: the absolute step the current mpp_run / mpp_replay call runs it to
@@ -69,6 +69,11 @@ struct mpp_ctx : TileMem {
   bool img_borrowed = false;
   bool box_dirty = true;
   bool cdf_ready = false;          // rowpart / rowbase / boxsum exist (made by the first launch that draws births)
+  // the data-driven translation reads its window's row sums from the transposed table rowwin (mpp_window.hpp; option
+  // window_rows, 0: the chains get a null pointer and form the sums from rowpart).  The table is made with boxsum, from the
+  // first push_state that finds the option on; win_dirty: it is not the one of the current maps and max_delta
+  int window_rows = 1;
+  bool win_dirty = true;
   int cap = 1024, cell_cap = 32, spec = 1, lanes = 0;
   // deep rounds (mpp_deep.hip): every lane of the chain's `spec` waves evaluates one step, at most `deep` steps per round
   // (default 128; 0 = off: one wave per step); deep_fixed > 0 pins the number of steps per round (tests); deep_stats: rounds, evaluated

@@ -23,6 +23,22 @@
 // index alone: a ring in LDS holds those of the next steps, extended by as many entries as a round commits.
 #include <cstdlib>
 
+#ifdef MPP_DEEP_PROF
+// diagnostic build only: cycles inside the draw of the data-driven translation (mpp_window.hpp), per wave, summed over the
+// launch -- up to the window's total, from there to the row, from there to the column.  The empty asm makes the stamp wait
+// for the value; the lanes of a wave that draw run the same instructions, the first of them adds the wave's cycles.  The
+// kernel moves the sums into phase slots 20 .. 22 of its wave when it ends.
+__device__ unsigned long long g_win_clk[16 * 3];
+#define MPP_WIN_T0() unsigned long long wt_ = clock64()
+#define MPP_WIN_STAMP(i, v)                                                                             \
+  do {                                                                                                  \
+    asm volatile("" ::"v"(v));                                                                          \
+    const unsigned long long n_ = clock64();                                                            \
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&g_win_clk[(threadIdx.x >> 6) * 3 + (i)], n_ - wt_); \
+    wt_ = n_;                                                                                           \
+  } while (0)
+#endif
+
 #include "mpp_chain.hpp"
 #include "mpp_commit.hpp"
 #include "mpp_prepass.hpp"
@@ -1149,6 +1165,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     c.t.ps[i] = L.s[slot]; c.t.pr[i] = L.r[slot]; c.t.pa[i] = L.a[slot];
   }
 #ifdef MPP_DEEP_PROF
+  if (c.lane == 0) for (int i = 0; i < 3; ++i) dph_[20 + i] = atomicExch(&g_win_clk[c.wave * 3 + i], 0ull);   // (one chain per launch: the probe's)
   if (stats && c.lane == 0) for (int i = 0; i < DPH_N; ++i) atomicAdd(stats + 16 + DPH_N * c.wave + i, dph_[i]);
 #endif
   if (tid == 0) {

@@ -60,6 +60,9 @@ struct TileRef {
   const MPP_GLOBAL double *rowpart;   // [H][W] inclusive partial sums of det within each row
   const MPP_GLOBAL double *rowbase;   // [H+1] exclusive prefix of row totals; rowbase[H] = sum(det)
   const MPP_GLOBAL double *boxsum;    // [H][W] sum of det over the (2*max_delta+1)^2 window clipped to the tile
+  // optional [W][H] sums of det over one row of that window, transposed (mpp_window.hpp); nullptr: the data-driven
+  // translation forms them from rowpart (option window_rows 0)
+  const MPP_GLOBAL double *rowwin;
   // optional [H][W][32] tables of the remapped mark probabilities -2*sigmoid(coef_k*P_k+icpt_k)+1 (the reference builds
   // these maps once per tile, energy_setup_legacy.py:142-147); nullptr: the three sigmoids are evaluated per proposal
   const MPP_GLOBAL double *rm[3];

@@ -114,6 +114,7 @@ void mpp_launch_birth_summary(hipStream_t st, int n_chains, int H, int W, const 
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);
+void mpp_launch_rowwin(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *rowwin);
 void mpp_launch_naive_init(hipStream_t st, const DevParams *P, const TileRef *tiles, int n_tiles, double threshold,
                            double nms_dist, unsigned long long *cand, int cand_cap);
 // the U-Net epilogues: the window (wx0, wy0, wh x ww) of an H x W crop into dst, row pitch ld_dst pixels (mpp_maps.hip, mpp_conv.hip)

@@ -12,6 +12,7 @@
 #include "mpp_launch.hpp"
 #include "mpp_rank_key.hpp"
 #include "mpp_unet_math.hpp"
+#include "mpp_window.hpp"
 
 // ---- birth CDF ---------------------------------------------------------------------------------
 // (all tiles of a context in one launch: blockIdx.y / blockIdx.x / blockIdx.z = tile)
@@ -57,6 +58,29 @@ extern "C" void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *row
     const size_t off = (size_t)t0 * H * W;
     hipLaunchKernelGGL(k_boxsum, dim3((W + 63) / 64, H, nt), dim3(64), 0, st, rowpart + off, H, W, md, boxsum + off);
   }
+}
+// rowwin (mpp_window.hpp): the sum of every row of every column's window, transposed -- rowwin[y][x] -- so that the rows a
+// draw of the data-driven translation walks lie side by side.  An entry is window_row_seg() of the two doubles the draw
+// reads without the table (and k_boxsum above adds up): the same subtraction of the same operands, hence the value the
+// draw forms today, bit for bit.  One lane per entry, consecutive lanes on consecutive x: the stores are coalesced, the
+// reads (two per entry, W * 8 bytes apart) are not -- the table is built once per set of maps.
+__global__ void k_rowwin(const double *rowpart_all, int H, int W, int md, double *rowwin_all) {
+  const size_t hw = (size_t)H * W;
+  const double *rowpart = rowpart_all + blockIdx.z * hw;
+  double *rowwin = rowwin_all + blockIdx.z * hw;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= H || y >= W) return;
+  const WinBox b = window_box(x, y, md, H, W);
+  rowwin[rowwin_index(x, y, H)] = window_row_seg(rowpart + (size_t)x * W, b.y0, b.y1);
+}
+// (rowwin: rowwin_count(n_tiles, H, W) doubles; the pad behind the last table is zeroed)
+extern "C" void mpp_launch_rowwin(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *rowwin) {
+  for (int t0 = 0; t0 < n_tiles; t0 += 65535) {            // gridDim.z limit
+    const int nt = n_tiles - t0 < 65535 ? n_tiles - t0 : 65535;
+    const size_t off = (size_t)t0 * H * W;
+    hipLaunchKernelGGL(k_rowwin, dim3((H + 63) / 64, W, nt), dim3(64), 0, st, rowpart + off, H, W, md, rowwin + off);
+  }
+  (void)hipMemsetAsync(rowwin + (size_t)n_tiles * H * W, 0, MPP_ROWWIN_PAD * sizeof(double), st);
 }
 extern "C" void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                                double *scratch_rowtot) {

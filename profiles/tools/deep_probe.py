@@ -33,7 +33,10 @@ def run(tile, objects, iters, spec, deep, fixed, reps, ntiles=1, cap=1024, repli
     st = ctx.deep_stats() if deep else {}
     if deep and os.environ.get("MPP_LIB_PATH", "").endswith("dprof.so"):
         names = ["A:types", "A:bar1", "A:sort+bar2", "B:draw", "B:pre", "E:delta(total)", "B:post", "bar3", "C:decide+trace+ring", "D:apply-delta",
-                 "D:bar4", "D:mutate", "e:tasks", "e:append", "e:load", "e:overlap", "e:pairs+rescan", "e:combine", "C:set-up+pairs", "C:bar5"]
+                 "D:bar4", "D:mutate", "e:tasks", "e:append", "e:load", "e:overlap", "e:pairs+rescan", "e:combine", "C:set-up+pairs", "C:bar5",
+                 "draw:tot", "draw:row", "draw:col"]
+        # (draw:*: inside B:draw, the data-driven translation's draw alone (csrc/mpp_window.hpp) -- up to the window's total,
+        # from there to the row, from there to the column)
         # (C of a round whose changing steps are dealt: "C:set-up+pairs" up to the exchange, "C:bar5" the wait at its barrier,
         # the rest -- the rule, tracing, the queues' cursors -- under "C:decide+trace+ring"; a round without: all of it there)
         R = max(1, st["rounds"])
