@@ -148,6 +148,10 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     // the data-driven translation reads its window's row sums from the transposed table (0: it forms them from rowpart)
     if (v < 0 || v > 1) return fail(c, -1, "window_rows must be 0 or 1");
     c->window_rows = (int)v; c->tiles_dirty = true;
+  } else if (!strcmp(name, "deep_skip_same")) {
+    // an untraced deep round skips the evaluation of a step that re-writes its target with the values it holds (0: it evaluates it)
+    if (v < 0 || v > 1) return fail(c, -1, "deep_skip_same must be 0 or 1");
+    c->deep_skip_same = (int)v;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -186,6 +190,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "hot_table_used")) return c->hot_table_used;
   if (!strcmp(name, "hot_past_births")) return c->hp.hot_past;
   if (!strcmp(name, "window_rows")) return c->window_rows;
+  if (!strcmp(name, "deep_skip_same")) return c->deep_skip_same;
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now

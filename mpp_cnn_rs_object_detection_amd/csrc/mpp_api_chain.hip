@@ -274,7 +274,8 @@ int ChainRun::launch_lds() {
     }
     if (pt.word) c->prepass_used = 1;
     if (pt.qoff) c->prepass_queues_used = 1;
-    HIPCHK(c, mpp_launch_deep(a, sh.waves, occ, nmax, fixed, c->deep_gain, (unsigned long long *)c->deep_stats.p, sh.ext, &pt));
+    const int flags = c->deep_skip_same ? MPP_DEEP_SKIP_SAME : 0;
+    HIPCHK(c, mpp_launch_deep(a, sh.waves, occ, nmax, fixed, c->deep_gain, flags, (unsigned long long *)c->deep_stats.p, sh.ext, &pt));
   } else {
     // the hot start reads its steps' draws from a table (mpp_hot.hip) where the pre-pass builds one with queues whose words can
     // carry a queue position; otherwise -- and for every other one-wave-per-step launch -- the chain draws them itself

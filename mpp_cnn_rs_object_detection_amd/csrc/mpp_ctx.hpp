@@ -82,6 +82,11 @@ struct mpp_ctx : TileMem {
   int handover_at = 1280;            // ... when the smoothed steps committed per round of 8 reach this / 256 (5.0: one tile is flat from 4.5 to 6.5, 64 tiles want it early -- 34.8 ms at 5.0, 36.3 at 5.5, 42 at 6.5)
   int handover_tiles = 64;           // ... in launches of at most this many chains (64 tiles of config 4: -6 %; 256 of config 5: +4 %)
   int deep = 128, deep_fixed = 0, deep_gain = 12;   // deep_gain / 8 x the steps the last rounds committed = depth of the next (12: 4 % faster than 16 on the bench tile and on config 5's chains, 10 and 20 slower)
+  // deep_skip_same 1: an untraced deep round does not evaluate a move / transform that proposes the values its target already
+  // holds (the step changes nothing, accepted or not, and nothing reads its outcome); 0: every step is evaluated.  It travels
+  // as a flag of mpp_launch_deep, not in DevParams: the block is an argument of every chain kernel, and a field more
+  // would move the arguments behind it in kernels this option has nothing to do with
+  int deep_skip_same = 1;
   DevWs deep_stats;
   // the birth pre-pass of a deep launch (mpp_prepass.hip): prepass 1 on, 0 off (the chains draw their births themselves);
   // a launch whose table would exceed prepass_mb MB runs without one; prepass_used: a deep launch of the last call used one

@@ -464,6 +464,14 @@ __device__ __forceinline__ void deep_mutate(const Chain &c, const Rec &r, int n,
     write_slot_1(c, slot, r);
   }
 }
+// Does a move / transform propose the five values its target already holds?  Committing it writes the bits that are there:
+// the cached geometry, unit energy and reductions are functions of those values.  The comparison is on the values (a mark
+// that sits off the class edges differs from the edge of its own class); float ==: -0.0 equals 0.0, a NaN equals nothing.
+__device__ __forceinline__ bool deep_same_values(const Lds &L, const Rec &r) {
+  if (!(r.has_rem && r.has_add)) return false;
+  const int sl = r.tslot;
+  return r.ax == r.rx && r.ay == r.ry && r.as == L.s[sl] && r.ar == L.r[sl] && r.aa == L.a[sl];
+}
 __device__ __forceinline__ unsigned long long low_mask(int k) { return k <= 0 ? 0ull : (k >= 64 ? ~0ull : ((1ull << k) - 1ull)); }
 
 // (QUE) The fields of a step that the neighbour pass does not read wait in LDS while it runs, in space of the step's own
@@ -515,11 +523,12 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
                                                                  const long long *until, long long trace_base,
                                                                  unsigned long long seed, unsigned int chain0, int trace_tile,
                                                                  mpp_step_out *out, mpp_proposal *props, int nmax,
-                                                                 int fixed_depth, int gain8, unsigned long long *stats,
-                                                                 PreTab pt) {
+                                                                 int fixed_depth, int gain8, int flags,
+                                                                 unsigned long long *stats, PreTab pt) {
   static_assert(!(TAB && EXT), "the pre-pass table is built for the instantiations without classic image energies");
   static_assert(!QUE || (TAB && WAVES == 8), "the queues are dealt to eight waves");
   const bool by_type = (gain8 & 0x100) == 0;      // (bit 8 of the gain word: deal the sorted steps in blocks instead -- A/B tests)
+  const bool skip_opt = (flags & MPP_DEEP_SKIP_SAME) != 0;        // (option deep_skip_same)
   gain8 &= 0xff;
   const DevParams *P = stage_params<(WAVES >= MPP_LDS_PARAMS_MIN_WAVES)>(Pv, WAVE * WAVES);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -539,6 +548,10 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   const Lds &L = c.L;
   const int tid = threadIdx.x, nthr = WAVE * WAVES;
   const bool tracing = DIAG && (out != nullptr || props != nullptr) && tile == trace_tile;
+  // A step that proposes the values its target already holds (deep_same_values) leaves the configuration as it is, accepted
+  // or not, and in an untraced chain nothing reads its dE, its densities or its accept bit: such a step is not evaluated.
+  // A traced chain records them for every step: it never skips.
+  const bool skip_same = skip_opt && !tracing;
 
   // ---------------------------------------------------------------- load the configuration (as mpp_chain_kernel does)
   int n0 = __builtin_amdgcn_readfirstlane(*c.t.n);
@@ -661,6 +674,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   }
   while (stage == 0 || (done < n_steps && err == 0)) {
     bool do_eval = my_commit && r.n_stash > 2;  // stage 0: the steps that commit and change more neighbours than they could note
+    bool same = false;                          // stage 1: my step re-writes its target unchanged and is not evaluated (skip_same)
     DPH_T0();
     if (stage == 1) {
     int N = fixed_depth > 0 ? fixed_depth : depth;
@@ -728,14 +742,15 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
         else draw_tail_q(c, kq, qe, n, r, &keep);
         DPH(3);
         if (r.valid && r.has_add && (r.ax < 0 || r.ax >= c.h.H || r.ay < 0 || r.ay >= c.h.W)) { r.valid = 0; r.kernel = -1; }
-        if (r.valid && !pre_b) {
+        same = skip_same && r.valid && deep_same_values(L, r);
+        if (r.valid && !pre_b && !same) {
           const MapVals pmv{0.f, 0.f, 0.f, 0.f, 0.0, 0.0, 0.0, 0};
           deep_add_geo(c, r, keep);
           deep_pre<false>(c, r, keep, tracing, pmv, nullptr);
         }
-        deep_park(D, myoff, r);
+        if (!same) deep_park(D, myoff, r);
       }
-      do_eval = mine && r.valid && (r.has_rem || r.has_add);
+      do_eval = mine && r.valid && (r.has_rem || r.has_add) && !same;
       DPH(4);
     } else {
     const bool act0 = c.lane < Lw;
@@ -753,15 +768,15 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       while (kt < P->n_kernels - 1 && P->p_cum[kt] <= uk) ++kt;
       if (TAB && (kt == MPP_K_UBIRTH || kt == MPP_K_DBIRTH)) pword = pt.word[(size_t)blockIdx.x * pt.stride + done + e];
     }
-    unsigned long long same = 0ull;
+    unsigned long long same_kt = 0ull;
     int cnt_lane = 0;                           // lane k: steps of type k in this wave
 #pragma unroll
     for (int k = 0; k < MPP_NKERNEL; ++k) {
       const unsigned long long m = __ballot(kt == k);
-      if (kt == k) same = m;
+      if (kt == k) same_kt = m;
       if (c.lane == k) cnt_lane = __popcll(m);
     }
-    const int rank = __popcll(same & below);
+    const int rank = __popcll(same_kt & below);
     if (c.lane < 16) D.tcnt[c.wave * 16 + c.lane] = (unsigned short)cnt_lane;
     DPH(0);
     __syncthreads();                            // (1) also: the changes of the previous round are in place
@@ -867,7 +882,8 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       DPH(3);
       if (r.kernel >= MPP_K_SPLIT) { r.valid = 0; r.kernel = -1; }
       if (r.valid && r.has_add && (r.ax < 0 || r.ax >= c.h.H || r.ay < 0 || r.ay >= c.h.W)) { r.valid = 0; r.kernel = -1; }
-      if (r.valid && !pre_b) {
+      same = skip_same && r.valid && deep_same_values(L, r);
+      if (r.valid && !pre_b && !same) {
         deep_add_geo(c, r, keep);
         if (!EXT) deep_pre<EXT>(c, r, keep, tracing, pmv, nullptr);
       }
@@ -881,7 +897,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       int cterm = -1;
       for (int k = 0; k < P->model.n_unit; ++k) if (P->model.unit[k].kind == MPP_U_CONTRAST) cterm = k;
       if (cterm >= 0) {
-        unsigned long long m = __ballot(mine && r.valid && r.has_add);
+        unsigned long long m = __ballot(mine && r.valid && r.has_add && !same);
         while (m) {
           const int l = __ffsll((long long)m) - 1;
           m &= m - 1;
@@ -893,8 +909,8 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
         }
       }
     }
-    if (EXT && mine && r.valid) deep_pre<EXT>(c, r, keep_x, tracing, pmv_x, have_cpre ? &cpre : nullptr);
-    do_eval = mine && r.valid && (r.has_rem || r.has_add);
+    if (EXT && mine && r.valid && !same) deep_pre<EXT>(c, r, keep_x, tracing, pmv_x, have_cpre ? &cpre : nullptr);
+    do_eval = mine && r.valid && (r.has_rem || r.has_add) && !same;
     DPH(4);
     }
     }
@@ -925,15 +941,18 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     if (mine) {
       // the step's temperature: its ring entry stays as it is while the step is in the window (the ring is filled two rounds ahead)
       const double Tm = D.tring[(int)((done + myoff) & (long long)rmask)];
-      if constexpr (QUE) deep_unpark_green(D, myoff, r);
-      if (r.valid) deep_post(c, r, n, Tm, tracing);
+      // (a skipped step: nothing was parked for it, and no test is made.  Its report below is the one an evaluated re-write
+      // gets, whichever way its test goes -- no DI_CHG, hence no DI_FULL / DI_NB*; no DI_RESC, for its added rectangle has the
+      // removed one's bits and takes every extremum over; the reach radius from the target's cache, r.rad being 0 -- except
+      // for DI_ACC, which the commit decision does not read: the bit stays clear, r.accepted is 0 from the round's reset.)
+      if (!same) {
+        if constexpr (QUE) deep_unpark_green(D, myoff, r);
+        if (r.valid) deep_post(c, r, n, Tm, tracing);
+      }
       // does the step change the configuration?  An accepted move that writes the values the slot already holds does not
       // (its cached geometry, unit energy and reductions are functions of those values: the same bits)
       bool chg = r.valid && r.accepted && (r.has_rem || r.has_add);
-      if (chg && r.has_rem && r.has_add) {
-        const int sl = r.tslot;
-        chg = !(r.ax == r.rx && r.ay == r.ry && r.as == L.s[sl] && r.ar == L.r[sl] && r.aa == L.a[sl]);
-      }
+      if (chg && deep_same_values(L, r)) chg = false;
       bool full = false;
       if (chg && r.has_add) {
         int ci, cj;
@@ -1183,14 +1202,14 @@ extern "C" size_t mpp_deep_lds_bytes(int cap, int ncell, int cell_cap, int rowba
 }
 
 template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false, int NCH = DEEP_NMAX_LIMIT / 64>
-static hipError_t launch_deep_d(const ChainLaunch &a, int nmax, int fixed_depth, int gain8, unsigned long long *stats,
-                                const PreTab &pt) {
+static hipError_t launch_deep_d(const ChainLaunch &a, int nmax, int fixed_depth, int gain8, int flags,
+                                unsigned long long *stats, const PreTab &pt) {
   if (nmax > 64 * NCH) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>), dim3(a.grid), dim3(WAVE * WAVES), a.lds, a.st, *a.P, a.tiles,
-                     a.tile0, a.until, a.trace_base, a.seed, a.chain0, a.trace_tile, a.out, a.props, nmax, fixed_depth, gain8, stats, pt);
+                     a.tile0, a.until, a.trace_base, a.seed, a.chain0, a.trace_tile, a.out, a.props, nmax, fixed_depth, gain8, flags, stats, pt);
   return hipGetLastError();
 }
 
@@ -1198,14 +1217,16 @@ static hipError_t launch_deep_d(const ChainLaunch &a, int nmax, int fixed_depth,
 // ext: a classic image energy among the unit terms (built for 1 and 8 waves, like the one-wave-per-step kernels)
 // pt: the launch's birth table (mpp_prepass.hip), or pt->word == nullptr: the chains draw their births themselves; with
 // pt->qoff, eight waves and the cost deal (gain8 without bit 8), the rounds take their steps from the table's queues
+// flags: MPP_DEEP_SKIP_SAME: an untraced chain does not evaluate the steps that re-write their target unchanged (option
+// deep_skip_same)
 // (a.tape is not read: deep rounds draw their proposals from Philox)
-extern "C" hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8,
+extern "C" hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8, int flags,
                                       unsigned long long *stats, int ext, const PreTab *pt) {
   const bool diag = a.out || a.props, tab = pt->word != nullptr && !ext;
   // GO_(W, O, X, T[, Q, N]): that instantiation, traced or not
 #define GO_(W, ...)                                                                                        \
-  return diag ? launch_deep_d<W, true, __VA_ARGS__>(a, nmax, fixed_depth, gain8, stats, *pt)               \
-              : launch_deep_d<W, false, __VA_ARGS__>(a, nmax, fixed_depth, gain8, stats, *pt)
+  return diag ? launch_deep_d<W, true, __VA_ARGS__>(a, nmax, fixed_depth, gain8, flags, stats, *pt)               \
+              : launch_deep_d<W, false, __VA_ARGS__>(a, nmax, fixed_depth, gain8, flags, stats, *pt)
   if (tab && pt->qoff != nullptr && waves == 8 && (gain8 & 0x100) == 0) {
     // the queue rounds keep two chunks of step reports per lane where the round has at most 128 steps (the default depth), four above
     if (nmax <= 128) { GO_(8, 2, false, true, true, 2); }

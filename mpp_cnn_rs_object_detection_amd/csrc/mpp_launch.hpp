@@ -51,6 +51,9 @@ struct BirthCache { double *lin, *r0, *r1, *e; int32_t *gate; };
 #define MPP_BIRTH_PARTS 256                        // partial summaries per chain (one per workgroup of the first pass)
 struct BirthPart { double v; long long idx, n_neg, n_nan; };   // smallest non-NaN value and its row-major index (-1: none)
 
+// flags of mpp_launch_deep
+#define MPP_DEEP_SKIP_SAME 1                       // option deep_skip_same: steps that re-write their target unchanged are not evaluated
+
 extern "C" {
 size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);
 size_t mpp_chain_static_lds_bytes(int waves);      // the staged parameter block: the same for every chain kernel
@@ -59,7 +62,7 @@ size_t mpp_chain_hbm_lds_bytes(int spec, int rowbase_n);
 size_t mpp_deep_lds_bytes(int cap, int ncell, int cell_cap, int rowbase_n, int waves, int nmax, int ext);
 hipError_t mpp_launch_chain(const ChainLaunch &a, int spec, int lanes, int occ);
 hipError_t mpp_launch_chain_hbm(const ChainLaunch &a, int waves, unsigned char *ws, size_t ws_stride);
-hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8,
+hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8, int flags,
                            unsigned long long *stats, int ext, const PreTab *pt);
 hipError_t mpp_launch_hot(const ChainLaunch &a, const PreTab *pt);
 hipError_t mpp_prepass_count(hipStream_t st, const DevParams *P, const TileRef *tiles, int tile0, int n_chains,
