@@ -256,6 +256,40 @@ int mpp_merge_score(mpp_ctx *ctx, double distance, int cap, int32_t *n_out, int3
 #define MPP_BIRTH_CHUNK 256        /* points staged per pass of a block */
 typedef struct { double min_dE; int32_t x, y; int64_t n_negative, n_nan; } mpp_birth_summary;
 int mpp_birth_energy_map(mpp_ctx *ctx, double *dE, double *marks_or_null, mpp_birth_summary *summary_or_null);
+/* The local minima of a float64 map below a level (csrc/mpp_birth_complete.hip): dE_dev [H][ld] float64, xy [cap][2] int32
+ * (row, col) and values [cap] float64 are DEVICE pointers; n_candidates / n_kept are host pointers (either may be NULL); the
+ * ctx's stream, synchronous.
+ *  - candidates: the pixels with dE < below.  A NaN never is one, -inf is;
+ *  - key: key(c) = (dE(c), x * W + y), compared lexicographically: equal values (-inf included) tie toward the smaller
+ *    row-major index;
+ *  - kept: a candidate c is kept iff no OTHER candidate c' with (double)(dx*dx + dy*dy) <= distance * distance has
+ *    key(c') < key(c).  The rule does not depend on an order of visits (it is not the rank-order NMS of mpp_detect_centers):
+ *    a candidate that loses to a neighbour which itself loses is dropped too -- callers that repeat the selection give it
+ *    its turn in a later round.  A non-candidate never beats a candidate: this is the minimum filter over the disc;
+ *  - output: the kept pixels and their values in ASCENDING ROW-MAJOR ORDER.  If more than cap are kept: -13, *n_kept = the
+ *    number needed, nothing written to xy / values.
+ * The candidates are compacted by ballot into a list in a workspace of the ctx (12 B per pixel at most, grown on demand) and
+ * resolved among the list only.  -1: distance < 0, a non-finite distance or below, ld < W, H*W >= 2^31, H or W < 1. */
+int mpp_select_minima(mpp_ctx *ctx, int H, int W, int ld, const double *dE_dev, double below, double distance, int cap,
+                      int32_t *xy, double *values, int64_t *n_candidates, int64_t *n_kept);
+/* Greedy completion: births from the birth-energy map until none lowers the energy by more than min_gain.  Every chain of the
+ * ctx on its own, from the state mpp_get_points_all reads.  A round:
+ *   the map of mpp_birth_energy_map of the current state (into a workspace of the ctx: 8 B per pixel per chain);
+ *   mpp_select_minima on it with below = -min_gain and distance = 2 * max_inter, max_inter the model's largest pair range --
+ *   two kept candidates then neither interact nor share a neighbour, so in real arithmetic the round lowers the energy by
+ *   exactly the sum of its dE;
+ *   the kept candidates u_c (the map's candidates: position c, marks edges[k][argmax class]) are appended to the chain's
+ *   configuration in slots n .. n+k-1, ascending row-major order.  The chain is then in the state mpp_set_points(old + new)
+ *   leaves.  Nothing crosses to the host but one record per chain and round.
+ * status 0: a round kept nothing (converged); 1: max_rounds rounds have appended points (1 <= max_rounds <= 1024); 2: the
+ * points of a round do not fit point_capacity -- nothing of that round is appended to that chain, the other chains go on.
+ * rounds: the rounds that appended points; n_added their points; n_after the chain's count; gain the sum of the appended dE,
+ * added one after another to a float64 that starts at 0.0, round by round and in slot order within a round; min_dE, x, y,
+ * n_negative, n_nan: the mpp_birth_summary of the map of the RETURNED state (after status 1 one more map is computed).
+ * report [n_chains]: HOST.  -1 with a message: max_rounds outside 1..1024, min_gain negative or not finite, and the refusals of
+ * mpp_birth_energy_map (no maps or no model; a classic image energy; more than 65535 chains). */
+typedef struct { int32_t status, rounds, n_added, n_after; double gain, min_dE; int32_t x, y; int64_t n_negative, n_nan; } mpp_complete_report;
+int mpp_birth_complete(mpp_ctx *ctx, int max_rounds, double min_gain, mpp_complete_report *report);
 /* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points.  Candidates are
  * det >= (float)threshold (float32, as NumPy compares); rank and NMS rule as mpp_detect_centers below.  A tile that keeps more
  * than point_capacity points: -12 ("naive init, tile t"), its first point_capacity picks stay stored; every call replaces

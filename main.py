@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Command-line entry, same flags as the reference's ``main.py:11-109``:
 
-    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map]
-    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map]
+    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map] [--birth-complete]
+    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map] [--birth-complete]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
 hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the CNN-only baseline's detections (DOTA hbb /
@@ -65,6 +65,11 @@ def build_parser():
                         help="(-m mpp, infer / infereval / detect) per image the birth-energy map under its detections -- the energy "
                              "change of a new object at every pixel: NNNN_birth_energy.png, the key birth_summary of the pickle and "
                              "one log line; same as inference.birth_map in the config")
+    parser.add_argument("--birth-complete", action="store_true",
+                        help="(-m mpp, infer / infereval / detect) complete every image's detections from its birth-energy map: "
+                             "births at the map's local minima, round after round, until no new object lowers the energy; the "
+                             "results are those of the completed list, the pickle gains the key birth_complete and one line is "
+                             "logged; same as inference.birth_complete in the config (whose max_rounds / min_gain it keeps)")
     parser.add_argument("--images", nargs="+", default=None, metavar="PATH",
                         help="(-p detect) image files, or directories whose image files are taken in sorted order")
     parser.add_argument("--out", default=None, metavar="DIR", help="(-p detect) where the results go")
@@ -74,6 +79,15 @@ def build_parser():
     parser.add_argument("--model-gsd", type=float, default=0.5, help="(-p detect) ground sampling distance the nets were trained at")
     parser.add_argument("--min-score", type=float, default=None, help="(-p detect) drop detections scored below this from the CSV")
     return parser
+
+
+def apply_birth_complete(args, config):
+    """--birth-complete turns inference.birth_complete on; parameters the config gives for it stay"""
+    if args.birth_complete and args.procedure in ("infer", "infereval", "detect"):
+        inference = config.setdefault("inference", {})
+        if not isinstance(inference.get("birth_complete"), dict):
+            inference["birth_complete"] = True
+    return config
 
 
 def main():
@@ -109,6 +123,7 @@ def main():
             config.setdefault("inference", {})["restarts"] = args.restarts
         if args.birth_map:
             config.setdefault("inference", {})["birth_map"] = True
+        apply_birth_complete(args, config)
         model = MPPModel(config, phase="val", load=True, device=local_rank,
                          nets=load_nets(config, local_rank, args.unet_max_pixels), spec_waves=args.spec_waves)
         detect.detect_files(model, args.images, args.out, gsd=args.gsd, model_gsd=args.model_gsd, min_score=args.min_score,
@@ -124,6 +139,7 @@ def main():
             config.setdefault("inference", {})["figures"] = True
         if args.birth_map and args.procedure in ("infer", "infereval"):
             config.setdefault("inference", {})["birth_map"] = True
+        apply_birth_complete(args, config)
         nets = None
         if args.unet:
             nets = load_nets(config, local_rank, args.unet_max_pixels)

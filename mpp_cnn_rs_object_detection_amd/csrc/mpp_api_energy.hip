@@ -1,5 +1,7 @@
 // mpp_api_energy.hip -- the from-scratch side of the C ABI (mpp_scratch.hip, mpp_maps.hip, mpp_gather.hip, mpp_metrics.hip):
 // total energy, deltas, Papangelou, merge + scoring, naive initialisation, packing of detections, rotated IoU.
+#include <cmath>
+
 #include "mpp_ctx.hpp"
 
 // Build the candidate grid of `tile` when its configuration is large enough to pay for four small launches; returns
@@ -96,19 +98,19 @@ extern "C" int mpp_total_energy_all(mpp_ctx *c, double *energy) {
   return 0;
 }
 
-// The birth-energy map of every chain (mpp_birth_map.hip): grids as mpp_total_energy_all builds them, the pre-pass that
-// caches every point's record, the map, and -- when asked for -- the summary, whose copy back is the call's only wait.
-extern "C" int mpp_birth_energy_map(mpp_ctx *c, double *dE, double *marks, mpp_birth_summary *summary) {
-  if (!c) return -1;
-  if (!c->have_maps || !c->have_model) return fail(c, -1, "birth_energy_map: mpp_set_maps / mpp_set_model have not been called");
-  if (!dE) return fail(c, -1, "birth_energy_map: dE is NULL");
+// What mpp_birth_energy_map and mpp_birth_complete refuse alike; `who` names the caller in the message.
+static int birth_refusals(mpp_ctx *c, const char *who) {
+  if (!c->have_maps || !c->have_model) return fail(c, -1, "%s: mpp_set_maps / mpp_set_model have not been called", who);
   if (model_class(c->hp).classic)
-    return fail(c, -1, "birth_energy_map: the model has a classic image energy (a candidate per pixel would need a rasterised "
-                       "footprint per pixel)");
-  int rc = push_state(c);
-  if (rc) return rc;
+    return fail(c, -1, "%s: the model has a classic image energy (a candidate per pixel would need a rasterised "
+                       "footprint per pixel)", who);
+  return 0;
+}
+// The launches of one birth-energy map of every chain (mpp_birth_map.hip): grids as mpp_total_energy_all builds them, the
+// pre-pass that caches every point's record, the map.  After push_state; part / d_sum: the summary's workspace.
+static int birth_map_launches(mpp_ctx *c, const char *who, double *dE, double *marks, BirthPart **part, mpp_birth_summary **d_sum) {
   const int T = c->n_tiles, ncell = c->hp.nx * c->hp.ny;
-  if (T > 65535) return fail(c, -1, "birth_energy_map: %d chains, at most 65535", T);
+  if (T > 65535) return fail(c, -1, "%s: %d chains, at most 65535", who, T);
   const bool grid = c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points;
   const size_t TC = (size_t)T * c->cap;
   // doubles: lin, r0, r1, e [T][cap]; the summary's parts and results; ints: gate [T][cap], then the grids
@@ -117,9 +119,9 @@ extern "C" int mpp_birth_energy_map(mpp_ctx *c, double *dE, double *marks, mpp_b
   if (c->birth_ws.reserve(c->stream, 4 * TC * sizeof(double) + part_bytes + sum_bytes + n_int * sizeof(int32_t)) != hipSuccess)
     return fail(c, -2, "no device memory for the point cache of %d chains", T);
   double *d0 = (double *)c->birth_ws.p;
-  BirthPart *part = (BirthPart *)(d0 + 4 * TC);
-  mpp_birth_summary *d_sum = (mpp_birth_summary *)(part + (size_t)T * MPP_BIRTH_PARTS);
-  int32_t *gate = (int32_t *)(d_sum + T);
+  *part = (BirthPart *)(d0 + 4 * TC);
+  *d_sum = (mpp_birth_summary *)(*part + (size_t)T * MPP_BIRTH_PARTS);
+  int32_t *gate = (int32_t *)(*d_sum + T);
   const BirthCache bc{d0, d0 + TC, d0 + 2 * TC, d0 + 3 * TC, gate};
   int32_t *gs = grid ? gate + TC : nullptr, *gc = grid ? gs + (size_t)T * (ncell + 1) : nullptr;
   int32_t *gi = grid ? gc + (size_t)T * ncell : nullptr;
@@ -127,15 +129,123 @@ extern "C" int mpp_birth_energy_map(mpp_ctx *c, double *dE, double *marks, mpp_b
   if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, gs, gc, gi);
   mpp_launch_birth_prepass(c->stream, c->dp, c->d_tiles, T, c->cap, bc, gs, gi, ncell + 1, c->grid_min_points);
   mpp_launch_birth_map(c->stream, c->dp, c->d_tiles, T, c->cap, c->H, c->W, bc, dE, marks);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && summary) {
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// The birth-energy map of every chain, and -- when asked for -- the summary, whose copy back is the call's only wait.
+extern "C" int mpp_birth_energy_map(mpp_ctx *c, double *dE, double *marks, mpp_birth_summary *summary) {
+  if (!c) return -1;
+  int rc = birth_refusals(c, "birth_energy_map");
+  if (rc) return rc;
+  if (!dE) return fail(c, -1, "birth_energy_map: dE is NULL");
+  if ((rc = push_state(c))) return rc;
+  BirthPart *part;
+  mpp_birth_summary *d_sum;
+  if ((rc = birth_map_launches(c, "birth_energy_map", dE, marks, &part, &d_sum))) return rc;
+  if (summary) {
+    const int T = c->n_tiles;
     mpp_launch_birth_summary(c->stream, T, c->H, c->W, dE, part, d_sum);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_sum, sum_bytes, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(summary, d_sum, (size_t)T * sizeof(mpp_birth_summary), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
     HIPCHK(c, e); HIPCHK(c, e2);
   }
-  HIPCHK(c, e);
+  return 0;
+}
+
+// The first block of a selection and its workspace (mpp_birth_complete.hip)
+static int minsel_setup(mpp_ctx *c, MinSel *s, const double *dE, size_t chain_stride, int T, int H, int W, int ld, double below,
+                        double distance, const mpp_complete_report *rep) {
+  *s = MinSel{};
+  s->dE = dE; s->chain_stride = chain_stride; s->H = H; s->W = W; s->ld = ld; s->n_chains = T;
+  s->below = below; s->d2 = distance * distance;
+  const double side = (double)(H > W ? H : W);
+  s->reach = (int)floor(distance < side ? distance + 1.0 : side);     // (one more than floor(distance): the test itself is d2's)
+  s->rep = rep;
+  if (c->minsel_ws.reserve(c->stream, mpp_minsel_bytes(T, H, W)) != hipSuccess)
+    return fail(c, -2, "no device memory for the candidate list of %d map(s) of %d x %d", T, H, W);
+  mpp_minsel_plan(s, c->minsel_ws.p);
+  return 0;
+}
+
+extern "C" int mpp_select_minima(mpp_ctx *c, int H, int W, int ld, const double *dE, double below, double distance, int cap,
+                                 int32_t *xy, double *values, int64_t *n_candidates, int64_t *n_kept) {
+  if (!c) return -1;
+  if (H < 1 || W < 1 || ld < W || !dE || cap < 0 || (cap > 0 && (!xy || !values)) || !(distance >= 0.0) || !std::isfinite(distance) ||
+      !std::isfinite(below) || (long long)H * W >= (1ll << 31))
+    return fail(c, -1, "bad select_minima arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  MinSel s;
+  int rc = minsel_setup(c, &s, dE, 0, 1, H, W, ld, below, distance, nullptr);
+  if (rc) return rc;
+  mpp_launch_minsel(c->stream, s);
+  hipError_t e = hipGetLastError();
+  int32_t n[2] = {0, 0};                                   // (n_cand and n_kept lie side by side for one chain)
+  if (e == hipSuccess) e = hipMemcpyAsync(n, s.n_cand, sizeof n, hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  if (n_candidates) *n_candidates = n[0];
+  if (n_kept) *n_kept = n[1];
+  if (n[1] > cap) return fail(c, -13, "select_minima: %d minima kept, the output holds %d", n[1], cap);
+  if (n[1] > 0) {
+    mpp_launch_minsel_emit(c->stream, s, cap, xy, values);
+    e = hipGetLastError();
+    e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e2);
+  }
+  return 0;
+}
+
+// Greedy completion.  Per round: the launches of the map, of the selection and of the append, and one
+// copy of the chains' reports; the maps and the point lists stay on the device.
+extern "C" int mpp_birth_complete(mpp_ctx *c, int max_rounds, double min_gain, mpp_complete_report *report) {
+  if (!c) return -1;
+  int rc = birth_refusals(c, "birth_complete");
+  if (rc) return rc;
+  if (!report) return fail(c, -1, "birth_complete: report is NULL");
+  if (max_rounds < 1 || max_rounds > 1024) return fail(c, -1, "birth_complete: max_rounds %d, must be 1..1024", max_rounds);
+  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(c, -1, "birth_complete: min_gain must be finite and >= 0");
+  if ((rc = push_state(c))) return rc;
+  const int T = c->n_tiles, H = c->H, W = c->W;
+  if (T > 65535) return fail(c, -1, "birth_complete: %d chains, at most 65535", T);
+  const size_t hw = (size_t)H * W, TC = (size_t)T * c->cap;
+  if (c->complete_ws.reserve(c->stream, (T * hw + TC) * sizeof(double) + (size_t)T * sizeof(mpp_complete_report)) != hipSuccess)
+    return fail(c, -2, "no device memory for the maps of %d chains", T);
+  double *dE = (double *)c->complete_ws.p, *gain_val = dE + T * hw;
+  mpp_complete_report *rep = (mpp_complete_report *)(gain_val + TC);
+  MinSel s;
+  if ((rc = minsel_setup(c, &s, dE, hw, T, H, W, W, -min_gain, 2.0 * c->hp.max_inter, rep))) return rc;
+  mpp_launch_complete_init(c->stream, T, rep);
+  BirthPart *part = nullptr;
+  mpp_birth_summary *d_sum = nullptr;
+  bool open = true, limit = false;
+  std::vector<int32_t> was(T, -1);
+  // (a chain is open for at most max_rounds appending rounds and the one that closes it)
+  for (int round = 0; round <= max_rounds && open; ++round) {
+    if ((rc = birth_map_launches(c, "birth_complete", dE, nullptr, &part, &d_sum))) return rc;
+    mpp_launch_minsel(c->stream, s);
+    mpp_launch_complete_round(c->stream, s, c->dp, c->d_tiles, c->cap, gain_val, max_rounds, rep);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(report, rep, (size_t)T * sizeof(mpp_complete_report), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e2);
+    open = limit = false;                                  // limit: a chain appended in this round and stopped at max_rounds
+    for (int t = 0; t < T; ++t) {
+      open = open || report[t].status < 0;
+      limit = limit || (report[t].status == 1 && was[t] < 0);
+      was[t] = report[t].status;
+    }
+  }
+  if (open) return fail(c, -9, "birth_complete: a chain is still open after %d rounds", max_rounds + 1);
+  // the summary of the returned state's map: the last map is that of every chain but those its round stopped at the limit
+  if (limit && (rc = birth_map_launches(c, "birth_complete", dE, nullptr, &part, &d_sum))) return rc;
+  mpp_launch_birth_summary(c->stream, T, H, W, dE, part, d_sum);
+  mpp_launch_complete_summary(c->stream, T, d_sum, rep);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(report, rep, (size_t)T * sizeof(mpp_complete_report), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
   return 0;
 }
 

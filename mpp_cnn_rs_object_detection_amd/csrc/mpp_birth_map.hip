@@ -9,6 +9,7 @@
 // from-scratch reduction bit for bit.  A pre-pass caches per point what does not depend on c -- lin, gate, the reductions and
 // e(v | X), through point_reductions of mpp_scratch.hpp, the code of mpp_total_energy -- and the map kernel, one lane per
 // pixel, adds the candidate to the cached reductions of the points near its block of pixels, staged in LDS.
+#include "mpp_birth.hpp"
 #include "mpp_device.hpp"
 #include "mpp_launch.hpp"
 #include "mpp_scratch.hpp"
@@ -41,19 +42,6 @@ __global__ __launch_bounds__(64) void k_birth_prepass(const DevParams *P, const 
 #define BIRTH_THREADS (BIRTH_BX * BIRTH_BY)
 static_assert(MPP_BIRTH_CHUNK >= BIRTH_THREADS, "a scan of one slot per lane must fit the chunk");
 
-// argmax class of a pixel's 32 mark probabilities: first maximum, a NaN wins (np.argmax; the rule of k_mark_classes)
-__device__ __forceinline__ int birth_argmax(const MPP_GLOBAL float *row) {
-  int am = 0;
-  float best = row[0];
-  if (!isnan(best))
-    for (int j = 1; j < MPP_NCLASS; ++j) {
-      const float v = row[j];
-      if (isnan(v)) { am = j; break; }
-      if (v > best) { best = v; am = j; }
-    }
-  return am;
-}
-
 __global__ __launch_bounds__(BIRTH_THREADS) void k_birth_map(const DevParams *P, const TileRef *tiles, int cap, BirthCache bc,
                                                              double *dE, double *marks) {
   // one chunk of the points within reach of the block: rectangle and cached record, in slot order
@@ -78,10 +66,7 @@ __global__ __launch_bounds__(BIRTH_THREADS) void k_birth_map(const DevParams *P,
   double lin_u = 0.0;
   int gate_u = 1;
   if (live) {
-    const size_t pix = ((size_t)x * W + y) * MPP_NCLASS;
-    u.s = P->maps.edges[0][birth_argmax(t.m[0] + pix)];
-    u.r = P->maps.edges[1][birth_argmax(t.m[1] + pix)];
-    u.a = P->maps.edges[2][birth_argmax(t.m[2] + pix)];
+    birth_candidate_marks(P, t, x, y, W, &u.s, &u.r, &u.a);
     gu = make_geo(u);
     unit_part<false>(P, t, &P->maps.edges[0][0], u, gu, &lin_u, &gate_u, nullptr);
   }

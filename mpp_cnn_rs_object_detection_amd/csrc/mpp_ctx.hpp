@@ -129,6 +129,8 @@ struct mpp_ctx : TileMem {
   DevWs energy_ws;                   // mpp_total_energy_all: every chain's point energies, their sums, the chains' grids
   DevWs birth_ws;                    // mpp_birth_energy_map: the per-point cache, the chains' grids, the summary's parts
   int birth_grid = 0;                // ... its last pre-pass built candidate grids
+  DevWs minsel_ws;                   // mpp_select_minima / mpp_birth_complete: the candidate list and its tables
+  DevWs complete_ws;                 // mpp_birth_complete: every chain's map, the appended values, the reports
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
   RescaleWs rescale;                 // workspace of mpp_rescale (mpp_rescale.hip)

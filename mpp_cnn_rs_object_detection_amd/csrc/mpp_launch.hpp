@@ -51,6 +51,22 @@ struct BirthCache { double *lin, *r0, *r1, *e; int32_t *gate; };
 #define MPP_BIRTH_PARTS 256                        // partial summaries per chain (one per workgroup of the first pass)
 struct BirthPart { double v; long long idx, n_neg, n_nan; };   // smallest non-NaN value and its row-major index (-1: none)
 
+// One selection of local minima over the maps of n_chains chains (mpp_birth_complete.hip), all device.  The caller sets the
+// first block; mpp_minsel_plan places the arrays of the second in a workspace of mpp_minsel_bytes bytes.
+struct MinSel {
+  const double *dE; size_t chain_stride;           // chain t's map starts at dE + t * chain_stride, rows ld apart
+  int H, W, ld, n_chains;
+  double below, d2;                                // candidates: dE < below; within reach: (double)(dx*dx + dy*dy) <= d2
+  int reach;                                       // no pixel further than this in a row or a column is within reach
+  const mpp_complete_report *rep;                  // nullptr, or [n_chains]: a chain whose status is >= 0 has no candidates
+  int nb_fill, nb_res;                             // blocks per chain of the compaction and of the resolve
+  double *val; int32_t *idx;                       // the candidates in row-major order, [n_chains][H*W]
+  int32_t *rows;                                   // [n_chains][H+1]: where a row's candidates start in the list
+  int32_t *cblk, *kblk;                            // per block: candidates / kept candidates in front of it
+  int32_t *n_cand, *n_kept;                        // [n_chains]
+  uint8_t *keep;                                   // [n_chains][H*W], by place in the list
+};
+
 // flags of mpp_launch_deep
 #define MPP_DEEP_SKIP_SAME 1                       // option deep_skip_same: steps that re-write their target unchanged are not evaluated
 
@@ -114,6 +130,18 @@ void mpp_launch_birth_map(hipStream_t st, const DevParams *P, const TileRef *til
                           BirthCache bc, double *dE, double *marks);
 void mpp_launch_birth_summary(hipStream_t st, int n_chains, int H, int W, const double *dE, BirthPart *part,
                               mpp_birth_summary *out);
+// the selection of local minima and the greedy completion (mpp_birth_complete.hip).  mpp_launch_minsel: from the maps to
+// n_cand, n_kept, keep and kblk; _emit: the kept pixels and values of chain t to xy / values + t * out_cap, out_cap >= every
+// n_kept.  The completion: rep [n_chains] device; _round appends an open chain's kept candidates behind its configuration
+// when they fit cap (their values to gain_val [n_chains][cap]) and books the round; _summary copies the summaries in.
+size_t mpp_minsel_bytes(int n_chains, int H, int W);
+void mpp_minsel_plan(MinSel *s, void *ws);
+void mpp_launch_minsel(hipStream_t st, const MinSel &s);
+void mpp_launch_minsel_emit(hipStream_t st, const MinSel &s, int out_cap, int32_t *xy, double *values);
+void mpp_launch_complete_init(hipStream_t st, int n_chains, mpp_complete_report *rep);
+void mpp_launch_complete_round(hipStream_t st, const MinSel &s, const DevParams *P, const TileRef *tiles, int cap,
+                               double *gain_val, int max_rounds, mpp_complete_report *rep);
+void mpp_launch_complete_summary(hipStream_t st, int n_chains, const mpp_birth_summary *sum, mpp_complete_report *rep);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);

@@ -7,6 +7,8 @@ device), and the detections are mapped back to the pixels of the file.  Per imag
 ``<stem>_results.pkl`` (the keys of ``infer``'s pickle, in the pixels the model saw, plus ``scale`` and ``source_shape``) and,
 with ``figures``, ``<stem>_detection.png`` drawn on the picture the model saw.  With ``inference.birth_map`` of the model's
 config (``--birth-map``) also ``<stem>_birth_energy.png`` and the key ``birth_summary`` of the pickle (``MPPModel.birth_map``).
+With ``inference.birth_complete`` (``--birth-complete``) the detections are completed from the birth-energy map first
+(``MPPModel.complete``): every file shows the completed list and the pickle has the key ``birth_complete``.
 """
 from __future__ import annotations
 
@@ -71,6 +73,7 @@ class DetectResult:
     scale: float
     source_shape: Tuple[int, int]
     birth: Any = None                 # ``inference.birth_map``: (dE [h,w] float64 device tensor, summary dict) of ``MPPModel.birth_map``
+    complete: Any = None              # ``inference.birth_complete``: the summary dict of ``MPPModel.complete`` (``detections`` are completed)
 
     def polygons(self) -> np.ndarray:
         """[n,4,2] corners in the pixels the model saw (``rect_to_poly`` of (a, b, angle), as ``infer`` stores them)"""
@@ -111,10 +114,10 @@ def detect_image(model, rgb_uint8: np.ndarray, gsd: Optional[float] = None, mode
     data = ImageWMaps(name=name, shape=tuple(image.shape[:2]), image=image, detection_map=None, param_dist_maps=None,
                       mappings=default_mappings(),
                       param_names=Rectangle.PARAMETERS, labels=None, gt_config=[])
-    model.last_birth = None
+    model.last_birth = model.last_complete = None
     detections, scores = model.infer_image(data, seed=seed)
     return DetectResult(detections=detections, scores=np.asarray(scores, dtype=np.float64), image=image, scale=scale,
-                        source_shape=(H, W), birth=getattr(model, "last_birth", None))
+                        source_shape=(H, W), birth=getattr(model, "last_birth", None), complete=getattr(model, "last_complete", None))
 
 
 def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Optional[float] = None, figures: bool = False,
@@ -134,6 +137,8 @@ def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Opti
               "scale": result.scale, "source_shape": tuple(result.source_shape)}
     if result.birth is not None:
         record["birth_summary"] = result.birth[1]
+    if result.complete is not None:
+        record["birth_complete"] = result.complete
     with open(os.path.join(out_dir, f"{stem}_results.pkl"), "wb") as f:
         pickle.dump(record, f)
     if figures:

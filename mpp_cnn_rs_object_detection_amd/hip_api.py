@@ -88,6 +88,11 @@ STEPOUT_DTYPE = np.dtype([("dE", "<f8"), ("fwd", "<f8"), ("bwd", "<f8"), ("log_a
 #: mpp_birth_summary, one per chain, and MPP_BIRTH_CHUNK: the points a block of the birth-energy map stages per pass
 BIRTH_SUMMARY_DTYPE = np.dtype([("min_dE", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_negative", "<i8"), ("n_nan", "<i8")], align=True)
 BIRTH_CHUNK = 256
+#: mpp_complete_report, one per chain (``MppContext.birth_complete``); status: 0 converged, 1 round limit, 2 capacity
+COMPLETE_REPORT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_added", "<i4"), ("n_after", "<i4"), ("gain", "<f8"),
+                                  ("min_dE", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_negative", "<i8"), ("n_nan", "<i8")], align=True)
+COMPLETE_CONVERGED, COMPLETE_ROUND_LIMIT, COMPLETE_CAPACITY = 0, 1, 2
+E_OUTPUT_FULL = -13     # mpp_select_minima: more minima kept than the output holds
 
 
 _vp, _i32, _i64, _dbl = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -115,6 +120,8 @@ PROTOTYPES = {
     "mpp_delta_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "mpp_papangelou": (_i32, [_vp, _i32, _vp]),
     "mpp_birth_energy_map": (_i32, [_vp, _vp, _vp, _vp]),
+    "mpp_select_minima": (_i32, [_vp, _i32, _i32, _i32, _vp, _dbl, _dbl, _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mpp_birth_complete": (_i32, [_vp, _i32, _dbl, _vp]),
     "mpp_conv3x3_c32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpp_conv3x3_stem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mpp_merge_score": (_i32, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -512,6 +519,41 @@ class MppContext:
         s = np.zeros(T, BIRTH_SUMMARY_DTYPE) if summary else None
         self._check(self._L.mpp_birth_energy_map(self._h, _ptr(out), _ptr(marks), _ptr(s)))
         return out, marks, s
+
+    def select_minima(self, dE, below: float, distance: float):
+        """``mpp_select_minima``: the local minima below ``below`` of a float64 CUDA tensor [H,W] on the ctx's GPU (a view
+        with unit column stride will do) -- the candidates ``dE < below`` that no other candidate within ``distance`` beats
+        on the key (value, row-major index).  Returns ``(xy, values, n_candidates)``: xy [k,2] int32 (row, col) and values
+        [k] float64 tensors on the device, in ascending row-major order."""
+        import torch
+        if not (_is_torch(dE) and dE.is_cuda and dE.device.index == self.device and dE.dtype == torch.float64 and dE.dim() == 2
+                and dE.shape[0] >= 1 and dE.shape[1] >= 1 and dE.stride(1) == 1 and (dE.shape[0] == 1 or dE.stride(0) >= dE.shape[1])):
+            raise ValueError(f"select_minima: dE must be a float64 [H,W] tensor with unit column stride on GPU {self.device}")
+        H, W = int(dE.shape[0]), int(dE.shape[1])
+        ld = int(dE.stride(0)) if H > 1 else W
+        dev = torch.device("cuda", self.device)
+        torch.cuda.current_stream(dev).synchronize()
+        nc, nk = C.c_int64(), C.c_int64()
+        cap = 256
+        while True:
+            xy = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+            values = torch.empty((cap,), dtype=torch.float64, device=dev)
+            rc = self._L.mpp_select_minima(self._h, H, W, ld, _ptr(dE), float(below), float(distance), cap, _ptr(xy), _ptr(values),
+                                           C.byref(nc), C.byref(nk))
+            if rc != E_OUTPUT_FULL:
+                break
+            cap = int(nk.value)                      # (the call says how many it keeps: the second one fits)
+        self._check(rc)
+        return xy[:nk.value], values[:nk.value], int(nc.value)
+
+    def birth_complete(self, max_rounds: int = 16, min_gain: float = 0.0) -> np.ndarray:
+        """``mpp_birth_complete``: every chain of the context takes the births of its birth-energy map -- the local minima
+        below ``-min_gain``, no two within twice the model's interaction range -- round after round until none is left,
+        ``max_rounds`` rounds have added points, or a round does not fit ``point_capacity``.  The chains' configurations are
+        changed on the device.  Returns one record of ``COMPLETE_REPORT_DTYPE`` per chain."""
+        rep = np.zeros(max(self.get_option("n_chains"), 1), COMPLETE_REPORT_DTYPE)
+        self._check(self._L.mpp_birth_complete(self._h, int(max_rounds), float(min_gain), _ptr(rep)))
+        return rep[:self.get_option("n_chains")]
 
     # -- the chain -----------------------------------------------------------------------------
     def merge_score(self, distance: float):

@@ -156,6 +156,41 @@ def check_birth_map(config: Dict, world_size: int = 1) -> bool:
     return bool(on)
 
 
+def check_birth_complete(config: Dict, world_size: int = 1) -> Optional[Dict]:
+    """``inference.birth_complete`` of a config (default off): greedy completion of every image's merged detections from
+    its birth-energy map (``MPPModel.complete``).  ``true``, or ``{"max_rounds": .., "min_gain": ..}`` (either key may be
+    left out: 16 rounds, gain 0).  Returns the two parameters as a dict, or None when it is off.  Like the birth map it
+    runs on ONE context that holds the whole image, so ranks that share one image refuse it -- before any collective, every
+    rank alike."""
+    v = (config.get("inference") or {}).get("birth_complete", False)
+    if isinstance(v, (bool, np.bool_)):
+        params = {} if v else None
+    elif isinstance(v, dict):
+        unknown = sorted(set(v) - {"max_rounds", "min_gain"})
+        if unknown:
+            raise ValueError(f"inference.birth_complete: unknown key(s) {unknown}; it takes max_rounds and min_gain")
+        params = dict(v)
+    else:
+        raise ValueError(f"inference.birth_complete must be true, false or a dict of max_rounds / min_gain, got {v!r}")
+    if params is None:
+        return None
+    r, g = params.get("max_rounds", 16), params.get("min_gain", 0.0)
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= 1024:
+        raise ValueError(f"inference.birth_complete.max_rounds must be an integer in 1..1024, got {r!r}")
+    if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not np.isfinite(g) or g < 0:
+        raise ValueError(f"inference.birth_complete.min_gain must be a finite number >= 0, got {g!r}")
+    if world_size > 1:
+        raise ValueError(f"inference.birth_complete needs an image held by one GPU; {world_size} ranks share this one "
+                         f"(set inference.birth_complete to false)")
+    return {"max_rounds": int(r), "min_gain": float(g)}
+
+
+def format_complete_summary(summary: Dict) -> str:
+    """the log line of one image's completion"""
+    return (f"birth completion: +{summary['n_added']} object(s) in {summary['rounds']} round(s), energy -{abs(summary['gain']):.2f}, "
+            f"{summary['n_negative']} pixel(s) still below 0")
+
+
 def format_birth_summary(summary: Dict) -> str:
     """the log line of one image's birth map"""
     return (f"birth map: min dE {summary['min_dE']:.2f} at ({summary['argmin'][0]}, {summary['argmin'][1]}), "
@@ -338,13 +373,35 @@ class MPPModel:
         ``inference.birth_map``: the birth-energy map of the image under the returned detections is left in
         ``self.last_birth`` = (dE [H,W] float64 device tensor, summary dict), see ``birth_map``."""
         check_restarts(self.config, world_size)               # (before any collective: every rank raises alike)
-        if not check_birth_map(self.config, world_size):
+        birth_map, complete = check_birth_map(self.config, world_size), check_birth_complete(self.config, world_size)
+        if not birth_map and complete is None:
             return self._infer_image(image_data, rank, world_size, region_data, seed)
         if region_data is None:
             region_data = self.region_maps(image_data, rank, world_size)
         merged, scores = self._infer_image(image_data, rank, world_size, region_data, seed)
-        self.last_birth = self.birth_map(region_data, merged)
+        if complete is not None:
+            merged, scores, self.last_complete = self.complete(region_data, merged)
+        if birth_map:
+            self.last_birth = self.birth_map(region_data, merged)
         return merged, scores
+
+    def complete(self, region_data: ImageWMaps, merged):
+        """Greedy completion of one image's detections (``inference.birth_complete``, ``EPointsSet.birth_complete``): one
+        context with the image as its single tile and ``merged`` as its configuration, exactly as ``birth_map`` builds it,
+        with room for the births.  Returns (completed, scores, summary): the ``EPointsSet`` of ``merged`` followed by the
+        added ``Rectangle``s in slot order, the final Papangelou scores of EVERY point of it (``papangelou_all``, the
+        scoring of ``merge_patches``' second pass: a detection next to a new one is rescored), summary = {"n_added",
+        "rounds", "gain", "status", "min_dE", "argmin", "n_negative", "n_nan"}; logs one line."""
+        pts = list(merged)
+        p = check_birth_complete(self.config) or {"max_rounds": 16, "min_gain": 0.0}
+        unit, pair = self.energy_setup.make_energies(region_data)
+        agg = EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
+                         device=self.device, point_capacity=max(1024, 2 * len(pts) + 64))
+        r = agg.birth_complete(energy_combinator=self.energy_model, max_rounds=p["max_rounds"], min_gain=p["min_gain"])
+        scores = agg.papangelou_all(energy_combinator=self.energy_model) if len(agg) else np.zeros(0)
+        summary = {k: r[k] for k in ("n_added", "rounds", "gain", "status", "min_dE", "argmin", "n_negative", "n_nan")}
+        logging.info(format_complete_summary(summary))
+        return agg, scores, summary
 
     def birth_map(self, region_data: ImageWMaps, merged):
         """The birth-energy map of one image (``EPointsSet.birth_energy_map``): one context with the image as its single
@@ -659,10 +716,12 @@ class MPPModel:
     #: one GPU runs chains at a time; every other image of a dataset belongs to one rank (``infer``)
     TILE_SHARD_MIN = 2048
 
-    def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None) -> dict:
+    def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None,
+                       complete_summary=None) -> dict:
         """Write ``NNNN_results.pkl`` of one image (mpp_model.py:333-366) and return what the two DOTA translators need
         of it (plain arrays: the records of all ranks travel to rank 0 in one gather).  ``birth_summary``
-        (``inference.birth_map``): one more key of the pickle."""
+        (``inference.birth_map``) and ``complete_summary`` (``inference.birth_complete``, key ``birth_complete``): one more
+        key of the pickle each."""
         pts = list(merged)
         pred_params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
         pred_centers = np.array([[p.x, p.y] for p in pts]).reshape(-1, 2)
@@ -681,6 +740,8 @@ class MPPModel:
                   "detection_score": list(map(float, scores)), "detection_params": pred_params}
         if birth_summary is not None:
             record["birth_summary"] = birth_summary
+        if complete_summary is not None:
+            record["birth_complete"] = complete_summary
         with open(out_file, "wb") as f:
             pickle.dump(record, f)
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
@@ -715,7 +776,9 @@ class MPPModel:
         pictures the reference writes per image, ``NNNN_detection.png`` and ``NNNN_gt.png``, beside ``NNNN_results.pkl``, by the
         rank that writes the pickle (``_write_figures``; without the score text).  Off, nothing of
         it runs.  ``inference.birth_map`` (off): per image the birth-energy map under its merged detections (``birth_map``):
-        ``NNNN_birth_energy.png``, the key ``birth_summary`` of the pickle and one log line.
+        ``NNNN_birth_energy.png``, the key ``birth_summary`` of the pickle and one log line.  ``inference.birth_complete``
+        (off): the merged detections are completed from that map first (``complete``): the pickle, the CSV, the figures and the
+        birth map are those of the completed list, the pickle has the key ``birth_complete``, and one log line says what was added.
 
         Several ranks (one per GPU): the DATASET is sharded by image -- the reference's own loop is serial over images
         (``mpp_model.py:220``) with a process pool inside each; here rank r takes the r-th block of the images and runs them
@@ -727,7 +790,7 @@ class MPPModel:
         if figures is None:
             figures = bool(self.config["inference"].get("figures", False))
         # (an image shared by all ranks refuses the option in ``infer_image``, before its first collective)
-        birth_map = check_birth_map(self.config)
+        birth_map, complete = check_birth_map(self.config), check_birth_complete(self.config)
         dataset = self.config["dataset"]["dataset"]
         results_dir = get_inference_path(os.path.split(self.save_path)[1], dataset, subset)
         os.makedirs(results_dir, exist_ok=True)
@@ -787,12 +850,15 @@ class MPPModel:
 
         try:
             for k, image_data, region_data, merged, scores in inferred():
-                birth = None
+                birth = done = None
+                if complete is not None:            # (before the map and the figures: they show the completed list)
+                    merged, scores, done = self.complete(region_data, merged)
                 if birth_map:                       # (the image's own maps and its merged detections: one context, one tile)
                     dE, birth = self.birth_map(region_data, merged)
                     self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
                     del dE
-                records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth))
+                records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth,
+                                                   complete_summary=done))
                 if figures:
                     self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all

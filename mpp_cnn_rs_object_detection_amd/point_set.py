@@ -222,6 +222,59 @@ class EPointsSet:
         dE, marks, s = self._ctx.birth_energy_map(marks=return_marks)
         return (dE[0], marks[0], s[0]) if return_marks else (dE[0], s[0])
 
+    def _grow_context(self):
+        """a context of its own with twice the point capacity and the same maps (the capacity is fixed once the maps are set)"""
+        from .hip_api import MppContext as Ctx
+        old = self._ctx
+        cap = old.get_option("point_capacity")
+        if cap >= 65535:
+            raise MemoryError("point capacity of the context cannot grow beyond 65535")
+        new = Ctx(old.device, point_capacity=min(65535, 2 * cap))
+        new.set_option("scratch_grid_min_points", old.get_option("scratch_grid_min_points"))
+        H, W = self.support_shape
+        if self.image_data is not None:
+            new.set_maps(self.image_data.detection_map, self.image_data.param_dist_maps)
+        else:
+            new.set_maps(np.zeros((H, W), np.float32), [np.zeros((H, W, 32), np.float32)] * 3)
+        pic = E.classic_image(self.ue_constructors)
+        if pic is not None:
+            new.set_image(pic)
+        if self._owns_ctx:
+            old.close()
+        self._ctx, self._owns_ctx, self._dirty = new, True, True
+
+    def birth_complete(self, energy_combinator=None, max_rounds: int = 16, min_gain: float = 0.0) -> dict:
+        """Greedy completion (``mpp_birth_complete``): the set takes the births of its birth-energy map -- per round the
+        local minima below ``-min_gain``, no two within twice the interaction range -- until none is left or ``max_rounds``
+        rounds have added points.  The new ``Rectangle``s are appended to the set in slot order.  A round that does not fit
+        the context's point capacity makes the set move to a context of twice the capacity and go on (the gain is then the
+        sum of the parts' gains).  Returns {"status" (0 converged, 1 round limit), "rounds", "n_added", "n_after", "gain",
+        "min_dE", "argmin": (x, y), "n_negative", "n_nan"}, the last four of the completed set's map."""
+        from .hip_api import COMPLETE_CAPACITY
+        out = {"status": 0, "rounds": 0, "n_added": 0, "n_after": len(self._points), "gain": 0.0}
+        left, first = int(max_rounds), True
+        while True:
+            self._use(energy_combinator)
+            rep = self._ctx.birth_complete(left, min_gain)[0]
+            k = int(rep["n_added"])
+            if k:
+                xy, marks = self._ctx.get_points(0)
+                assert len(xy) == len(self._points) + k
+                for (x, y), m in zip(xy[-k:], marks[-k:]):
+                    u = Rectangle(int(x), int(y), size=float(m[0]), ratio=float(m[1]), angle=float(m[2]))
+                    self._index[u] = len(self._points)
+                    self._points.append(u)
+            out["rounds"] += int(rep["rounds"])
+            out["n_added"] += k
+            out["gain"] = float(rep["gain"]) if first else out["gain"] + float(rep["gain"])
+            left, first = left - int(rep["rounds"]), False
+            if int(rep["status"]) != COMPLETE_CAPACITY:
+                break
+            self._grow_context()
+        out.update(status=int(rep["status"]), n_after=int(rep["n_after"]), min_dE=float(rep["min_dE"]),
+                   argmin=(int(rep["x"]), int(rep["y"])), n_negative=int(rep["n_negative"]), n_nan=int(rep["n_nan"]))
+        return out
+
     # -- mutation ------------------------------------------------------------------------------------
     def apply_perturbation(self, p: Perturbation, inplace: bool = False) -> "EPointsSet":
         """Reference ``energy_point_set.py:118-154``."""
