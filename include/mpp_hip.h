@@ -311,8 +311,49 @@ int mpp_run(mpp_ctx *ctx, int64_t n_steps, uint64_t seed, uint32_t chain0, int t
  * ctx; seeds == NULL or chains == NULL: back to mpp_run's arguments.  Reset by mpp_set_maps. */
 int mpp_set_chain_keys(mpp_ctx *ctx, int n, const uint64_t *seeds, const uint32_t *chains);
 int mpp_step_index(mpp_ctx *ctx, int tile, int64_t *step);
-/* time of the last mpp_run / mpp_replay kernel in ms (HIP events on the ctx's stream) */
+/* time of the last mpp_run / mpp_replay kernel in ms (HIP events on the ctx's stream); after mpp_run_tempered the sum over
+ * its segments */
 int mpp_last_kernel_ms(mpp_ctx *ctx, double *ms);
+
+/* Parallel tempering (replica exchange; csrc/mpp_tempering.hip) ------------- */
+/* Every chain anneals by its own triple (current T, alpha, T_target) in device memory.  sched: HOST [n_chains][3].
+ * mpp_get_schedules reads the triples as the last launch left them (the kernels write the current temperature back);
+ * mpp_set_schedules replaces them and touches nothing else (no step counter, no ladder): -1 if a triple has T < T_target or
+ * an entry that is not finite, and then nothing is written.  mpp_set_schedule gives every chain the same triple, resets the
+ * step counters as before, and clears any ladder. */
+int mpp_get_schedules(mpp_ctx *ctx, double *sched);
+int mpp_set_schedules(mpp_ctx *ctx, const double *sched);
+/* The temperature ladder over the "replicas" R >= 2 chains of every tile; call it after mpp_set_schedule(T0, alpha, T_target).
+ * Chain r * n + i (n tiles) is replica r of tile i and gets (T0 * f_r, alpha, T_target * f_r) with f_0 = 1.0 and
+ * f_r = f_{r-1} * ratio, multiplied one after another in float64; rung[r * n + i] = r; the exchange counters (the options
+ * below) are zeroed.  A rung is a place on the ladder: an accepted exchange swaps the schedule triples and the rungs of two
+ * chains, so the chain at rung 0 of a tile is the one that currently follows the coldest schedule.
+ * -1 with a message: no maps, R < 2, a ratio < 1 or not finite.  Cleared by mpp_set_schedule and mpp_set_maps. */
+int mpp_set_ladder(mpp_ctx *ctx, double ratio);
+/* One attempted exchange: at absolute step `step`, tile `tile`, between rung k (chain_a, energy Ea, current temperature Ta)
+ * and rung k + 1 (chain_b, Eb, Tb) -- chain indices of the ctx, all values as read BEFORE the swap; u the uniform draw. */
+typedef struct { int64_t step; int32_t tile, k, chain_a, chain_b, accepted, _pad; double Ea, Eb, Ta, Tb, u; } mpp_exchange_record;
+/* mpp_run(ctx, n_steps, seed, chain0, -1, NULL, NULL) with an exchange whenever the chains reach an absolute step count
+ * s > 0 with s % every == 0 (s as mpp_step_index reports it: cutting a run into calls changes neither the chains nor the
+ * log).  The exchange at s, e = s / every, entirely on the ctx's stream -- no energy, temperature or decision reaches the host:
+ *   1. every chain's energy, by the launches of mpp_total_energy_all (the same bits);
+ *   2. one kernel, one thread per (tile i, pair (k, k + 1)), k + 1 < R: for R = 2 the only pair at every exchange, for R > 2 the
+ *      pairs with k % 2 == e % 2.  a / b: the chains of tile i at rungs k / k + 1.
+ *        d = (1.0 / Ta - 1.0 / Tb) * (Ea - Eb)                                     (float64)
+ *        u = u53(w[0], w[1]), w = Philox4x32-10(ctr = (lo32(s), hi32(s), 0x80000000 | k, chain id), key = seed), chain id and
+ *            seed those of replica 0 of tile i: its mpp_set_chain_keys entry when keys are in force, else (chain0 + i, seed).
+ *            The chains' own draws use blocks 0..2 and the split / merge ones; the high bit keeps this draw apart;
+ *        accept iff Ta > 0, Tb > 0, Ea and Eb finite, and (d >= 0 or u < exp(d)).
+ *      On accept the two schedule triples and the two rungs are swapped; points, keys, intensity and step stay.
+ * The log (HOST, log_cap records, may be NULL) receives the call's records ordered by (exchange, tile, pair); records past
+ * log_cap are dropped and still counted in *n_logged_or_null.  mpp_last_kernel_ms: the sum over the segments.
+ * -1 with a message: no ladder; every < 1; the chains of the ctx are not all at the same step.  A sticky chain error ends the
+ * call before the next exchange with that error's code.
+ * Read-only options, zeroed by mpp_set_ladder: "tempering_exchanges" (exchange steps so far), "tempering_attempts" and
+ * "tempering_accepted" (pairs), "tempering_ms" / "tempering_us" (time of the energy and exchange launches, from events,
+ * rounded to whole milliseconds / microseconds). */
+int mpp_run_tempered(mpp_ctx *ctx, int64_t n_steps, uint64_t seed, uint32_t chain0, int64_t every,
+                     mpp_exchange_record *log_or_null, int64_t log_cap, int64_t *n_logged_or_null);
 
 /* score-map epilogue of the two U-Nets (position_net/pos_net_model.py:186-200,338-346,
  * torch_div.py:8-43; shape_net/shape_net_model.py:139-141): all device pointers.

@@ -2,6 +2,7 @@
 """Command-line entry, same flags as the reference's ``main.py:11-109``:
 
     python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map] [--birth-complete]
+                   [--restarts R [--tempering [RATIO]]]
     python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map] [--birth-complete]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
@@ -38,6 +39,13 @@ def _restarts(text):
     return v
 
 
+def _ratio(text):
+    v = float(text)
+    if not (v >= 1.0) or v == float("inf"):
+        raise argparse.ArgumentTypeError(f"{text}: a finite ratio of at least 1")
+    return v
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-m", "--model", help="model to use")
@@ -58,6 +66,11 @@ def build_parser():
     parser.add_argument("--restarts", type=_restarts, default=None,
                         help="(-m mpp, infer / infereval) independent chains per tile, the lowest-energy one is kept; "
                              "overrides inference.restarts of the config (default 1)")
+    parser.add_argument("--tempering", type=_ratio, nargs="?", const=True, default=None, metavar="RATIO",
+                        help="(-m mpp, infer / infereval / detect) parallel tempering: the restarts of a tile anneal on a ladder of "
+                             "temperatures, RATIO apart from rung to rung (default: the sampler's), and neighbouring rungs "
+                             "exchange their schedules at intervals; needs --restarts or inference.restarts of at least 2; same "
+                             "as inference.tempering in the config (whose 'every' it keeps); off by default")
     parser.add_argument("--figures", action="store_true",
                         help="(-m mpp, infer / infereval / detect) write the result pictures composed on the GPU: NNNN_detection.png, "
                              "NNNN_gt.png (and NNNN_detection_map.png) beside NNNN_results.pkl; same as inference.figures in the config")
@@ -87,6 +100,18 @@ def apply_birth_complete(args, config):
         inference = config.setdefault("inference", {})
         if not isinstance(inference.get("birth_complete"), dict):
             inference["birth_complete"] = True
+    return config
+
+
+def apply_tempering(args, config):
+    """--tempering turns inference.tempering on; --tempering RATIO sets its ratio; an interval the config gives stays"""
+    if args.tempering is not None and args.procedure in ("infer", "infereval", "detect"):
+        inference = config.setdefault("inference", {})
+        if args.tempering is not True:
+            kept = inference["tempering"] if isinstance(inference.get("tempering"), dict) else {}
+            inference["tempering"] = dict(kept, ratio=args.tempering)
+        elif not isinstance(inference.get("tempering"), dict):
+            inference["tempering"] = True
     return config
 
 
@@ -124,6 +149,7 @@ def main():
         if args.birth_map:
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
+        apply_tempering(args, config)
         model = MPPModel(config, phase="val", load=True, device=local_rank,
                          nets=load_nets(config, local_rank, args.unet_max_pixels), spec_waves=args.spec_waves)
         detect.detect_files(model, args.images, args.out, gsd=args.gsd, model_gsd=args.model_gsd, min_score=args.min_score,
@@ -140,6 +166,7 @@ def main():
         if args.birth_map and args.procedure in ("infer", "infereval"):
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
+        apply_tempering(args, config)
         nets = None
         if args.unet:
             nets = load_nets(config, local_rank, args.unet_max_pixels)

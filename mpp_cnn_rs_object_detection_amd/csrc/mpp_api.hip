@@ -24,6 +24,7 @@ extern "C" int mpp_create(int device_id, mpp_ctx **out) {
   c->hp.hot_past = 1;
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&c->own_stream) != hipSuccess ||
       hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+      hipEventCreate(&c->ev2) != hipSuccess || hipEventCreate(&c->ev3) != hipSuccess ||
       c->dp.alloc(1) != hipSuccess) {
     delete c;
     return -2;
@@ -55,6 +56,8 @@ extern "C" int mpp_destroy(mpp_ctx *c) {
   mpp_rescale_ws_free(&c->rescale);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
+  if (c->ev2) (void)hipEventDestroy(c->ev2);
+  if (c->ev3) (void)hipEventDestroy(c->ev3);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;                                      // (the workspaces and the parameter block go with their owners)
   return 0;
@@ -191,6 +194,19 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "hot_past_births")) return c->hp.hot_past;
   if (!strcmp(name, "window_rows")) return c->window_rows;
   if (!strcmp(name, "deep_skip_same")) return c->deep_skip_same;
+  // parallel tempering since the last mpp_set_ladder: exchange steps, attempted and accepted pairs, time of their launches
+  if (!strcmp(name, "tempering_exchanges")) return c->x_exchanges;
+  if (!strcmp(name, "tempering_attempts")) return c->x_attempts;
+  if (!strcmp(name, "tempering_accepted")) {
+    if (!c->ladder || !c->x_acc.p) return 0;
+    std::vector<long long> acc((size_t)c->n_maps * (c->replicas - 1));
+    if (hipMemcpy(acc.data(), c->x_acc.p, acc.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    long long sum = 0;
+    for (long long v : acc) sum += v;
+    return sum;
+  }
+  if (!strcmp(name, "tempering_ms")) return (int64_t)llround(c->x_ms);
+  if (!strcmp(name, "tempering_us")) return (int64_t)llround(c->x_ms * 1000.0);
   if (!strcmp(name, "detect_launches")) return c->detect.launches;
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now
@@ -317,6 +333,7 @@ extern "C" int mpp_set_maps(mpp_ctx *c, int n_tiles, int H, int W, const float *
   free_tiles(c);
   c->n_maps = n_tiles; c->n_tiles = n_tiles * c->replicas; c->H = H; c->W = W;
   c->key_seed.clear(); c->key_chain.clear();
+  c->ladder = false;                               // (its rungs went with the tiles' arrays)
   const size_t hw = (size_t)H * W, M = (size_t)n_tiles, T = (size_t)c->n_tiles;
   const float *src[4] = {det, m0, m1, m2};
   float **dst[4] = {&c->det, &c->m[0], &c->m[1], &c->m[2]};
@@ -558,6 +575,7 @@ extern "C" int mpp_set_schedule(mpp_ctx *c, double T0, double alpha, double T_ta
   if (!c) return -1;
   if (!(T0 >= T_target)) return fail(c, -1, "t0 must be >= t_target");          // rjmcmc.py:71
   c->sched[0] = T0; c->sched[1] = alpha; c->sched[2] = T_target;
+  c->ladder = false;                               // every chain on the same schedule again: mpp_set_ladder sets a new one
   if (c->have_maps) {
     std::vector<double> sched((size_t)c->n_tiles * 3);
     for (int t = 0; t < c->n_tiles; ++t) { sched[3 * t] = T0; sched[3 * t + 1] = alpha; sched[3 * t + 2] = T_target; }

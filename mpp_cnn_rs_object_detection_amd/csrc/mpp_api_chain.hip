@@ -1,5 +1,7 @@
 // mpp_api_chain.hip -- the chains of the C ABI (mpp_run, mpp_replay): birth and remap tables, the birth pre-pass, and
 // run_chain, which routes every chain to the LDS or the device-memory kernel and grows the capacities until all are done.
+#include <cmath>
+
 #include "mpp_ctx.hpp"
 
 // More slots per tile: the five configuration arrays are re-allocated with the new stride and copied.
@@ -469,6 +471,132 @@ extern "C" int mpp_run(mpp_ctx *c, int64_t n_steps, uint64_t seed, uint32_t chai
   if (d_props && e == hipSuccess) e = hipMemcpy(props, d_props, (size_t)n_steps * sizeof(mpp_proposal), hipMemcpyDeviceToHost);
   HIPCHK(c, e);
   return rc;
+}
+
+// ---- parallel tempering (mpp_tempering.hip) -----------------------------------------------------
+extern "C" int mpp_get_schedules(mpp_ctx *c, double *sched) {
+  if (!c || !sched) return fail(c, -1, "bad get_schedules arguments");
+  if (!c->have_maps) return fail(c, -1, "mpp_set_maps has not been called");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(sched, c->T, (size_t)c->n_tiles * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int mpp_set_schedules(mpp_ctx *c, const double *sched) {
+  if (!c || !sched) return fail(c, -1, "bad set_schedules arguments");
+  if (!c->have_maps) return fail(c, -1, "mpp_set_maps has not been called");
+  for (int t = 0; t < c->n_tiles; ++t) {
+    const double *s = sched + 3 * (size_t)t;
+    if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !std::isfinite(s[2]))
+      return fail(c, -1, "set_schedules: chain %d has an entry that is not finite", t);
+    if (s[0] < s[2]) return fail(c, -1, "set_schedules: chain %d has T < T_target", t);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(c->T, sched, (size_t)c->n_tiles * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int mpp_set_ladder(mpp_ctx *c, double ratio) {
+  if (!c) return -1;
+  if (!c->have_maps) return fail(c, -1, "mpp_set_maps has not been called");
+  const int R = c->replicas, n = c->n_maps, T = c->n_tiles;
+  if (R < 2) return fail(c, -1, "set_ladder: a ladder needs replicas >= 2, the ctx holds %d", R);
+  if (!std::isfinite(ratio) || !(ratio >= 1.0)) return fail(c, -1, "set_ladder: ratio must be finite and >= 1");
+  std::vector<double> sched((size_t)T * 3);
+  std::vector<int32_t> rung(T);
+  double f = 1.0;
+  for (int r = 0; r < R; ++r) {
+    if (r > 0) f *= ratio;
+    if (!std::isfinite(c->sched[0] * f)) return fail(c, -1, "set_ladder: the temperature of rung %d is not finite", r);
+    for (int i = 0; i < n; ++i) {
+      double *s = sched.data() + 3 * ((size_t)r * n + i);
+      s[0] = c->sched[0] * f; s[1] = c->sched[1]; s[2] = c->sched[2] * f;
+      rung[(size_t)r * n + i] = r;
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->rung.p) HIPCHK(c, c->rung.alloc((size_t)T));
+  if (!c->x_acc.p) HIPCHK(c, c->x_acc.alloc((size_t)n * (R - 1)));
+  HIPCHK(c, hipMemcpyAsync(c->T, sched.data(), sched.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->rung, rung.data(), (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->x_acc, 0, (size_t)n * (R - 1) * sizeof(long long), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->ladder = true;
+  c->x_exchanges = c->x_attempts = 0; c->x_ms = 0.0;
+  return 0;
+}
+
+extern "C" int mpp_run_tempered(mpp_ctx *c, int64_t n_steps, uint64_t seed, uint32_t chain0, int64_t every,
+                                mpp_exchange_record *log, int64_t log_cap, int64_t *n_logged) {
+  if (!c) return -1;
+  if (n_logged) *n_logged = 0;
+  if (!c->have_maps) return fail(c, -1, "mpp_set_maps has not been called");
+  if (!c->ladder || !c->rung.p) return fail(c, -1, "run_tempered: no ladder is set (mpp_set_ladder)");
+  if (every < 1) return fail(c, -1, "run_tempered: every must be >= 1");
+  if (log && log_cap < 0) return fail(c, -1, "run_tempered: log_cap must be >= 0");
+  if (n_steps <= 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int T = c->n_tiles, R = c->replicas, n = c->n_maps;
+  std::vector<int64_t> step(T);
+  HIPCHK(c, hipMemcpyAsync(step.data(), c->step, (size_t)T * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int t = 1; t < T; ++t)
+    if (step[t] != step[0])
+      return fail(c, -1, "run_tempered: chain %d is at step %lld, chain 0 at %lld: an exchange needs all chains at the same step", t,
+                  (long long)step[t], (long long)step[0]);
+  const int64_t s0 = step[0], s1 = s0 + n_steps;
+  // pairs of exchange e (mpp_launch_exchange): the records of the call are numbered ahead, exchange by exchange
+  auto pairs = [R](int64_t e) { return (int64_t)((R - (R == 2 ? 0 : (int)(e & 1))) / 2); };
+  int64_t total = 0;
+  for (int64_t s = (s0 / every + 1) * every; s <= s1; s += every) total += (int64_t)n * pairs(s / every);
+  if (!log) log_cap = 0;
+  const int64_t kept = total < log_cap ? total : log_cap;
+  if (kept > 0 && c->x_log.reserve(c->stream, (size_t)kept * sizeof(mpp_exchange_record)) != hipSuccess)
+    return fail(c, -2, "no device memory for %lld exchange records", (long long)kept);
+  mpp_exchange_record *d_log = kept > 0 ? (mpp_exchange_record *)c->x_log.p : nullptr;
+  double ms_sum = 0.0;
+  int hbm = 0, pre = 0, que = 0, hot = 0;
+  bool timing = false;                         // ev2 / ev3 hold an exchange whose time has not been read
+  auto take_time = [&]() {                     // (after a wait for the stream)
+    float ms = 0.f;
+    if (timing && hipEventElapsedTime(&ms, c->ev2, c->ev3) == hipSuccess) c->x_ms += ms;
+    timing = false;
+  };
+  int64_t base = 0;
+  int rc = 0;
+  for (int64_t pos = s0; pos < s1;) {
+    const int64_t next = (pos / every + 1) * every, to = next < s1 ? next : s1;
+    rc = run_chain(c, T, 0, to - pos, seed, chain0, nullptr, -1, nullptr, nullptr);   // (it ends with the stream idle)
+    ms_sum += c->last_ms;
+    hbm = c->hbm_chains > hbm ? c->hbm_chains : hbm;
+    pre |= c->prepass_used; que |= c->prepass_queues_used; hot |= c->hot_table_used;
+    take_time();
+    if (rc) break;
+    pos = to;
+    if (pos % every) continue;
+    double *d_e = nullptr;
+    if ((rc = push_state(c))) break;
+    HIPCHK(c, hipEventRecord(c->ev2, c->stream));
+    if ((rc = chain_energy_launches(c, &d_e))) break;
+    mpp_launch_exchange(c->stream, c->d_tiles, n, R, c->T, c->rung, d_e, (long long)pos, (long long)(pos / every), seed, chain0,
+                        c->x_acc, d_log, (long long)base, (long long)kept);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev3, c->stream));
+    timing = true;
+    base += (int64_t)n * pairs(pos / every);
+    c->x_exchanges += 1; c->x_attempts += (int64_t)n * pairs(pos / every);
+  }
+  c->last_ms = ms_sum;
+  c->hbm_chains = hbm; c->prepass_used = pre; c->prepass_queues_used = que; c->hot_table_used = hot;
+  hipError_t e = hipSuccess;
+  if (rc == 0 && kept > 0) e = hipMemcpyAsync(log, d_log, (size_t)kept * sizeof(mpp_exchange_record), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  take_time();
+  if (rc) return rc;
+  HIPCHK(c, e); HIPCHK(c, e2);
+  if (n_logged) *n_logged = base;
+  return 0;
 }
 
 extern "C" int mpp_step_index(mpp_ctx *c, int tile, int64_t *step) {

@@ -71,28 +71,15 @@ extern "C" int mpp_total_energy(mpp_ctx *c, int tile, double *energy, double *ve
   return 0;
 }
 
-// mpp_total_energy of every chain of the context at once, from the written-back state: the point energies of all chains in
-// one launch (the kernel of mpp_total_energy, so the same bits), their sums in slot order on the device, one copy of
-// n_chains doubles and one synchronise.  The counts stay on the device: the grids are built for every chain whenever a
-// chain could reach scratch_grid_min_points, and each chain uses its own only from that many points on.
+// mpp_total_energy of every chain of the context at once: the launches of chain_energy_launches (mpp_ctx.hpp), one copy of
+// n_chains doubles and one synchronise.
 extern "C" int mpp_total_energy_all(mpp_ctx *c, double *energy) {
   if (!c || !energy) return fail(c, -1, "bad total_energy_all arguments");
   int rc = push_state(c);
   if (rc) return rc;
-  const int T = c->n_tiles, ncell = c->hp.nx * c->hp.ny;
-  if (T > 65535) return fail(c, -1, "total_energy_all: %d chains, at most 65535", T);
-  const bool grid = c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points;
-  const size_t TC = (size_t)T * c->cap;
-  const size_t n_dbl = TC + (size_t)T, n_int = grid ? (size_t)T * (2 * (size_t)ncell + 1) + TC : 0;
-  if (c->energy_ws.reserve(c->stream, n_dbl * sizeof(double) + n_int * sizeof(int32_t)) != hipSuccess)
-    return fail(c, -2, "no device memory for the energies of %d chains", T);
-  double *e_pts = (double *)c->energy_ws.p, *d_sum = e_pts + TC;
-  int32_t *gs = grid ? (int32_t *)(d_sum + T) : nullptr, *gc = grid ? gs + (size_t)T * (ncell + 1) : nullptr;
-  int32_t *gi = grid ? gc + (size_t)T * ncell : nullptr;
-  if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, gs, gc, gi);
-  mpp_launch_chain_energies(c->stream, c->dp, c->d_tiles, T, c->cap, e_pts, d_sum, gs, gi, ncell + 1, c->grid_min_points);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(energy, d_sum, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  double *d_sum = nullptr;
+  if ((rc = chain_energy_launches(c, &d_sum))) return rc;
+  hipError_t e = hipMemcpyAsync(energy, d_sum, (size_t)c->n_tiles * sizeof(double), hipMemcpyDeviceToHost, c->stream);
   hipError_t e2 = hipStreamSynchronize(c->stream);
   HIPCHK(c, e); HIPCHK(c, e2);
   return 0;

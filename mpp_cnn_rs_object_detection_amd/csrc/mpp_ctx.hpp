@@ -51,12 +51,15 @@ struct TileMem {
   DevBuf<long long> until;           // per tile: the absolute step the current mpp_run / mpp_replay call runs it to
   DevBuf<double> remap[3];           // tables of the remapped marks (chains only), see ensure_remap_tables
   DevBuf<TileRef> d_tiles;
+  DevBuf<int32_t> rung;              // parallel tempering (mpp_set_ladder): per chain, its place on its tile's temperature ladder
+  DevBuf<long long> x_acc;           // ... and per (tile, pair of neighbouring rungs) the accepted exchanges
 };
 
 struct mpp_ctx : TileMem {
   int device = 0;
   hipStream_t stream = nullptr, own_stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev2 = nullptr, ev3 = nullptr;     // around the energy and exchange launches of mpp_run_tempered
   std::string err;
   DevParams hp;
   DevBuf<DevParams> dp;
@@ -123,6 +126,12 @@ struct mpp_ctx : TileMem {
   std::vector<TileRef> h_tiles;
   double sched[3] = {1.0, 1.0, 0.0};
   double last_ms = 0.0;
+  // parallel tempering: a ladder is set (rung / x_acc exist); exchange steps and attempted pairs since then, the time of their
+  // launches; the device log of the call in hand
+  bool ladder = false;
+  int64_t x_exchanges = 0, x_attempts = 0;
+  double x_ms = 0.0;
+  DevWs x_log;
   // uniform grid over one tile's configuration for the from-scratch energies (built per call; see mpp_scratch.hip)
   DevWs g_cells, g_items;            // cell starts [ncell + 1] then cursors [ncell]; the points by cell [cap]
   int grid_min_points = 256;
@@ -154,6 +163,28 @@ static int fail(mpp_ctx *c, int code, const char *fmt, ...) {
 
 int push_state(mpp_ctx *c);             // (mpp_api.hip)
 int check_tile(mpp_ctx *c, int tile);
+
+// The launches of mpp_total_energy_all, after push_state: every chain's energy, from the written-back state, stays on the
+// device in *d_sum [n_chains] (workspace energy_ws).  The point energies of all chains in one launch (the kernel of
+// mpp_total_energy, so the same bits), their sums in slot order.  The counts stay on the device: the grids are built for every
+// chain whenever a chain could reach scratch_grid_min_points, and each chain uses its own only from that many points on.
+static int chain_energy_launches(mpp_ctx *c, double **d_sum) {
+  const int T = c->n_tiles, ncell = c->hp.nx * c->hp.ny;
+  if (T > 65535) return fail(c, -1, "total_energy_all: %d chains, at most 65535", T);
+  const bool grid = c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points;
+  const size_t TC = (size_t)T * c->cap;
+  const size_t n_dbl = TC + (size_t)T, n_int = grid ? (size_t)T * (2 * (size_t)ncell + 1) + TC : 0;
+  if (c->energy_ws.reserve(c->stream, n_dbl * sizeof(double) + n_int * sizeof(int32_t)) != hipSuccess)
+    return fail(c, -2, "no device memory for the energies of %d chains", T);
+  double *e_pts = (double *)c->energy_ws.p;
+  *d_sum = e_pts + TC;
+  int32_t *gs = grid ? (int32_t *)(*d_sum + T) : nullptr, *gc = grid ? gs + (size_t)T * (ncell + 1) : nullptr;
+  int32_t *gi = grid ? gc + (size_t)T * ncell : nullptr;
+  if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, gs, gc, gi);
+  mpp_launch_chain_energies(c->stream, c->dp, c->d_tiles, T, c->cap, e_pts, *d_sum, gs, gi, ncell + 1, c->grid_min_points);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
 
 static const char *chain_error_text(int e) {
   static const char *const text[] = {"a cell of the spatial hash holds more points than cell_capacity allows",

@@ -142,6 +142,12 @@ void mpp_launch_complete_init(hipStream_t st, int n_chains, mpp_complete_report 
 void mpp_launch_complete_round(hipStream_t st, const MinSel &s, const DevParams *P, const TileRef *tiles, int cap,
                                double *gain_val, int max_rounds, mpp_complete_report *rep);
 void mpp_launch_complete_summary(hipStream_t st, int n_chains, const mpp_birth_summary *sum, mpp_complete_report *rep);
+// the exchange of parallel tempering at absolute step s, exchange number e (mpp_tempering.hip), all device: tiles the ctx's
+// table (entry i: replica 0 of tile i, whose key the draw takes), sched [n_chains][3], rung [n_chains], energy [n_chains];
+// accepted [n_maps][R - 1] counts per (tile, pair); log nullptr or log_cap records, this exchange's from log_base on
+void mpp_launch_exchange(hipStream_t st, const TileRef *tiles, int n_maps, int R, double *sched, int32_t *rung, const double *energy,
+                         long long s, long long e, unsigned long long seed, unsigned int chain0, long long *accepted,
+                         mpp_exchange_record *log, long long log_base, long long log_cap);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);

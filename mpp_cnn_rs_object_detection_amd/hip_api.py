@@ -92,6 +92,12 @@ BIRTH_CHUNK = 256
 COMPLETE_REPORT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_added", "<i4"), ("n_after", "<i4"), ("gain", "<f8"),
                                   ("min_dE", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_negative", "<i8"), ("n_nan", "<i8")], align=True)
 COMPLETE_CONVERGED, COMPLETE_ROUND_LIMIT, COMPLETE_CAPACITY = 0, 1, 2
+#: mpp_exchange_record, one per attempted exchange of ``MppContext.run_tempered``: the values as read before the swap
+EXCHANGE_RECORD_DTYPE = np.dtype([("step", "<i8"), ("tile", "<i4"), ("k", "<i4"), ("chain_a", "<i4"), ("chain_b", "<i4"),
+                                  ("accepted", "<i4"), ("_pad", "<i4"), ("Ea", "<f8"), ("Eb", "<f8"), ("Ta", "<f8"),
+                                  ("Tb", "<f8"), ("u", "<f8")], align=True)
+#: steps between two exchanges unless told otherwise: a segment of a run gets its hot start only from 4096 steps on
+TEMPERING_EVERY = 4096
 E_OUTPUT_FULL = -13     # mpp_select_minima: more minima kept than the output holds
 
 
@@ -132,6 +138,10 @@ PROTOTYPES = {
     "mpp_set_chain_keys": (_i32, [_vp, _i32, _vp, _vp]),
     "mpp_step_index": (_i32, [_vp, _i32, C.POINTER(C.c_int64)]),
     "mpp_last_kernel_ms": (_i32, [_vp, C.POINTER(_dbl)]),
+    "mpp_get_schedules": (_i32, [_vp, _vp]),
+    "mpp_set_schedules": (_i32, [_vp, _vp]),
+    "mpp_set_ladder": (_i32, [_vp, _dbl]),
+    "mpp_run_tempered": (_i32, [_vp, _i64, C.c_uint64, C.c_uint32, _i64, _vp, _i64, C.POINTER(C.c_int64)]),
     "mpp_affine_relu": (_i32, [_vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp]),
     "mpp_posnet_epilogue_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _dbl, _dbl, _i32, _i32, _i32, _i32, _vp, _i32]),
     "mpp_shapenet_epilogue_win": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32]),
@@ -266,6 +276,7 @@ class MppContext:
         self.device = int(device)
         self._keep = []          # keeps borrowed device tensors / host arrays alive
         self.n_tiles = 0
+        self.exchange_records = 0       # records the last run_tempered made
         self.shape = (0, 0)
         self.n_terms = 0
         self.names: List[str] = []
@@ -582,6 +593,52 @@ class MppContext:
             return out, props
         self._check(self._L.mpp_run(self._h, int(n_steps), int(seed), int(chain0), -1, None, None))
         return None
+
+    # -- parallel tempering ---------------------------------------------------
+    def get_schedules(self) -> np.ndarray:
+        """Every chain's (current T, alpha, T_target) as the last launch left it, float64 ``[n_chains, 3]``"""
+        sched = np.zeros((max(self.get_option("n_chains"), 1), 3), np.float64)
+        self._check(self._L.mpp_get_schedules(self._h, _ptr(sched)))
+        return sched[:self.get_option("n_chains")]
+
+    def set_schedules(self, sched):
+        """Replace every chain's (current T, alpha, T_target); nothing else changes (``mpp_set_schedules``)."""
+        sched = np.ascontiguousarray(sched, dtype=np.float64)
+        if sched.shape != (self.get_option("n_chains"), 3):
+            raise ValueError(f"set_schedules: one (T, alpha, T_target) per chain of the context ({self.get_option('n_chains')})")
+        self._check(self._L.mpp_set_schedules(self._h, _ptr(sched)))
+
+    def set_ladder(self, ratio: float):
+        """The temperature ladder over the replicas of every tile, after ``set_schedule``: replica r anneals ``ratio ** r``
+        times hotter (``mpp_set_ladder``).  Zeroes the exchange counters."""
+        self._check(self._L.mpp_set_ladder(self._h, float(ratio)))
+
+    def run_tempered(self, n_steps: int, seed: int, chain0: int = 0, every: int = TEMPERING_EVERY, log: bool = True,
+                     log_cap: Optional[int] = None) -> Optional[np.ndarray]:
+        """``run`` with replica exchanges whenever the chains reach a multiple of ``every`` steps (``mpp_run_tempered``).
+        Returns the call's attempted exchanges as records of ``EXCHANGE_RECORD_DTYPE`` in (exchange, tile, pair) order --
+        at most ``log_cap`` of them (None: all) --, or None when ``log`` is False.  ``exchange_records`` holds the number
+        of records the call made, kept or not."""
+        n_logged = C.c_int64()
+        if not log:
+            self._check(self._L.mpp_run_tempered(self._h, int(n_steps), int(seed), int(chain0), int(every), None, 0,
+                                                 C.byref(n_logged)))
+            self.exchange_records = int(n_logged.value)
+            return None
+        if log_cap is None:                     # no more than one record per tile and pair of rungs at every boundary
+            R = max(self.get_option("replicas"), 1)
+            n = self.get_option("n_chains") // R
+            log_cap = n * max(R - 1, 0) * (int(n_steps) // max(int(every), 1) + 1)
+        rec = np.zeros(max(int(log_cap), 1), EXCHANGE_RECORD_DTYPE)
+        self._check(self._L.mpp_run_tempered(self._h, int(n_steps), int(seed), int(chain0), int(every), _ptr(rec), int(log_cap),
+                                             C.byref(n_logged)))
+        self.exchange_records = int(n_logged.value)
+        return rec[:min(self.exchange_records, int(log_cap))]
+
+    def tempering_stats(self) -> dict:
+        """Since the last ``set_ladder``: exchange steps, attempted and accepted pairs, ms of the energy and exchange launches"""
+        return {"exchanges": self.get_option("tempering_exchanges"), "attempts": self.get_option("tempering_attempts"),
+                "accepted": self.get_option("tempering_accepted"), "ms": self.get_option("tempering_us") / 1000.0}
 
     def set_chain_keys(self, seeds=None, chains=None):
         """Per-chain Philox key and chain id (``mpp_set_chain_keys``); ``None``: back to ``run``'s seed and chain0 + tile."""

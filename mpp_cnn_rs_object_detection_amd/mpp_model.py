@@ -36,7 +36,7 @@ from .hip_api import MppError
 from .point_set import EPointsSet
 from .dota_results import DOTAResultsTranslator
 from .paths import fetch_data_paths, get_inference_path, get_model_base_path
-from .sampler import TileBatchSampler, resolve_schedule
+from .sampler import TileBatchSampler, exchange_rates, resolve_schedule, resolve_tempering
 from .shapes import Rectangle, rect_to_poly, sra_to_wla
 
 TRAIN_MODES = ["manual", "grad_descent", "integral_criterion", "ordering_criterion"]
@@ -140,6 +140,46 @@ def check_restarts(config: Dict, world_size: int = 1) -> int:
         raise ValueError(f"inference.restarts = {r} needs an image sampled by one GPU; {world_size} ranks share this one "
                          f"(set inference.restarts to 1)")
     return int(r)
+
+
+def check_tempering(config: Dict, world_size: int = 1) -> Optional[Dict]:
+    """``inference.tempering`` of a config (default off): ``true`` or ``{"ratio": r, "every": K}`` -- the restarts of a tile
+    on a temperature ladder with exchanges (``TileBatchSampler``).  Returns None (off) or the mapping
+    with both keys.  It exchanges the replicas of a tile, so it refuses what ``inference.restarts`` refuses, and also one
+    restart."""
+    t = (config.get("inference") or {}).get("tempering", False)
+    restarts = check_restarts(config, world_size)
+    if t is None or t is False:
+        return None
+    if not (t is True or isinstance(t, dict)):
+        raise ValueError(f"inference.tempering must be true, false or a mapping with 'ratio' and / or 'every', got {t!r}")
+    if restarts < 2:
+        raise ValueError(f"inference.tempering exchanges the restarts of a tile: set inference.restarts to 2 or more "
+                         f"(it is {restarts})")
+    ratio, every = resolve_tempering(t, restarts)
+    return {"ratio": ratio, "every": every}
+
+
+def tempering_summary(sampler, first: int = 0, n: Optional[int] = None) -> Optional[Dict]:
+    """What a tempered launch did to the tiles ``first .. first + n`` of ``sampler`` (one image's; default: all): ratio,
+    every, the number of exchange steps, accepted / attempted per pair of rungs over those tiles, per tile the rung its
+    winning replica ended on, and the device time of the launch's energy and exchange kernels (the whole launch's)."""
+    if sampler is None or not getattr(sampler, "tempering", None):
+        return None
+    n = len(sampler.tiles) - first if n is None else n
+    log = sampler.exchange_log
+    log = log[(log["tile"] >= first) & (log["tile"] < first + n)]
+    tiles = np.arange(first, first + n)
+    return {"ratio": sampler.tempering[0], "every": sampler.tempering[1], "exchanges": int(len(np.unique(log["step"]))),
+            "exchange_rate": exchange_rates(log, sampler.restarts),
+            "winner_rung": sampler.replica_rung[sampler.replica_winner[tiles], tiles], "tempering_ms": sampler.tempering_ms}
+
+
+def format_tempering_summary(summary: Dict) -> str:
+    rate = ", ".join("-" if np.isnan(r) else f"{r:.2f}" for r in summary["exchange_rate"])
+    w = summary["winner_rung"]
+    return (f"tempering: ratio {summary['ratio']:g}, {summary['exchanges']} exchange(s) every {summary['every']} steps, accepted "
+            f"per pair of rungs [{rate}], {int(np.count_nonzero(w == 0))} of {len(w)} winner(s) on the coldest rung")
 
 
 def check_birth_map(config: Dict, world_size: int = 1) -> bool:
@@ -373,6 +413,7 @@ class MPPModel:
         ``inference.birth_map``: the birth-energy map of the image under the returned detections is left in
         ``self.last_birth`` = (dE [H,W] float64 device tensor, summary dict), see ``birth_map``."""
         check_restarts(self.config, world_size)               # (before any collective: every rank raises alike)
+        check_tempering(self.config, world_size)
         birth_map, complete = check_birth_map(self.config, world_size), check_birth_complete(self.config, world_size)
         if not birth_map and complete is None:
             return self._infer_image(image_data, rank, world_size, region_data, seed)
@@ -476,7 +517,11 @@ class MPPModel:
                          "total_steps": total, "snapshot_step": snaps[-1] if snaps else total - 1,
                          "kernel_ms": sampler.kernel_ms if sampler else 0.0,
                          "replica_energy": sampler.replica_energy if sampler else None,
-                         "replica_winner": sampler.replica_winner if sampler else None}
+                         "replica_winner": sampler.replica_winner if sampler else None,
+                         "tempering": tempering_summary(sampler)}
+        self.last_tempering = [self.last_run["tempering"]]
+        if self.last_run["tempering"] is not None:
+            logging.info(f"image {image_data.name}: {format_tempering_summary(self.last_run['tempering'])}")
         if world_size == 1 and arrays:
             # merge + scores on the device (``mpp_merge_score``); an image with more detections than its walk takes: the host
             xy = [r[0] + np.asarray(t.crop_data["tl_anchor"], dtype=np.int32) for r, t in zip(raw, tiles)]
@@ -560,7 +605,8 @@ class MPPModel:
         sampler = TileBatchSampler(tiles, self.energy_setup, self.energy_model, device=self.device,
                                    spec_waves=self.spec_waves, use_split_merge=bool(p.get("use_split_merge", False)),
                                    stacked_maps=getattr(self, "_stacked_maps", None),
-                                   restarts=check_restarts(self.config, world_size))
+                                   restarts=check_restarts(self.config, world_size),
+                                   tempering=check_tempering(self.config, world_size))
         self._stacked_maps = None
         sampler.init("naive")
         pack = None
@@ -607,7 +653,7 @@ class MPPModel:
         alpha, T_target, total, snaps = resolve_schedule(1, p["init_temperature"], p["alpha_t"], p["burn_in"],
                                                           p["samples_interval"], p["target_temperature"],
                                                           p.get("iter_multiplier"))
-        restarts = check_restarts(self.config)
+        restarts, tempering = check_restarts(self.config), check_tempering(self.config)
         layout, tiles, seeds, chains = [], [], [], []
         for k, (data, region) in enumerate(zip(images, regions)):
             patch, anchors = self.tile_layout(tuple(int(v) for v in data.shape[:2]))
@@ -627,7 +673,7 @@ class MPPModel:
         sampler = TileBatchSampler(tiles, self.energy_setup, self.energy_model, device=self.device, spec_waves=self.spec_waves,
                                    use_split_merge=bool(p.get("use_split_merge", False)),
                                    keys=(seeds, chains) if restarts == 1 else (seeds, chains, [n for _, n in layout for _ in range(n)]),
-                                   restarts=restarts)
+                                   restarts=restarts, tempering=tempering)
         sampler.init("naive")
         # merge + scores on the device for the whole batch when the images share a shape and a picture-free energy setup
         # (the classic image energies read a per-image picture the batch context does not hold)
@@ -639,6 +685,11 @@ class MPPModel:
         if sampler.hbm_chains:
             logging.info(f"{sampler.hbm_chains} chain(s) outgrew the LDS and continued with their state in device memory")
         self._log_restarts(sampler)
+        # (per image: its tiles' replicas paired up among themselves, drawing from the image's own key)
+        self.last_tempering = [tempering_summary(sampler, first, n) for first, n in layout]
+        for data, t in zip(images, self.last_tempering):
+            if t is not None:
+                logging.info(f"image {data.name}: {format_tempering_summary(t)}")
         if on_device:
             aggregated = []
             for first, n in layout:
@@ -717,11 +768,11 @@ class MPPModel:
     TILE_SHARD_MIN = 2048
 
     def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None,
-                       complete_summary=None) -> dict:
+                       complete_summary=None, tempering=None) -> dict:
         """Write ``NNNN_results.pkl`` of one image (mpp_model.py:333-366) and return what the two DOTA translators need
         of it (plain arrays: the records of all ranks travel to rank 0 in one gather).  ``birth_summary``
         (``inference.birth_map``) and ``complete_summary`` (``inference.birth_complete``, key ``birth_complete``): one more
-        key of the pickle each."""
+        key of the pickle each; ``tempering`` (``inference.tempering``): the image's ``tempering_summary``, key ``tempering``."""
         pts = list(merged)
         pred_params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
         pred_centers = np.array([[p.x, p.y] for p in pts]).reshape(-1, 2)
@@ -742,6 +793,8 @@ class MPPModel:
             record["birth_summary"] = birth_summary
         if complete_summary is not None:
             record["birth_complete"] = complete_summary
+        if tempering is not None:
+            record["tempering"] = tempering
         with open(out_file, "wb") as f:
             pickle.dump(record, f)
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
@@ -791,6 +844,7 @@ class MPPModel:
             figures = bool(self.config["inference"].get("figures", False))
         # (an image shared by all ranks refuses the option in ``infer_image``, before its first collective)
         birth_map, complete = check_birth_map(self.config), check_birth_complete(self.config)
+        check_tempering(self.config)
         dataset = self.config["dataset"]["dataset"]
         results_dir = get_inference_path(os.path.split(self.save_path)[1], dataset, subset)
         os.makedirs(results_dir, exist_ok=True)
@@ -835,8 +889,8 @@ class MPPModel:
 
             def flush():
                 res = self.infer_images([b[1] for b in batch], [b[2] for b in batch], image_seeds=[seeds[b[0]] for b in batch])
-                for (k, image_data, region_data), (merged, scores) in zip(batch, res):
-                    yield k, image_data, region_data, merged, scores
+                for (k, image_data, region_data), (merged, scores), tempered in zip(batch, res, self.last_tempering):
+                    yield k, image_data, region_data, merged, scores, tempered
 
             for k, (image_data, region_data) in stream:
                 patch, anchors = self.tile_layout(tuple(int(v) for v in image_data.shape[:2]))
@@ -849,7 +903,7 @@ class MPPModel:
                 yield from flush()
 
         try:
-            for k, image_data, region_data, merged, scores in inferred():
+            for k, image_data, region_data, merged, scores, tempered in inferred():
                 birth = done = None
                 if complete is not None:            # (before the map and the figures: they show the completed list)
                     merged, scores, done = self.complete(region_data, merged)
@@ -858,7 +912,7 @@ class MPPModel:
                     self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
                     del dE
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth,
-                                                   complete_summary=done))
+                                                   complete_summary=done, tempering=tempered))
                 if figures:
                     self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all

@@ -110,12 +110,53 @@ def select_replicas(energy, n_tiles: int) -> np.ndarray:
     return best
 
 
+#: ``tempering`` defaults: the factor between the schedules of neighbouring rungs (the swept value with the lowest mean winner
+#: energy at R = 4, every 4096 -- which still is no lower than that of plain restarts: profiles/tempering.md) and the steps
+#: between two exchanges (the shortest interval whose segments still get a hot start)
+TEMPERING_RATIO, TEMPERING_EVERY = 1.25, 4096
+
+
+def resolve_tempering(tempering, restarts: int):
+    """``None`` / ``False`` -> None; ``True`` or ``{"ratio": r, "every": K}`` (either key optional) -> ``(ratio, every)``.
+    Raises ``ValueError`` for fewer than two restarts, a ratio below 1 or not finite, an interval below 1, unknown keys."""
+    if tempering is None or tempering is False:
+        return None
+    opts = {} if tempering is True else tempering
+    if not isinstance(opts, dict) or set(opts) - {"ratio", "every"}:
+        raise ValueError(f"tempering must be true or a mapping with 'ratio' and / or 'every', got {tempering!r}")
+    if int(restarts) < 2:
+        raise ValueError(f"tempering exchanges the replicas of a tile: it needs restarts >= 2, got {restarts}")
+    ratio, every = opts.get("ratio", TEMPERING_RATIO), opts.get("every", TEMPERING_EVERY)
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not np.isfinite(ratio) or ratio < 1:
+        raise ValueError(f"tempering: ratio must be a finite number >= 1, got {ratio!r}")
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"tempering: every must be an integer >= 1, got {every!r}")
+    return float(ratio), int(every)
+
+
+def rungs_after(log, n_tiles: int, restarts: int) -> np.ndarray:
+    """The rung of every chain, int64 ``[restarts, n_tiles]``, after the exchanges of ``log`` (records of
+    ``EXCHANGE_RECORD_DTYPE`` from the ladder's start on): replica r starts on rung r, an accepted record swaps two."""
+    rung = np.repeat(np.arange(restarts, dtype=np.int64), n_tiles)
+    for a, b in zip(log["chain_a"][log["accepted"] != 0].tolist(), log["chain_b"][log["accepted"] != 0].tolist()):
+        rung[a], rung[b] = rung[b], rung[a]
+    return rung.reshape(restarts, n_tiles)
+
+
+def exchange_rates(log, restarts: int) -> np.ndarray:
+    """accepted / attempted per pair of neighbouring rungs, float64 ``[restarts - 1]`` (NaN: a pair never attempted)"""
+    tried = np.bincount(log["k"], minlength=restarts - 1).astype(np.float64)
+    took = np.bincount(log["k"], weights=(log["accepted"] != 0), minlength=restarts - 1).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(tried > 0, took / tried, np.nan)
+
+
 class TileBatchSampler:
     """All tiles of an image (or of a batch of images) sampled concurrently on one GPU."""
 
     def __init__(self, tiles: Sequence[ImageWMaps], energy_setup, energy_combinator, device: int = 0,
                  point_capacity: int = 1024, spec_waves: Optional[int] = 8, ctx: Optional[MppContext] = None,
-                 use_split_merge: bool = False, keys=None, stacked_maps=None, restarts: int = 1):
+                 use_split_merge: bool = False, keys=None, stacked_maps=None, restarts: int = 1, tempering=None):
         """``keys`` = (seeds, chain ids), one per tile: the Philox key and chain id each tile's chain uses instead of the
         launch's seed and ``chain0 + tile`` -- tiles of several images in one launch keep the chains they would run in a
         launch of their own image (``mpp_set_chain_keys``).
@@ -125,12 +166,20 @@ class TileBatchSampler:
         own), and ``run`` hands back, per tile, the replica whose returned state has the lowest total energy
         (``select_replicas``; kept in ``replica_energy`` [R, n_tiles] and ``replica_winner`` [n_tiles]).  With ``keys`` of
         several images a third entry gives, per tile, the tile count of its image (the images' tiles in order): replica
-        ids are per image."""
+        ids are per image.
+
+        ``tempering`` = ``True`` or ``{"ratio": r, "every": K}`` (needs ``restarts`` >= 2): parallel tempering.  Replica r of
+        a tile starts on rung r of a temperature ladder (its schedule ``ratio ** r`` times hotter) and every K steps
+        neighbouring rungs of a tile exchange their schedules by a Metropolis test (``MppContext.run_tempered``).  The
+        returned state is chosen as for restarts.  ``run`` keeps ``replica_rung`` [R, n_tiles] (the rungs at the returned
+        state), ``exchange_log`` and ``exchange_rate`` [R - 1].  ``None``: the replicas never interact."""
         self.use_split_merge = use_split_merge
         self.restarts = int(restarts)
         if self.restarts < 1:
             raise ValueError(f"restarts must be >= 1, got {restarts}")
         self.replica_energy = self.replica_winner = None
+        self.tempering = resolve_tempering(tempering, self.restarts)
+        self.replica_rung = self.exchange_log = self.exchange_rate = None
         shapes = {tuple(t.shape[:2]) for t in tiles}
         if len(shapes) != 1:
             raise ValueError(f"all tiles of a batch must have the same shape, got {shapes}")
@@ -238,6 +287,9 @@ class TileBatchSampler:
             else:
                 self.ctx.set_chain_keys(np.full(R * n, int(seed), np.uint64), replica_chain_ids(n, R, chain0))
         self.ctx.set_schedule(T0, alpha, T_target)
+        if self.tempering:
+            self.ctx.set_ladder(self.tempering[0])
+            self._logs = []
         wanted = list(snapshot_steps)[-num_samples:] if snapshot_steps else []
         samples = [[] for _ in self.tiles]
 
@@ -249,6 +301,8 @@ class TileBatchSampler:
             if R > 1:
                 self.replica_energy = self.ctx.total_energy_all().reshape(R, n)
                 self.replica_winner = select_replicas(self.replica_energy, n)
+                if self.tempering:
+                    self.replica_rung = rungs_after(np.concatenate(self._logs), n, R)
                 chains = [chains[int(r) * n + i] for i, r in enumerate(self.replica_winner)]
             for i, pts in enumerate(chains[:n]):
                 samples[i].append(pts if as_arrays else _to_rectangles(*pts))
@@ -264,10 +318,17 @@ class TileBatchSampler:
             self._run_resumable(total_steps - done, seed, chain0)
         if not wanted:
             take()
+        if self.tempering:
+            self.exchange_log = np.concatenate(self._logs)
+            self.exchange_rate = exchange_rates(self.exchange_log, R)
+            self.tempering_ms = self.ctx.tempering_stats()["ms"]
         return samples
 
     def _run_resumable(self, n_steps: int, seed: int, chain0: int):
-        self.ctx.run(n_steps, seed, chain0)
+        if self.tempering:
+            self._logs.append(self.ctx.run_tempered(n_steps, seed, chain0, every=self.tempering[1]))
+        else:
+            self.ctx.run(n_steps, seed, chain0)
         self.kernel_ms += self.ctx.last_kernel_ms()
         self.hbm_chains = max(self.hbm_chains, self.ctx.get_option("hbm_chains"))
 
@@ -276,15 +337,18 @@ def sample_rjmcmc_batch(tiles: Sequence[ImageWMaps], rng: np.random.Generator, n
                         init_config, init_temperature: float, alpha_t, burn_in: int, energy_setup,
                         samples_interval: int, target_temperature: float, verbose: int = 0, iter_multiplier=None,
                         use_split_merge: bool = False, device: int = 0, spec_waves: int = 8,
-                        point_capacity: int = 1024, chain0: int = 0, restarts: int = 1):
+                        point_capacity: int = 1024, chain0: int = 0, restarts: int = 1, tempering=None):
     """``sample_rjmcmc`` for many equally-shaped tiles at once; returns one result list per tile.
-    ``restarts`` R > 1: R chains per tile, the configuration of the one with the lowest energy is returned."""
+    ``restarts`` R > 1: R chains per tile, the configuration of the one with the lowest energy is returned.
+    ``tempering``: those chains on a temperature ladder, with exchanges (``TileBatchSampler``)."""
+    resolve_tempering(tempering, restarts)
     if restarts > 1 and num_samples > 1:
         raise ValueError("restarts > 1 with num_samples > 1: a winner is defined for one returned state")
     alpha, T_target, total, snaps = resolve_schedule(num_samples, init_temperature, alpha_t, burn_in, samples_interval,
                                                       target_temperature, iter_multiplier)
     sampler = TileBatchSampler(tiles, energy_setup, energy_combinator, device=device, spec_waves=spec_waves,
-                               point_capacity=point_capacity, use_split_merge=use_split_merge, restarts=restarts)
+                               point_capacity=point_capacity, use_split_merge=use_split_merge, restarts=restarts,
+                               tempering=tempering)
     sampler.init(init_config)
     seed = int(rng.integers(0, 2 ** 63 - 1))
     start = time.perf_counter()
