@@ -202,6 +202,10 @@ int mpp_total_energy(mpp_ctx *ctx, int tile, double *energy, double *vectors_or_
  * chain.  A fixed number of launches, one copy of n_chains doubles and one synchronise, however many chains; honours
  * "scratch_grid_min_points".  What the choice among restarts reads (sampler.select_replicas). */
 int mpp_total_energy_all(mpp_ctx *ctx, double *energy);
+/* The per-point energies behind mpp_total_energy_all, from the same launches: e HOST [n_chains][point_capacity],
+ * e[c][s] = e(point in slot s of chain c | the chain's configuration) for s < n_c, 0.0 behind n_c.  Row c added up in slot
+ * order from 0.0 is energy[c] of mpp_total_energy_all, bit for bit.  The same refusals. */
+int mpp_point_energies_all(mpp_ctx *ctx, double *e);
 /* energy_delta(Perturbation) for a batch of perturbations with list removals/additions:
  * case i removes slots rem[rem_off[i]..rem_off[i+1]) and adds rectangles add_off[i]..add_off[i+1] */
 int mpp_delta_batch(mpp_ctx *ctx, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
@@ -290,6 +294,44 @@ int mpp_select_minima(mpp_ctx *ctx, int H, int W, int ld, const double *dE_dev, 
  * mpp_birth_energy_map (no maps or no model; a classic image energy; more than 65535 chains). */
 typedef struct { int32_t status, rounds, n_added, n_after; double gain, min_dE; int32_t x, y; int64_t n_negative, n_nan; } mpp_complete_report;
 int mpp_birth_complete(mpp_ctx *ctx, int max_rounds, double min_gain, mpp_complete_report *report);
+/* Recombination of restarts (csrc/mpp_recombine.hip): per tile, the best replica PER INTERACTION
+ * CLUSTER instead of the best replica as a whole.  n = n_chains / "replicas" tiles, R = "replicas" >= 2, chain r * n + i is
+ * replica r of tile i; the state is the one mpp_get_points_all reads.  All on the ctx's stream; only the reports and src
+ * cross to the host.  The rules, such that a restatement on the host matches every output exactly:
+ *   1. energies  the launches of mpp_total_energy_all: per-point e and per-chain sums, the same bits ("scratch_grid_min_points"
+ *                is honoured).
+ *   2. winner    w_i, the rule of sampler.select_replicas: start at replica 0; replica r replaces the best when its chain
+ *                energy is strictly lower, or when the best is not finite and r's is.
+ *   3. link      two points of the tile -- of any two replicas, or of the same one -- are linked iff
+ *                sqrt((double)dx*dx + (double)dy*dy) <= max_inter in float64, the "interacts" test of the energy kernels
+ *                (points_interact, csrc/mpp_scratch.hpp).  Coincident points are linked.
+ *   4. cluster   a connected component of the links; its id is the smallest global index g = r * point_capacity + slot among
+ *                its members.  (Min-label propagation with pointer jumping, one workgroup per tile, until a sweep changes
+ *                nothing; the labels live in LDS while the tile's points over all replicas number at most
+ *                "recombine_lds_points", default and upper limit MPP_RECOMBINE_LDS_POINTS, else in a workspace of the ctx.)
+ *   5. sums      S[r][C] = the sum of e over replica r's members of C in ascending slot order, float64 from 0.0; a replica
+ *                without a member in C has S = 0.0 and competes like any other.
+ *   6. choice    best = w_i; for r = 0 .. R-1, r != w_i: r is taken when S[r][C] < S[best][C], or when S[best][C] is not
+ *                finite and S[r][C] is.  Ties stay with the winner.
+ *   7. composite replicas in the order w_i, then 0 .. R-1 without w_i, slots ascending within a replica; a point is kept iff
+ *                its cluster chose its replica.  The m_i kept points go to slots 0 .. m_i-1 of chain w_i * n + i (positions,
+ *                marks, count, error code 0): the state mpp_set_points(composite) leaves.  Staged through a workspace.  Every
+ *                other chain, and every schedule, key, step counter and intensity, is untouched.
+ *   8. status    0: no cluster chose another replica -- nothing is written, the winner chain keeps its bytes; 1: recombined;
+ *                2: m_i > point_capacity -- nothing is written for that tile, the other tiles go on.
+ *   9. report    status, winner; n_clusters, n_taken (clusters that chose r != w_i); n_before / n_after: the count of chain
+ *                w_i * n + i before / after the call; E_winner: that chain's energy (rule 1); E_sum: the chosen S added in
+ *                ascending cluster id, float64 from 0.0 (whatever the status); E_after: the launches of rule 1 once more on
+ *                the written state -- mpp_total_energy(ctx, w_i * n + i, ..) bit for bit, E_winner for status 0 and 2.
+ *  10. src       src_or_null HOST [n][point_capacity][2] int32: src[i][k] = (replica, slot) composite slot k came from, for
+ *                k < n_after; for status 0 and 2 that is (w_i, k); (-1, -1) behind n_after.
+ * Every point of X* keeps the neighbours it had in its replica and gains none (both lie in its cluster), and the pair
+ * reductions are max / min, so e(v | X*) = e(v | X_r(C)) bit for bit and, in real arithmetic, E_after = E_sum <= E_winner.
+ * report HOST [n].  -1 with a message: no maps or no model; "replicas" < 2; more than 65535 chains.  A model with a classic
+ * image energy is allowed (its unit terms are per point); a reduction that is not MPP_REDUCE_MAX / MPP_REDUCE_MIN is refused. */
+#define MPP_RECOMBINE_LDS_POINTS 2048      /* points of a tile, over all replicas, whose labels fit the LDS */
+typedef struct { int32_t status, winner, n_clusters, n_taken, n_before, n_after; double E_winner, E_sum, E_after; } mpp_recombine_report;
+int mpp_recombine(mpp_ctx *ctx, mpp_recombine_report *report, int32_t *src_or_null);
 /* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points.  Candidates are
  * det >= (float)threshold (float32, as NumPy compares); rank and NMS rule as mpp_detect_centers below.  A tile that keeps more
  * than point_capacity points: -12 ("naive init, tile t"), its first point_capacity picks stay stored; every call replaces

@@ -2,7 +2,7 @@
 """Command-line entry, same flags as the reference's ``main.py:11-109``:
 
     python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map] [--birth-complete]
-                   [--restarts R [--tempering [RATIO]]]
+                   [--restarts R [--tempering [RATIO]] [--recombine]]
     python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map] [--birth-complete]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
@@ -71,6 +71,11 @@ def build_parser():
                              "temperatures, RATIO apart from rung to rung (default: the sampler's), and neighbouring rungs "
                              "exchange their schedules at intervals; needs --restarts or inference.restarts of at least 2; same "
                              "as inference.tempering in the config (whose 'every' it keeps); off by default")
+    parser.add_argument("--recombine", action="store_true",
+                        help="(-m mpp, infer / infereval / detect) recombine the restarts of a tile: every interaction cluster of "
+                             "the returned configuration comes from the restart that spends the least energy there, instead of "
+                             "the lowest-energy restart as a whole; needs --restarts or inference.restarts of at least 2; same as "
+                             "inference.recombine in the config; off by default")
     parser.add_argument("--figures", action="store_true",
                         help="(-m mpp, infer / infereval / detect) write the result pictures composed on the GPU: NNNN_detection.png, "
                              "NNNN_gt.png (and NNNN_detection_map.png) beside NNNN_results.pkl; same as inference.figures in the config")
@@ -100,6 +105,13 @@ def apply_birth_complete(args, config):
         inference = config.setdefault("inference", {})
         if not isinstance(inference.get("birth_complete"), dict):
             inference["birth_complete"] = True
+    return config
+
+
+def apply_recombine(args, config):
+    """--recombine turns inference.recombine on"""
+    if args.recombine and args.procedure in ("infer", "infereval", "detect"):
+        config.setdefault("inference", {})["recombine"] = True
     return config
 
 
@@ -150,6 +162,7 @@ def main():
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
         apply_tempering(args, config)
+        apply_recombine(args, config)
         model = MPPModel(config, phase="val", load=True, device=local_rank,
                          nets=load_nets(config, local_rank, args.unet_max_pixels), spec_waves=args.spec_waves)
         detect.detect_files(model, args.images, args.out, gsd=args.gsd, model_gsd=args.model_gsd, min_score=args.min_score,
@@ -167,6 +180,7 @@ def main():
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
         apply_tempering(args, config)
+        apply_recombine(args, config)
         nets = None
         if args.unet:
             nets = load_nets(config, local_rank, args.unet_max_pixels)

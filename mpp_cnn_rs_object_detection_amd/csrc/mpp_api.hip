@@ -117,6 +117,10 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     // configurations of at least this many points get a candidate grid for the from-scratch energies; 0 = never
     if (v < 0) return fail(c, -1, "scratch_grid_min_points must be >= 0");
     c->grid_min_points = (int)v;
+  } else if (!strcmp(name, "recombine_lds_points")) {
+    // mpp_recombine labels a tile of at most this many points (over its replicas) in LDS, a larger one in device memory
+    if (v < 0 || v > MPP_RECOMBINE_LDS_POINTS) return fail(c, -1, "recombine_lds_points must be in 0..%d", MPP_RECOMBINE_LDS_POINTS);
+    c->recombine_lds = (int)v;
   } else if (!strcmp(name, "cell_capacity")) {
     if (v < 1 || v > MPP_CELL_CAP_MAX) return fail(c, -1, "cell_capacity must be in 1..%d", MPP_CELL_CAP_MAX);
     c->cell_cap = (int)v; c->params_dirty = true;
@@ -211,6 +215,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "rescale_bands")) return c->rescale.bands;                  // bands of the last mpp_rescale
   if (!strcmp(name, "rescale_bytes")) return (int64_t)c->rescale.dev_bytes;     // its device workspace right now
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
+  if (!strcmp(name, "recombine_lds_points")) return c->recombine_lds;
   if (!strcmp(name, "birth_map_grid")) return c->birth_grid;                    // the last birth map's pre-pass built grids
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)

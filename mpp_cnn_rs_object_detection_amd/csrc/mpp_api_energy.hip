@@ -85,6 +85,56 @@ extern "C" int mpp_total_energy_all(mpp_ctx *c, double *energy) {
   return 0;
 }
 
+// The per-point energies of those launches (they start the workspace): rows of cap doubles, zero behind a chain's count.
+extern "C" int mpp_point_energies_all(mpp_ctx *c, double *e) {
+  if (!c || !e) return fail(c, -1, "bad point_energies_all arguments");
+  int rc = push_state(c);
+  if (rc) return rc;
+  double *d_sum = nullptr;
+  if ((rc = chain_energy_launches(c, &d_sum))) return rc;
+  const int T = c->n_tiles;
+  const size_t TC = (size_t)T * c->cap;
+  std::vector<int32_t> n(T);
+  hipError_t e0 = hipMemcpyAsync(e, c->energy_ws.p, TC * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e1 = hipMemcpyAsync(n.data(), c->n, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e0); HIPCHK(c, e1); HIPCHK(c, e2);
+  for (int t = 0; t < T; ++t)                                   // (the kernel writes the slots below the count only)
+    for (int s = n[t] < 0 ? 0 : n[t]; s < c->cap; ++s) e[(size_t)t * c->cap + s] = 0.0;
+  return 0;
+}
+
+// Recombination of restarts (mpp_recombine.hip; the rules: include/mpp_hip.h): the energy launches, the tiles' kernel, the
+// energy launches on the written state, one copy of the reports (and of src) and one synchronise.
+extern "C" int mpp_recombine(mpp_ctx *c, mpp_recombine_report *report, int32_t *src) {
+  if (!c) return -1;
+  if (!c->have_maps || !c->have_model) return fail(c, -1, "recombine: mpp_set_maps / mpp_set_model have not been called");
+  if (!report) return fail(c, -1, "recombine: report is NULL");
+  const int R = c->replicas, T = c->n_tiles, n = c->n_maps;
+  if (R < 2) return fail(c, -1, "recombine: it chooses among the replicas of a tile, \"replicas\" is %d (needs >= 2)", R);
+  if (T > 65535) return fail(c, -1, "recombine: %d chains, at most 65535", T);
+  for (int p = 0; p < c->hp.model.n_pair; ++p)                   // (the locality argument needs an order-free reduction)
+    if (c->hp.model.pair[p].reduce != MPP_REDUCE_MAX && c->hp.model.pair[p].reduce != MPP_REDUCE_MIN)
+      return fail(c, -1, "recombine: pair term %d has a reduction that is neither max nor min", p);
+  int rc = push_state(c);
+  if (rc) return rc;
+  if (c->recombine_ws.reserve(c->stream, mpp_recombine_bytes(n, R, c->cap)) != hipSuccess)
+    return fail(c, -2, "no device memory for the recombination of %d tile(s) of %d replicas", n, R);
+  Recomb ws;
+  mpp_recombine_plan(&ws, n, R, c->cap, c->recombine_ws.p);
+  double *d_sum = nullptr;
+  if ((rc = chain_energy_launches(c, &d_sum))) return rc;
+  mpp_launch_recombine(c->stream, c->dp, c->d_tiles, ws, (const double *)c->energy_ws.p, d_sum, c->recombine_lds);
+  if ((rc = chain_energy_launches(c, &d_sum))) return rc;
+  mpp_launch_recombine_after(c->stream, ws, d_sum);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(report, ws.rep, (size_t)n * sizeof(mpp_recombine_report), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && src) e = hipMemcpyAsync(src, ws.src, (size_t)n * c->cap * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
 // What mpp_birth_energy_map and mpp_birth_complete refuse alike; `who` names the caller in the message.
 static int birth_refusals(mpp_ctx *c, const char *who) {
   if (!c->have_maps || !c->have_model) return fail(c, -1, "%s: mpp_set_maps / mpp_set_model have not been called", who);

@@ -140,6 +140,8 @@ struct mpp_ctx : TileMem {
   int birth_grid = 0;                // ... its last pre-pass built candidate grids
   DevWs minsel_ws;                   // mpp_select_minima / mpp_birth_complete: the candidate list and its tables
   DevWs complete_ws;                 // mpp_birth_complete: every chain's map, the appended values, the reports
+  DevWs recombine_ws;                // mpp_recombine: the tiles' labels and cluster choices, the staged composites, the reports
+  int recombine_lds = MPP_RECOMBINE_LDS_POINTS;   // ... a tile of more points over its replicas labels in the workspace, not in LDS
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)
   RescaleWs rescale;                 // workspace of mpp_rescale (mpp_rescale.hip)

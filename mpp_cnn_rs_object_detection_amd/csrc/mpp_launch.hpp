@@ -148,6 +148,24 @@ void mpp_launch_complete_summary(hipStream_t st, int n_chains, const mpp_birth_s
 void mpp_launch_exchange(hipStream_t st, const TileRef *tiles, int n_maps, int R, double *sched, int32_t *rung, const double *energy,
                          long long s, long long e, unsigned long long seed, unsigned int chain0, long long *accepted,
                          mpp_exchange_record *log, long long log_base, long long log_cap);
+// the recombination of restarts (mpp_recombine.hip), all device.  Recomb: the workspace of one call, placed by
+// mpp_recombine_plan in mpp_recombine_bytes bytes.  mpp_launch_recombine: from the point energies e_pts [n_chains][cap] and
+// chain energies e_sum [n_chains] (those of mpp_launch_chain_energies) to the written winner chains, rep and src; a tile of
+// more than lds_points points over its replicas labels in the workspace.  _after: E_after of every report from the chain
+// energies of the written state.
+struct Recomb {
+  int n, R, cap;                                   // tiles, replicas, point capacity
+  int32_t *off;                                    // [n][R + 1] where a replica's points start in the tile's compact order
+  int32_t *lab, *choice; uint32_t *xy; double *chosen;   // [n][R * cap] labels, packed positions, and per cluster root its replica and sum
+  int32_t *spx, *spy; double *sps, *spr, *spa;     // [n][cap] the staged composite
+  int32_t *src;                                    // [n][cap][2]
+  mpp_recombine_report *rep;                       // [n]
+};
+size_t mpp_recombine_bytes(int n, int R, int cap);
+void mpp_recombine_plan(Recomb *rc, int n, int R, int cap, void *ws);
+void mpp_launch_recombine(hipStream_t st, const DevParams *P, const TileRef *tiles, const Recomb &rc, const double *e_pts,
+                          const double *e_sum, int lds_points);
+void mpp_launch_recombine_after(hipStream_t st, const Recomb &rc, const double *e_sum);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);

@@ -12,6 +12,15 @@ __device__ __forceinline__ int grid_coord(const DevParams *P, int x) {
   return P->res_shift >= 0 ? (x >> P->res_shift) : (x / P->res_int);
 }
 
+// "u and v interact": the centres, (ix, iy) apart, lie within the model's largest pair range.  The one statement of the
+// predicate the from-scratch kernels evaluate inline (point_reductions below, the touched / listed tests of mpp_scratch.hip and
+// mpp_birth_map.hip keep their own copies of the expression: it is the same arithmetic, and their code is not touched).
+// What links two points of mpp_recombine (mpp_recombine.hip).
+__device__ __forceinline__ bool points_interact(const DevParams *P, int ix, int iy) {
+  const double dx = (double)ix, dy = (double)iy;
+  return sqrt(dx * dx + dy * dy) <= P->max_inter;
+}
+
 struct Overlay {
   int n_excl; const int32_t *excl;          // slots removed
   int n_extra; const int32_t *exy; const double *emarks;   // rectangles added

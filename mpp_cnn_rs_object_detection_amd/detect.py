@@ -75,6 +75,7 @@ class DetectResult:
     birth: Any = None                 # ``inference.birth_map``: (dE [h,w] float64 device tensor, summary dict) of ``MPPModel.birth_map``
     complete: Any = None              # ``inference.birth_complete``: the summary dict of ``MPPModel.complete`` (``detections`` are completed)
     tempering: Any = None             # ``inference.tempering``: ``last_run["tempering"]`` (exchange rates, the winners' rungs)
+    recombine: Any = None             # ``inference.recombine``: ``last_run["recombine"]`` (per tile: status, clusters, energies)
 
     def polygons(self) -> np.ndarray:
         """[n,4,2] corners in the pixels the model saw (``rect_to_poly`` of (a, b, angle), as ``infer`` stores them)"""
@@ -119,7 +120,8 @@ def detect_image(model, rgb_uint8: np.ndarray, gsd: Optional[float] = None, mode
     detections, scores = model.infer_image(data, seed=seed)
     return DetectResult(detections=detections, scores=np.asarray(scores, dtype=np.float64), image=image, scale=scale,
                         source_shape=(H, W), birth=getattr(model, "last_birth", None), complete=getattr(model, "last_complete", None),
-                        tempering=(getattr(model, "last_run", None) or {}).get("tempering"))
+                        tempering=(getattr(model, "last_run", None) or {}).get("tempering"),
+                        recombine=(getattr(model, "last_run", None) or {}).get("recombine"))
 
 
 def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Optional[float] = None, figures: bool = False,
@@ -143,6 +145,8 @@ def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Opti
         record["birth_complete"] = result.complete
     if result.tempering is not None:
         record["tempering"] = result.tempering
+    if result.recombine is not None:
+        record["recombine"] = result.recombine
     with open(os.path.join(out_dir, f"{stem}_results.pkl"), "wb") as f:
         pickle.dump(record, f)
     if figures:

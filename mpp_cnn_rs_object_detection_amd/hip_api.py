@@ -92,6 +92,12 @@ BIRTH_CHUNK = 256
 COMPLETE_REPORT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_added", "<i4"), ("n_after", "<i4"), ("gain", "<f8"),
                                   ("min_dE", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_negative", "<i8"), ("n_nan", "<i8")], align=True)
 COMPLETE_CONVERGED, COMPLETE_ROUND_LIMIT, COMPLETE_CAPACITY = 0, 1, 2
+#: mpp_recombine_report, one per tile (``MppContext.recombine``); status: 0 the winner stays as it is, 1 recombined, 2 the
+#: composite does not fit point_capacity.  RECOMBINE_LDS_POINTS: the points of a tile whose labels fit the LDS
+RECOMBINE_REPORT_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_clusters", "<i4"), ("n_taken", "<i4"), ("n_before", "<i4"),
+                                   ("n_after", "<i4"), ("E_winner", "<f8"), ("E_sum", "<f8"), ("E_after", "<f8")], align=True)
+RECOMBINE_UNCHANGED, RECOMBINE_DONE, RECOMBINE_CAPACITY = 0, 1, 2
+RECOMBINE_LDS_POINTS = 2048
 #: mpp_exchange_record, one per attempted exchange of ``MppContext.run_tempered``: the values as read before the swap
 EXCHANGE_RECORD_DTYPE = np.dtype([("step", "<i8"), ("tile", "<i4"), ("k", "<i4"), ("chain_a", "<i4"), ("chain_b", "<i4"),
                                   ("accepted", "<i4"), ("_pad", "<i4"), ("Ea", "<f8"), ("Eb", "<f8"), ("Ta", "<f8"),
@@ -122,12 +128,14 @@ PROTOTYPES = {
     "mpp_pack_detections": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, C.POINTER(C.c_int32)]),
     "mpp_total_energy": (_i32, [_vp, _i32, C.POINTER(_dbl), _vp]),
     "mpp_total_energy_all": (_i32, [_vp, _vp]),
+    "mpp_point_energies_all": (_i32, [_vp, _vp]),
     "mpp_delta_batch": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpp_delta_vectors": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "mpp_papangelou": (_i32, [_vp, _i32, _vp]),
     "mpp_birth_energy_map": (_i32, [_vp, _vp, _vp, _vp]),
     "mpp_select_minima": (_i32, [_vp, _i32, _i32, _i32, _vp, _dbl, _dbl, _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mpp_birth_complete": (_i32, [_vp, _i32, _dbl, _vp]),
+    "mpp_recombine": (_i32, [_vp, _vp, _vp]),
     "mpp_conv3x3_c32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpp_conv3x3_stem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mpp_merge_score": (_i32, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -456,6 +464,25 @@ class MppContext:
         e = np.zeros(self.get_option("n_chains"), np.float64)
         self._check(self._L.mpp_total_energy_all(self._h, _ptr(e)))
         return e
+
+    def point_energies_all(self) -> np.ndarray:
+        """The per-point energies behind :meth:`total_energy_all`, float64 ``[n_chains, point_capacity]``: row c holds the
+        energies of chain c's points in slot order, 0.0 behind its count; the row summed in that order from 0.0 is
+        ``total_energy_all()[c]`` bit for bit (``mpp_point_energies_all``)"""
+        e = np.zeros((max(self.get_option("n_chains"), 1), self.get_option("point_capacity")), np.float64)
+        self._check(self._L.mpp_point_energies_all(self._h, _ptr(e)))
+        return e[:self.get_option("n_chains")]
+
+    def recombine(self, src: bool = False):
+        """``mpp_recombine``: per tile, the winning replica's chain takes, for every interaction cluster of the union of the
+        tile's replicas, the points of the replica that spends the least energy there (the rules: ``include/mpp_hip.h``).
+        Returns one record of ``RECOMBINE_REPORT_DTYPE`` per tile; with ``src`` also int32 ``[n_tiles, point_capacity, 2]``,
+        the (replica, slot) every slot of the returned winner chain came from, (-1, -1) behind its count."""
+        n = self.get_option("n_chains") // max(self.get_option("replicas"), 1)
+        rep = np.zeros(max(n, 1), RECOMBINE_REPORT_DTYPE)
+        where = np.full((max(n, 1), self.get_option("point_capacity"), 2), -1, np.int32) if src else None
+        self._check(self._L.mpp_recombine(self._h, _ptr(rep), _ptr(where)))
+        return (rep[:n], where[:n]) if src else rep[:n]
 
     @staticmethod
     def _pack_cases(removals, add_xy, add_marks):

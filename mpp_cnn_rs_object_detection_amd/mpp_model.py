@@ -182,6 +182,41 @@ def format_tempering_summary(summary: Dict) -> str:
             f"per pair of rungs [{rate}], {int(np.count_nonzero(w == 0))} of {len(w)} winner(s) on the coldest rung")
 
 
+def check_recombine(config: Dict, world_size: int = 1) -> bool:
+    """``inference.recombine`` of a config (default off): ``true`` or ``false`` -- a tile returns, for every interaction
+    cluster of the union of its restarts' points, the points of the restart that spends the least energy there, instead of
+    its lowest-energy restart as a whole (``TileBatchSampler``).  It chooses among the restarts of a
+    tile, so it refuses what ``inference.restarts`` refuses, and also one restart."""
+    v = (config.get("inference") or {}).get("recombine", False)
+    restarts = check_restarts(config, world_size)
+    if v is None or v is False:
+        return False
+    if v is not True:
+        raise ValueError(f"inference.recombine must be true or false, got {v!r}")
+    if restarts < 2:
+        raise ValueError(f"inference.recombine chooses among the restarts of a tile: set inference.restarts to 2 or more "
+                         f"(it is {restarts})")
+    return True
+
+
+def recombine_summary(sampler, first: int = 0, n: Optional[int] = None) -> Optional[Dict]:
+    """What the recombination did to the tiles ``first .. first + n`` of ``sampler`` (one image's; default: all), per tile:
+    status (0 the winner as it was, 1 recombined, 2 the composite did not fit), clusters, clusters taken from another
+    replica than the winner, the winner's energy and the energy of the returned configuration."""
+    rep = getattr(sampler, "recombine_report", None) if sampler is not None else None
+    if rep is None:
+        return None
+    rep = rep[first:(len(rep) if n is None else first + n)]
+    return {k: rep[k].copy() for k in ("status", "n_clusters", "n_taken", "E_winner", "E_after")}
+
+
+def format_recombine_summary(summary: Dict) -> str:
+    s = summary
+    gain = float(np.nansum(s["E_winner"] - s["E_after"]))
+    return (f"recombine: {int(s['n_taken'].sum())} of {int(s['n_clusters'].sum())} cluster(s) in "
+            f"{int(np.count_nonzero(s['status'] == 1))} of {len(s['status'])} tile(s) taken from another replica, energy -{gain:.3f}")
+
+
 def check_birth_map(config: Dict, world_size: int = 1) -> bool:
     """``inference.birth_map`` of a config (default off): the birth-energy map of every image, computed on ONE context that
     holds the image as its single tile with the merged detections.  Ranks that share one image hold a region of its maps
@@ -414,6 +449,7 @@ class MPPModel:
         ``self.last_birth`` = (dE [H,W] float64 device tensor, summary dict), see ``birth_map``."""
         check_restarts(self.config, world_size)               # (before any collective: every rank raises alike)
         check_tempering(self.config, world_size)
+        check_recombine(self.config, world_size)
         birth_map, complete = check_birth_map(self.config, world_size), check_birth_complete(self.config, world_size)
         if not birth_map and complete is None:
             return self._infer_image(image_data, rank, world_size, region_data, seed)
@@ -518,10 +554,13 @@ class MPPModel:
                          "kernel_ms": sampler.kernel_ms if sampler else 0.0,
                          "replica_energy": sampler.replica_energy if sampler else None,
                          "replica_winner": sampler.replica_winner if sampler else None,
-                         "tempering": tempering_summary(sampler)}
+                         "tempering": tempering_summary(sampler), "recombine": recombine_summary(sampler)}
         self.last_tempering = [self.last_run["tempering"]]
         if self.last_run["tempering"] is not None:
             logging.info(f"image {image_data.name}: {format_tempering_summary(self.last_run['tempering'])}")
+        self.last_recombine = [self.last_run["recombine"]]
+        if self.last_run["recombine"] is not None:
+            logging.info(f"image {image_data.name}: {format_recombine_summary(self.last_run['recombine'])}")
         if world_size == 1 and arrays:
             # merge + scores on the device (``mpp_merge_score``); an image with more detections than its walk takes: the host
             xy = [r[0] + np.asarray(t.crop_data["tl_anchor"], dtype=np.int32) for r, t in zip(raw, tiles)]
@@ -606,7 +645,8 @@ class MPPModel:
                                    spec_waves=self.spec_waves, use_split_merge=bool(p.get("use_split_merge", False)),
                                    stacked_maps=getattr(self, "_stacked_maps", None),
                                    restarts=check_restarts(self.config, world_size),
-                                   tempering=check_tempering(self.config, world_size))
+                                   tempering=check_tempering(self.config, world_size),
+                                   recombine=check_recombine(self.config, world_size))
         self._stacked_maps = None
         sampler.init("naive")
         pack = None
@@ -653,7 +693,7 @@ class MPPModel:
         alpha, T_target, total, snaps = resolve_schedule(1, p["init_temperature"], p["alpha_t"], p["burn_in"],
                                                           p["samples_interval"], p["target_temperature"],
                                                           p.get("iter_multiplier"))
-        restarts, tempering = check_restarts(self.config), check_tempering(self.config)
+        restarts, tempering, recombine = check_restarts(self.config), check_tempering(self.config), check_recombine(self.config)
         layout, tiles, seeds, chains = [], [], [], []
         for k, (data, region) in enumerate(zip(images, regions)):
             patch, anchors = self.tile_layout(tuple(int(v) for v in data.shape[:2]))
@@ -673,7 +713,7 @@ class MPPModel:
         sampler = TileBatchSampler(tiles, self.energy_setup, self.energy_model, device=self.device, spec_waves=self.spec_waves,
                                    use_split_merge=bool(p.get("use_split_merge", False)),
                                    keys=(seeds, chains) if restarts == 1 else (seeds, chains, [n for _, n in layout for _ in range(n)]),
-                                   restarts=restarts, tempering=tempering)
+                                   restarts=restarts, tempering=tempering, recombine=recombine)
         sampler.init("naive")
         # merge + scores on the device for the whole batch when the images share a shape and a picture-free energy setup
         # (the classic image energies read a per-image picture the batch context does not hold)
@@ -690,6 +730,10 @@ class MPPModel:
         for data, t in zip(images, self.last_tempering):
             if t is not None:
                 logging.info(f"image {data.name}: {format_tempering_summary(t)}")
+        self.last_recombine = [recombine_summary(sampler, first, n) for first, n in layout]
+        for data, t in zip(images, self.last_recombine):
+            if t is not None:
+                logging.info(f"image {data.name}: {format_recombine_summary(t)}")
         if on_device:
             aggregated = []
             for first, n in layout:
@@ -768,11 +812,12 @@ class MPPModel:
     TILE_SHARD_MIN = 2048
 
     def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None,
-                       complete_summary=None, tempering=None) -> dict:
+                       complete_summary=None, tempering=None, recombine=None) -> dict:
         """Write ``NNNN_results.pkl`` of one image (mpp_model.py:333-366) and return what the two DOTA translators need
         of it (plain arrays: the records of all ranks travel to rank 0 in one gather).  ``birth_summary``
         (``inference.birth_map``) and ``complete_summary`` (``inference.birth_complete``, key ``birth_complete``): one more
-        key of the pickle each; ``tempering`` (``inference.tempering``): the image's ``tempering_summary``, key ``tempering``."""
+        key of the pickle each; ``tempering`` (``inference.tempering``): the image's ``tempering_summary``, key ``tempering``;
+        ``recombine`` (``inference.recombine``): the image's ``recombine_summary``, key ``recombine``."""
         pts = list(merged)
         pred_params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
         pred_centers = np.array([[p.x, p.y] for p in pts]).reshape(-1, 2)
@@ -795,6 +840,8 @@ class MPPModel:
             record["birth_complete"] = complete_summary
         if tempering is not None:
             record["tempering"] = tempering
+        if recombine is not None:
+            record["recombine"] = recombine
         with open(out_file, "wb") as f:
             pickle.dump(record, f)
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
@@ -832,6 +879,8 @@ class MPPModel:
         ``NNNN_birth_energy.png``, the key ``birth_summary`` of the pickle and one log line.  ``inference.birth_complete``
         (off): the merged detections are completed from that map first (``complete``): the pickle, the CSV, the figures and the
         birth map are those of the completed list, the pickle has the key ``birth_complete``, and one log line says what was added.
+        ``inference.recombine`` (off, needs ``inference.restarts`` >= 2): every tile returns the best restart per interaction
+        cluster (``check_recombine``); the pickle has the key ``recombine`` and one log line per image says what was taken.
 
         Several ranks (one per GPU): the DATASET is sharded by image -- the reference's own loop is serial over images
         (``mpp_model.py:220``) with a process pool inside each; here rank r takes the r-th block of the images and runs them
@@ -845,6 +894,7 @@ class MPPModel:
         # (an image shared by all ranks refuses the option in ``infer_image``, before its first collective)
         birth_map, complete = check_birth_map(self.config), check_birth_complete(self.config)
         check_tempering(self.config)
+        check_recombine(self.config)
         dataset = self.config["dataset"]["dataset"]
         results_dir = get_inference_path(os.path.split(self.save_path)[1], dataset, subset)
         os.makedirs(results_dir, exist_ok=True)
@@ -889,8 +939,9 @@ class MPPModel:
 
             def flush():
                 res = self.infer_images([b[1] for b in batch], [b[2] for b in batch], image_seeds=[seeds[b[0]] for b in batch])
-                for (k, image_data, region_data), (merged, scores), tempered in zip(batch, res, self.last_tempering):
-                    yield k, image_data, region_data, merged, scores, tempered
+                for (k, image_data, region_data), (merged, scores), tempered, recombined in zip(batch, res, self.last_tempering,
+                                                                                                   self.last_recombine):
+                    yield k, image_data, region_data, merged, scores, tempered, recombined
 
             for k, (image_data, region_data) in stream:
                 patch, anchors = self.tile_layout(tuple(int(v) for v in image_data.shape[:2]))
@@ -903,7 +954,7 @@ class MPPModel:
                 yield from flush()
 
         try:
-            for k, image_data, region_data, merged, scores, tempered in inferred():
+            for k, image_data, region_data, merged, scores, tempered, recombined in inferred():
                 birth = done = None
                 if complete is not None:            # (before the map and the figures: they show the completed list)
                     merged, scores, done = self.complete(region_data, merged)
@@ -912,7 +963,7 @@ class MPPModel:
                     self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
                     del dE
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth,
-                                                   complete_summary=done, tempering=tempered))
+                                                   complete_summary=done, tempering=tempered, recombine=recombined))
                 if figures:
                     self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all

@@ -156,7 +156,8 @@ class TileBatchSampler:
 
     def __init__(self, tiles: Sequence[ImageWMaps], energy_setup, energy_combinator, device: int = 0,
                  point_capacity: int = 1024, spec_waves: Optional[int] = 8, ctx: Optional[MppContext] = None,
-                 use_split_merge: bool = False, keys=None, stacked_maps=None, restarts: int = 1, tempering=None):
+                 use_split_merge: bool = False, keys=None, stacked_maps=None, restarts: int = 1, tempering=None,
+                 recombine: bool = False):
         """``keys`` = (seeds, chain ids), one per tile: the Philox key and chain id each tile's chain uses instead of the
         launch's seed and ``chain0 + tile`` -- tiles of several images in one launch keep the chains they would run in a
         launch of their own image (``mpp_set_chain_keys``).
@@ -172,12 +173,21 @@ class TileBatchSampler:
         a tile starts on rung r of a temperature ladder (its schedule ``ratio ** r`` times hotter) and every K steps
         neighbouring rungs of a tile exchange their schedules by a Metropolis test (``MppContext.run_tempered``).  The
         returned state is chosen as for restarts.  ``run`` keeps ``replica_rung`` [R, n_tiles] (the rungs at the returned
-        state), ``exchange_log`` and ``exchange_rate`` [R - 1].  ``None``: the replicas never interact."""
+        state), ``exchange_log`` and ``exchange_rate`` [R - 1].  ``None``: the replicas never interact.
+
+        ``recombine`` (needs ``restarts`` >= 2): the returned state of a tile is not its winning replica as a whole but, for
+        every interaction cluster of the union of the replicas' points, the replica that spends the least energy there
+        (``MppContext.recombine``) -- in real arithmetic never a higher energy than the winner's.
+        ``replica_energy`` is that of the replicas as sampled, ``replica_winner`` the whole-tile winner (whose chain holds
+        the composite afterwards), ``recombine_report`` the call's records.  Works with ``tempering``."""
         self.use_split_merge = use_split_merge
         self.restarts = int(restarts)
         if self.restarts < 1:
             raise ValueError(f"restarts must be >= 1, got {restarts}")
-        self.replica_energy = self.replica_winner = None
+        self.recombine = bool(recombine)
+        if self.recombine and self.restarts < 2:
+            raise ValueError(f"recombine chooses among the restarts of a tile: it needs restarts >= 2, got {restarts}")
+        self.replica_energy = self.replica_winner = self.recombine_report = None
         self.tempering = resolve_tempering(tempering, self.restarts)
         self.replica_rung = self.exchange_log = self.exchange_rate = None
         shapes = {tuple(t.shape[:2]) for t in tiles}
@@ -297,10 +307,16 @@ class TileBatchSampler:
             if on_device is not None:
                 on_device(self.ctx)
                 return
+            if self.recombine:
+                # (the energies of the replicas as sampled, then the call that rewrites the winners' chains; they are read after it)
+                self.replica_energy = self.ctx.total_energy_all().reshape(R, n)
+                self.recombine_report = self.ctx.recombine()
+                self.replica_winner = self.recombine_report["winner"].astype(np.int64)
             chains = self.ctx.get_points_all()
             if R > 1:
-                self.replica_energy = self.ctx.total_energy_all().reshape(R, n)
-                self.replica_winner = select_replicas(self.replica_energy, n)
+                if not self.recombine:
+                    self.replica_energy = self.ctx.total_energy_all().reshape(R, n)
+                    self.replica_winner = select_replicas(self.replica_energy, n)
                 if self.tempering:
                     self.replica_rung = rungs_after(np.concatenate(self._logs), n, R)
                 chains = [chains[int(r) * n + i] for i, r in enumerate(self.replica_winner)]
@@ -337,18 +353,22 @@ def sample_rjmcmc_batch(tiles: Sequence[ImageWMaps], rng: np.random.Generator, n
                         init_config, init_temperature: float, alpha_t, burn_in: int, energy_setup,
                         samples_interval: int, target_temperature: float, verbose: int = 0, iter_multiplier=None,
                         use_split_merge: bool = False, device: int = 0, spec_waves: int = 8,
-                        point_capacity: int = 1024, chain0: int = 0, restarts: int = 1, tempering=None):
+                        point_capacity: int = 1024, chain0: int = 0, restarts: int = 1, tempering=None,
+                        recombine: bool = False):
     """``sample_rjmcmc`` for many equally-shaped tiles at once; returns one result list per tile.
     ``restarts`` R > 1: R chains per tile, the configuration of the one with the lowest energy is returned.
-    ``tempering``: those chains on a temperature ladder, with exchanges (``TileBatchSampler``)."""
+    ``tempering``: those chains on a temperature ladder, with exchanges (``TileBatchSampler``).
+    ``recombine``: the returned configuration takes every interaction cluster from its best replica (``TileBatchSampler``)."""
     resolve_tempering(tempering, restarts)
+    if recombine and restarts < 2:
+        raise ValueError(f"recombine chooses among the restarts of a tile: it needs restarts >= 2, got {restarts}")
     if restarts > 1 and num_samples > 1:
         raise ValueError("restarts > 1 with num_samples > 1: a winner is defined for one returned state")
     alpha, T_target, total, snaps = resolve_schedule(num_samples, init_temperature, alpha_t, burn_in, samples_interval,
                                                       target_temperature, iter_multiplier)
     sampler = TileBatchSampler(tiles, energy_setup, energy_combinator, device=device, spec_waves=spec_waves,
                                point_capacity=point_capacity, use_split_merge=use_split_merge, restarts=restarts,
-                               tempering=tempering)
+                               tempering=tempering, recombine=recombine)
     sampler.init(init_config)
     seed = int(rng.integers(0, 2 ** 63 - 1))
     start = time.perf_counter()
@@ -366,7 +386,8 @@ def sample_rjmcmc(image_data: ImageWMaps, rng: np.random.Generator, num_samples:
                   use_split_merge: bool = False, **gpu_options):
     """Drop-in for the reference's ``sample_rjmcmc`` (one tile).  Returns ``[points]`` for
     ``num_samples == 1`` and the last ``num_samples`` sampled configurations otherwise.  ``restarts=R`` (among the
-    ``gpu_options``): the lowest-energy result of R independent chains."""
+    ``gpu_options``): the lowest-energy result of R independent chains; with ``recombine=True`` every interaction cluster
+    of the result comes from its best chain."""
     return sample_rjmcmc_batch([image_data], rng, num_samples, energy_combinator, init_config, init_temperature,
                                alpha_t, burn_in, energy_setup, samples_interval, target_temperature, verbose,
                                iter_multiplier, use_split_merge, **gpu_options)[0]
