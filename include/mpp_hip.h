@@ -332,6 +332,64 @@ int mpp_birth_complete(mpp_ctx *ctx, int max_rounds, double min_gain, mpp_comple
 #define MPP_RECOMBINE_LDS_POINTS 2048      /* points of a tile, over all replicas, whose labels fit the LDS */
 typedef struct { int32_t status, winner, n_clusters, n_taken, n_before, n_after; double E_winner, E_sum, E_after; } mpp_recombine_report;
 int mpp_recombine(mpp_ctx *ctx, mpp_recombine_report *report, int32_t *src_or_null);
+/* Local descent (csrc/mpp_descent.hip): greedy deaths and births to a joint fixed point.
+ *
+ * mpp_papangelou_all: dE HOST [n_chains][point_capacity]; dE[c][s] = mpp_papangelou(ctx, c)[s] bit for bit for s < n_c and 0.0
+ * behind n_c.  The launches of mpp_merge_score's scoring (the candidate grids when point_capacity reaches
+ * "scratch_grid_min_points" -- with or without them the bits are the same --, then the Papangelou kernel over every chain) and
+ * one copy back.  Refuses what mpp_total_energy_all refuses.
+ *
+ * mpp_select_points: the descent's selection on a caller's list of n points; xy_dev [n][2] int32, values_dev [n] float64 and
+ * keep_dev [n] uint8 are DEVICE pointers, n_candidates / n_kept HOST (either may be NULL); the ctx's stream, synchronous.
+ *  - candidates: the points with values[i] > above.  A NaN never is one, +inf is;
+ *  - key: key(i) = (-values[i], i): the larger value wins, equal values tie toward the smaller slot;
+ *  - kept: a candidate is kept iff no OTHER candidate j with (double)(dx*dx + dy*dy) <= distance * distance (dx, dy 64-bit
+ *    integers) has a smaller key.  Two points on one pixel are rivals.  Order-free as mpp_select_minima: a candidate that loses
+ *    to a loser is dropped for this round;
+ *  - keep[i] = 1 or 0 for every i < n.
+ * -1: distance < 0, a non-finite distance or above, n < 0.
+ *
+ * mpp_descend: every chain of the ctx on its own, from the state mpp_get_points_all reads.  what: MPP_DESCEND_DEATHS,
+ * MPP_DESCEND_BIRTHS or both.  A round:
+ *   death half (bit 1)  p(v) = E(X) - E(X - v) of every point of the current state, the values of mpp_papangelou; the selection
+ *                       above with above = min_gain and distance = 2 * max_inter; the kept points are REMOVED by stable
+ *                       compaction (the survivors keep their relative slot order).  The chain is then in the state
+ *                       mpp_set_points(survivors in slot order) leaves.  Two points removed in one round neither interact nor
+ *                       share a neighbour, so in real arithmetic the half lowers the energy by exactly the sum of its p;
+ *   birth half (bit 2)  one round of mpp_birth_complete on the state the death half left: the map, mpp_select_minima with
+ *                       below = -min_gain and distance = 2 * max_inter, the append in ascending row-major order.
+ * status 0: a whole round changed nothing -- a joint fixed point for min_gain; 1: max_rounds (1..1024) rounds have changed the
+ * chain; 2: a birth half does not fit point_capacity -- nothing of that half is appended and the chain closes, what its death
+ * half removed stays removed and counted (the round counts when it removed something); the other chains go on.  A closed
+ * chain is not touched again.
+ * report [n_chains] HOST: rounds = the rounds that changed the chain; n_added, n_removed, n_after; gain_births = the sum of the
+ * appended dE, gain_deaths = the sum of the removed p, each a float64 from 0.0 to which the values are added one after another,
+ * round by round and in slot order within a round.  Of the RETURNED state: max_p the largest non-NaN p and slot_max the first
+ * slot that has it ((-inf, -1) for an empty chain or when every p is NaN), n_positive the count of p > 0, and -- when bit 2 is
+ * set -- the mpp_birth_summary fields min_dE, x, y, n_negative, n_nan (without bit 2 no map is computed: 0.0, -1, -1, 0, 0).
+ * After status 1 or 2 one more Papangelou pass, after status 1 one more map is computed for these fields.
+ * src_or_null HOST [n_chains][point_capacity] int32: for every final slot the slot the point had when the call began, -1 for a
+ * born point and behind n_after.
+ * With what = MPP_DESCEND_BIRTHS the chain state and every shared report field equal those of mpp_birth_complete bit for bit.
+ * Per round a fixed number of launches and one copy of n_chains reports; no point list and no map crosses to the host.
+ * -1 with a message: what outside 1..3; max_rounds outside 1..1024; min_gain negative or not finite; a pair reduction that is
+ * neither max nor min; more than 65535 chains; no maps or no model; with bit 2 a classic image energy (deaths alone are
+ * allowed: the unit terms are per point).
+ * The map's dE(c) and the from-scratch p of the same point are one real number in two summation orders: with min_gain = 0 a
+ * point within rounding of 0 could be born and removed in turn; max_rounds ends that with status 1, a min_gain above the
+ * rounding bound excludes it. */
+#define MPP_DESCEND_DEATHS 1
+#define MPP_DESCEND_BIRTHS 2
+typedef struct {
+  int32_t status, rounds, n_added, n_removed, n_after, slot_max;
+  double gain_births, gain_deaths, max_p, min_dE;
+  int32_t x, y;
+  int64_t n_positive, n_negative, n_nan;
+} mpp_descent_report;
+int mpp_papangelou_all(mpp_ctx *ctx, double *dE);
+int mpp_select_points(mpp_ctx *ctx, int n, const int32_t *xy_dev, const double *values_dev, double above, double distance,
+                      uint8_t *keep_dev, int64_t *n_candidates, int64_t *n_kept);
+int mpp_descend(mpp_ctx *ctx, int what, int max_rounds, double min_gain, mpp_descent_report *report, int32_t *src_or_null);
 /* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points.  Candidates are
  * det >= (float)threshold (float32, as NumPy compares); rank and NMS rule as mpp_detect_centers below.  A tile that keeps more
  * than point_capacity points: -12 ("naive init, tile t"), its first point_capacity picks stay stored; every call replaces

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Command-line entry, same flags as the reference's ``main.py:11-109``:
 
-    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map] [--birth-complete]
+    python main.py -p infer -m mpp -c mpp_hrcM [-d DATASET] [-o] [--figures] [--birth-map] [--birth-complete] [--descent]
                    [--restarts R [--tempering [RATIO]] [--recombine]]
-    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map] [--birth-complete]
+    python main.py -p detect -m mpp -c mpp_hrcM --images PATH [PATH ...] --out DIR [--gsd G] [--figures] [--birth-map] [--birth-complete] [--descent]
 
 ``-m mpp`` runs the MI355X sampler; ``-m posnet`` / ``-m shapenet`` with ``-p infer`` write the score-map
 hand-off pickles the reference's MPP stage reads (``NNNN_results.pkl``) and the CNN-only baseline's detections (DOTA hbb /
@@ -88,6 +88,11 @@ def build_parser():
                              "births at the map's local minima, round after round, until no new object lowers the energy; the "
                              "results are those of the completed list, the pickle gains the key birth_complete and one line is "
                              "logged; same as inference.birth_complete in the config (whose max_rounds / min_gain it keeps)")
+    parser.add_argument("--descent", action="store_true",
+                        help="(-m mpp, infer / infereval / detect) local descent of every image's detections: rounds of greedy "
+                             "deaths (objects whose removal lowers the energy) and of the births of --birth-complete, until a whole "
+                             "round changes nothing; the results are those of the descended list, the pickle gains the key descent "
+                             "and one line is logged; same as inference.descent in the config (whose parameters it keeps)")
     parser.add_argument("--images", nargs="+", default=None, metavar="PATH",
                         help="(-p detect) image files, or directories whose image files are taken in sorted order")
     parser.add_argument("--out", default=None, metavar="DIR", help="(-p detect) where the results go")
@@ -105,6 +110,15 @@ def apply_birth_complete(args, config):
         inference = config.setdefault("inference", {})
         if not isinstance(inference.get("birth_complete"), dict):
             inference["birth_complete"] = True
+    return config
+
+
+def apply_descent(args, config):
+    """--descent turns inference.descent on; parameters the config gives for it stay"""
+    if args.descent and args.procedure in ("infer", "infereval", "detect"):
+        inference = config.setdefault("inference", {})
+        if not isinstance(inference.get("descent"), dict):
+            inference["descent"] = True
     return config
 
 
@@ -161,6 +175,7 @@ def main():
         if args.birth_map:
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
+        apply_descent(args, config)
         apply_tempering(args, config)
         apply_recombine(args, config)
         model = MPPModel(config, phase="val", load=True, device=local_rank,
@@ -179,6 +194,7 @@ def main():
         if args.birth_map and args.procedure in ("infer", "infereval"):
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
+        apply_descent(args, config)
         apply_tempering(args, config)
         apply_recombine(args, config)
         nets = None

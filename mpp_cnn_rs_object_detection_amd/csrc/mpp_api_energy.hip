@@ -286,6 +286,144 @@ extern "C" int mpp_birth_complete(mpp_ctx *c, int max_rounds, double min_gain, m
   return 0;
 }
 
+// ---- the local descent (mpp_descent.hip) -------------------------------------------------------------------
+// Does the Papangelou pass of every chain take its neighbours from candidate grids?  As chain_energy_launches decides it: when
+// a chain could reach scratch_grid_min_points.  k_papangelou_tiles has no threshold per chain, so then every chain uses its
+// grid; the values are the same bits either way.
+static int descent_ncell(const mpp_ctx *c) {
+  const int ncell = c->hp.nx * c->hp.ny;
+  return c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points ? ncell : 0;
+}
+// The launches of mpp_merge_score's scoring for every chain, into d.p; the counts stay on the device (a block per slot of the
+// capacity: the blocks behind a chain's count return at once).
+static int papangelou_launches(mpp_ctx *c, const Descent &d, int ncell) {
+  const int T = c->n_tiles;
+  if (ncell > 0) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, d.gs, d.gc, d.gi);
+  mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, c->cap, c->cap, d.p, d.gs, d.gi, ncell + 1, c->cap);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+extern "C" int mpp_papangelou_all(mpp_ctx *c, double *dE) {
+  if (!c || !dE) return fail(c, -1, "bad papangelou_all arguments");
+  int rc = push_state(c);
+  if (rc) return rc;
+  const int T = c->n_tiles, ncell = descent_ncell(c);
+  if (T > 65535) return fail(c, -1, "papangelou_all: %d chains, at most 65535", T);
+  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, 0, ncell)) != hipSuccess)
+    return fail(c, -2, "no device memory for the Papangelou values of %d chains", T);
+  Descent d;
+  mpp_descent_plan(&d, T, c->cap, 0, ncell, c->descent_ws.p);
+  const size_t bytes = (size_t)T * c->cap * sizeof(double);
+  HIPCHK(c, hipMemsetAsync(d.p, 0, bytes, c->stream));           // (the kernel writes the slots below a chain's count only)
+  if ((rc = papangelou_launches(c, d, ncell))) return rc;
+  hipError_t e = hipMemcpyAsync(dE, d.p, bytes, hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
+extern "C" int mpp_select_points(mpp_ctx *c, int n, const int32_t *xy, const double *values, double above, double distance,
+                                 uint8_t *keep, int64_t *n_candidates, int64_t *n_kept) {
+  if (!c) return -1;
+  if (n < 0 || (n > 0 && (!xy || !values || !keep)) || !(distance >= 0.0) || !std::isfinite(distance) || !std::isfinite(above))
+    return fail(c, -1, "bad select_points arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  int32_t count[2] = {0, 0};
+  if (n > 0) {
+    if (c->ptsel_ws.reserve(c->stream, sizeof count) != hipSuccess) return fail(c, -2, "no device memory for select_points");
+    PtSel s{};
+    s.n_chains = 1; s.x = xy; s.y = xy + 1; s.stride = 2; s.n = n; s.val = values; s.keep = keep;
+    s.above = above; s.d2 = distance * distance; s.count = (int32_t *)c->ptsel_ws.p;
+    HIPCHK(c, hipMemsetAsync(s.count, 0, sizeof count, c->stream));
+    mpp_launch_ptsel(c->stream, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(count, s.count, sizeof count, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e2);
+  }
+  if (n_candidates) *n_candidates = count[0];
+  if (n_kept) *n_kept = count[1];
+  return 0;
+}
+
+// Per round: the launches of the Papangelou pass, of the selection among points and of the removal; those of one round of the
+// completion; the round's book; one copy of the chains' reports.  The point lists and the maps stay on the device.
+extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain, mpp_descent_report *report, int32_t *src) {
+  if (!c) return -1;
+  if (what < 1 || what > 3) return fail(c, -1, "descend: what %d, must be 1 (deaths), 2 (births) or 3 (both)", what);
+  const bool deaths = what & MPP_DESCEND_DEATHS, births = what & MPP_DESCEND_BIRTHS;
+  int rc = 0;
+  if (births) { if ((rc = birth_refusals(c, "descend"))) return rc; }
+  else if (!c->have_maps || !c->have_model) return fail(c, -1, "descend: mpp_set_maps / mpp_set_model have not been called");
+  if (!report) return fail(c, -1, "descend: report is NULL");
+  if (max_rounds < 1 || max_rounds > 1024) return fail(c, -1, "descend: max_rounds %d, must be 1..1024", max_rounds);
+  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(c, -1, "descend: min_gain must be finite and >= 0");
+  for (int p = 0; p < c->hp.model.n_pair; ++p)                   // (a round's gains add up only under an order-free reduction)
+    if (c->hp.model.pair[p].reduce != MPP_REDUCE_MAX && c->hp.model.pair[p].reduce != MPP_REDUCE_MIN)
+      return fail(c, -1, "descend: pair term %d has a reduction that is neither max nor min", p);
+  const int T = c->n_tiles, H = c->H, W = c->W;
+  if (T > 65535) return fail(c, -1, "descend: %d chains, at most 65535", T);
+  if ((rc = push_state(c))) return rc;
+  const size_t hw = births ? (size_t)H * W : 0;
+  const int ncell = descent_ncell(c);
+  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, hw, ncell)) != hipSuccess)
+    return fail(c, -2, "no device memory for the descent of %d chains", T);
+  Descent d;
+  mpp_descent_plan(&d, T, c->cap, hw, ncell, c->descent_ws.p);
+  const double reach = 2.0 * c->hp.max_inter;
+  MinSel s{};
+  if (births && (rc = minsel_setup(c, &s, d.dE, hw, T, H, W, W, -min_gain, reach, d.crep))) return rc;
+  PtSel ps{};
+  ps.tiles = c->d_tiles; ps.n_chains = T; ps.cap = c->cap; ps.val = d.p; ps.keep = d.keep; ps.pitch = (size_t)c->cap;
+  ps.above = min_gain; ps.d2 = reach * reach; ps.closed = d.crep;
+  mpp_launch_complete_init(c->stream, T, d.crep);
+  mpp_launch_descent_init(c->stream, c->d_tiles, d);
+  BirthPart *part = nullptr;
+  mpp_birth_summary *d_sum = nullptr;
+  bool open = true, stale_p = !deaths, stale_map = false;
+  std::vector<int32_t> was(T, -1);
+  // (a chain is open for at most max_rounds rounds that change it and the one that closes it)
+  for (int round = 0; round <= max_rounds && open; ++round) {
+    if (deaths) {
+      if ((rc = papangelou_launches(c, d, ncell))) return rc;
+      mpp_launch_ptsel(c->stream, ps);
+      mpp_launch_descent_remove(c->stream, c->d_tiles, d);
+    }
+    if (births) {
+      if ((rc = birth_map_launches(c, "descend", d.dE, nullptr, &part, &d_sum))) return rc;
+      mpp_launch_minsel(c->stream, s);
+      mpp_launch_complete_round(c->stream, s, c->dp, c->d_tiles, c->cap, d.gain_val, 1 << 30, d.crep);
+    }
+    mpp_launch_descent_round(c->stream, c->d_tiles, d, what, max_rounds);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(report, d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e2);
+    open = false;
+    for (int t = 0; t < T; ++t) {
+      const int st = report[t].status;
+      open = open || st < 0;
+      // a chain that changed in the round that closed it: its last Papangelou values (its last map) are not its state's
+      if (was[t] < 0 && st > 0) { stale_p = true; stale_map = stale_map || st == 1; }
+      was[t] = st;
+    }
+  }
+  if (open) return fail(c, -9, "descend: a chain is still open after %d rounds", max_rounds + 1);
+  if (stale_p && (rc = papangelou_launches(c, d, ncell))) return rc;
+  if (births) {
+    if (stale_map && (rc = birth_map_launches(c, "descend", d.dE, nullptr, &part, &d_sum))) return rc;
+    mpp_launch_birth_summary(c->stream, T, H, W, d.dE, part, d_sum);
+  }
+  mpp_launch_descent_summary(c->stream, c->d_tiles, d, births ? d_sum : nullptr);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(report, d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && src) e = hipMemcpyAsync(src, d.src, (size_t)T * c->cap * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
 // shared body of mpp_delta_batch (dE != NULL) and mpp_delta_vectors (before/after/mask != NULL)
 static int delta_cases(mpp_ctx *c, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
                        const int32_t *add_off, const int32_t *add_xy, const double *add_marks, double *dE, int stride,

@@ -141,6 +141,8 @@ struct mpp_ctx : TileMem {
   DevWs minsel_ws;                   // mpp_select_minima / mpp_birth_complete: the candidate list and its tables
   DevWs complete_ws;                 // mpp_birth_complete: every chain's map, the appended values, the reports
   DevWs recombine_ws;                // mpp_recombine: the tiles' labels and cluster choices, the staged composites, the reports
+  DevWs descent_ws;                  // mpp_descend / mpp_papangelou_all: the Papangelou values, the grids, the round's lists, the reports
+  DevWs ptsel_ws;                    // mpp_select_points: its two counters
   int recombine_lds = MPP_RECOMBINE_LDS_POINTS;   // ... a tile of more points over its replicas labels in the workspace, not in LDS
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)

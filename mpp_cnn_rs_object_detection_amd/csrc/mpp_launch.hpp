@@ -166,6 +166,37 @@ void mpp_recombine_plan(Recomb *rc, int n, int R, int cap, void *ws);
 void mpp_launch_recombine(hipStream_t st, const DevParams *P, const TileRef *tiles, const Recomb &rc, const double *e_pts,
                           const double *e_sum, int lds_points);
 void mpp_launch_recombine_after(hipStream_t st, const Recomb &rc, const double *e_sum);
+// the local descent (mpp_descent.hip), all device.  PtSel: one selection among points -- of the chains of `tiles` (their
+// values and keep bytes `pitch` entries apart; a chain whose closed[] status is >= 0 has no candidates), or, tiles == nullptr,
+// of one list of n points at x[i * stride], y[i * stride]; count: nullptr or two zeroed ints, candidates and kept.
+struct PtSel {
+  const TileRef *tiles; int n_chains, cap;
+  const int32_t *x, *y; int stride, n;
+  const double *val; uint8_t *keep; size_t pitch;
+  double above, d2;
+  const mpp_complete_report *closed;
+  int32_t *count;
+};
+// The workspace of one mpp_descend, placed by mpp_descent_plan in mpp_descent_bytes bytes (hw: the pixels of a map, 0 without
+// births; ncell: the cells of a candidate grid, 0 without grids).
+struct Descent {
+  int n_chains, cap;
+  double *p, *rem_val, *gain_val;                  // [n_chains][cap]: Papangelou values; the removed p and the appended dE of a round by place
+  double *dE;                                      // [n_chains][hw] the maps
+  mpp_descent_report *rep;                         // [n_chains]
+  mpp_complete_report *crep;                       // [n_chains] the birth half's book (the completion's); status >= 0: the chain is closed
+  int32_t *src, *gi;                               // [n_chains][cap]: where a slot's point started; the grids' items
+  int32_t *gs, *gc;                                // [n_chains][ncell + 1], [n_chains][ncell]
+  int32_t *n_rem;                                  // [n_chains] points the round's death half removed
+  uint8_t *keep;                                   // [n_chains][cap] the selection's answer: 1 = remove
+};
+size_t mpp_descent_bytes(int n_chains, int cap, size_t hw, int ncell);
+void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, int ncell, void *ws);
+void mpp_launch_ptsel(hipStream_t st, const PtSel &s);
+void mpp_launch_descent_init(hipStream_t st, const TileRef *tiles, const Descent &d);
+void mpp_launch_descent_remove(hipStream_t st, const TileRef *tiles, const Descent &d);
+void mpp_launch_descent_round(hipStream_t st, const TileRef *tiles, const Descent &d, int what, int max_rounds);
+void mpp_launch_descent_summary(hipStream_t st, const TileRef *tiles, const Descent &d, const mpp_birth_summary *sum_or_null);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);

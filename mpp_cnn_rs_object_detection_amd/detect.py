@@ -8,7 +8,9 @@ device), and the detections are mapped back to the pixels of the file.  Per imag
 with ``figures``, ``<stem>_detection.png`` drawn on the picture the model saw.  With ``inference.birth_map`` of the model's
 config (``--birth-map``) also ``<stem>_birth_energy.png`` and the key ``birth_summary`` of the pickle (``MPPModel.birth_map``).
 With ``inference.birth_complete`` (``--birth-complete``) the detections are completed from the birth-energy map first
-(``MPPModel.complete``): every file shows the completed list and the pickle has the key ``birth_complete``.
+(``MPPModel.complete``): every file shows the completed list and the pickle has the key ``birth_complete``.  With
+``inference.descent`` (``--descent``) they go through the local descent (``MPPModel.descend``): every file shows the descended
+list and the pickle has the key ``descent``.
 """
 from __future__ import annotations
 
@@ -74,6 +76,7 @@ class DetectResult:
     source_shape: Tuple[int, int]
     birth: Any = None                 # ``inference.birth_map``: (dE [h,w] float64 device tensor, summary dict) of ``MPPModel.birth_map``
     complete: Any = None              # ``inference.birth_complete``: the summary dict of ``MPPModel.complete`` (``detections`` are completed)
+    descent: Any = None               # ``inference.descent``: the summary dict of ``MPPModel.descend`` (``detections`` are descended)
     tempering: Any = None             # ``inference.tempering``: ``last_run["tempering"]`` (exchange rates, the winners' rungs)
     recombine: Any = None             # ``inference.recombine``: ``last_run["recombine"]`` (per tile: status, clusters, energies)
 
@@ -116,10 +119,11 @@ def detect_image(model, rgb_uint8: np.ndarray, gsd: Optional[float] = None, mode
     data = ImageWMaps(name=name, shape=tuple(image.shape[:2]), image=image, detection_map=None, param_dist_maps=None,
                       mappings=default_mappings(),
                       param_names=Rectangle.PARAMETERS, labels=None, gt_config=[])
-    model.last_birth = model.last_complete = None
+    model.last_birth = model.last_complete = model.last_descent = None
     detections, scores = model.infer_image(data, seed=seed)
     return DetectResult(detections=detections, scores=np.asarray(scores, dtype=np.float64), image=image, scale=scale,
                         source_shape=(H, W), birth=getattr(model, "last_birth", None), complete=getattr(model, "last_complete", None),
+                        descent=getattr(model, "last_descent", None),
                         tempering=(getattr(model, "last_run", None) or {}).get("tempering"),
                         recombine=(getattr(model, "last_run", None) or {}).get("recombine"))
 
@@ -143,6 +147,8 @@ def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Opti
         record["birth_summary"] = result.birth[1]
     if result.complete is not None:
         record["birth_complete"] = result.complete
+    if result.descent is not None:
+        record["descent"] = result.descent
     if result.tempering is not None:
         record["tempering"] = result.tempering
     if result.recombine is not None:

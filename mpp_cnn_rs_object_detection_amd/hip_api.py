@@ -98,6 +98,13 @@ RECOMBINE_REPORT_DTYPE = np.dtype([("status", "<i4"), ("winner", "<i4"), ("n_clu
                                    ("n_after", "<i4"), ("E_winner", "<f8"), ("E_sum", "<f8"), ("E_after", "<f8")], align=True)
 RECOMBINE_UNCHANGED, RECOMBINE_DONE, RECOMBINE_CAPACITY = 0, 1, 2
 RECOMBINE_LDS_POINTS = 2048
+#: mpp_descent_report, one per chain (``MppContext.descend``); status: 0 joint fixed point, 1 round limit, 2 capacity
+DESCENT_REPORT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_added", "<i4"), ("n_removed", "<i4"), ("n_after", "<i4"),
+                                 ("slot_max", "<i4"), ("gain_births", "<f8"), ("gain_deaths", "<f8"), ("max_p", "<f8"),
+                                 ("min_dE", "<f8"), ("x", "<i4"), ("y", "<i4"), ("n_positive", "<i8"), ("n_negative", "<i8"),
+                                 ("n_nan", "<i8")], align=True)
+DESCEND_DEATHS, DESCEND_BIRTHS = 1, 2
+DESCENT_FIXED_POINT, DESCENT_ROUND_LIMIT, DESCENT_CAPACITY = 0, 1, 2
 #: mpp_exchange_record, one per attempted exchange of ``MppContext.run_tempered``: the values as read before the swap
 EXCHANGE_RECORD_DTYPE = np.dtype([("step", "<i8"), ("tile", "<i4"), ("k", "<i4"), ("chain_a", "<i4"), ("chain_b", "<i4"),
                                   ("accepted", "<i4"), ("_pad", "<i4"), ("Ea", "<f8"), ("Eb", "<f8"), ("Ta", "<f8"),
@@ -136,6 +143,9 @@ PROTOTYPES = {
     "mpp_select_minima": (_i32, [_vp, _i32, _i32, _i32, _vp, _dbl, _dbl, _i32, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mpp_birth_complete": (_i32, [_vp, _i32, _dbl, _vp]),
     "mpp_recombine": (_i32, [_vp, _vp, _vp]),
+    "mpp_papangelou_all": (_i32, [_vp, _vp]),
+    "mpp_select_points": (_i32, [_vp, _i32, _vp, _vp, _dbl, _dbl, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mpp_descend": (_i32, [_vp, _i32, _i32, _dbl, _vp, _vp]),
     "mpp_conv3x3_c32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpp_conv3x3_stem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mpp_merge_score": (_i32, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -592,6 +602,51 @@ class MppContext:
         rep = np.zeros(max(self.get_option("n_chains"), 1), COMPLETE_REPORT_DTYPE)
         self._check(self._L.mpp_birth_complete(self._h, int(max_rounds), float(min_gain), _ptr(rep)))
         return rep[:self.get_option("n_chains")]
+
+    def papangelou_all(self) -> np.ndarray:
+        """``papangelou(t)`` of every chain of the context, bit for bit, with one device read (``mpp_papangelou_all``): float64
+        ``[n_chains, point_capacity]``, row c the values of chain c's points in slot order, 0.0 behind its count"""
+        d = np.zeros((max(self.get_option("n_chains"), 1), self.get_option("point_capacity")), np.float64)
+        self._check(self._L.mpp_papangelou_all(self._h, _ptr(d)))
+        return d[:self.get_option("n_chains")]
+
+    def select_points(self, xy, values, above: float, distance: float):
+        """``mpp_select_points``: the descent's selection on a list of points -- the candidates ``values > above`` that no
+        other candidate within ``distance`` beats on the key (-value, slot).  ``xy`` [n,2] int32 and ``values`` [n] float64:
+        arrays, or contiguous CUDA tensors on the ctx's GPU.  Returns ``(keep, n_candidates, n_kept)``, keep a uint8 tensor
+        [n] on the device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def on_device(name, a, dtype, shape):
+            t = a if _is_torch(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=dtype).reshape(shape)).to(dev)
+            if not (t.is_cuda and t.device.index == self.device and t.dtype == getattr(torch, np.dtype(dtype).name)
+                    and t.is_contiguous() and t.dim() == len(shape) and (len(shape) == 1 or t.shape[1] == 2)):
+                raise ValueError(f"select_points: {name} must be a contiguous {np.dtype(dtype).name} tensor on GPU {self.device}")
+            return t
+        xy, values = on_device("xy", xy, np.int32, (-1, 2)), on_device("values", values, np.float64, (-1,))
+        if xy.shape[0] != values.shape[0]:
+            raise ValueError("select_points: one value per point")
+        n = int(values.shape[0])
+        keep = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        nc, nk = C.c_int64(), C.c_int64()
+        self._check(self._L.mpp_select_points(self._h, n, _ptr(xy), _ptr(values), float(above), float(distance), _ptr(keep),
+                                              C.byref(nc), C.byref(nk)))
+        return keep, int(nc.value), int(nk.value)
+
+    def descend(self, what: int = 3, max_rounds: int = 16, min_gain: float = 0.0, src: bool = False):
+        """``mpp_descend``: every chain of the context alternates death rounds -- the points whose removal lowers the energy
+        by more than ``min_gain``, no two within twice the model's interaction range, leave by stable compaction -- and birth
+        rounds (one round of :meth:`birth_complete`) until a whole round changes nothing, ``max_rounds`` rounds have changed
+        the chain, or a birth round does not fit ``point_capacity``.  ``what``: ``DESCEND_DEATHS``, ``DESCEND_BIRTHS`` or
+        both.  Returns one record of ``DESCENT_REPORT_DTYPE`` per chain; with ``src`` also int32 ``[n_chains,
+        point_capacity]``: the slot every final slot's point had when the call began, -1 for a born point and behind the count."""
+        T = self.get_option("n_chains")
+        rep = np.zeros(max(T, 1), DESCENT_REPORT_DTYPE)
+        where = np.full((max(T, 1), self.get_option("point_capacity")), -1, np.int32) if src else None
+        self._check(self._L.mpp_descend(self._h, int(what), int(max_rounds), float(min_gain), _ptr(rep), _ptr(where)))
+        return (rep[:T], where[:T]) if src else rep[:T]
 
     # -- the chain -----------------------------------------------------------------------------
     def merge_score(self, distance: float):

@@ -266,6 +266,50 @@ def format_complete_summary(summary: Dict) -> str:
             f"{summary['n_negative']} pixel(s) still below 0")
 
 
+def check_descent(config: Dict, world_size: int = 1) -> Optional[Dict]:
+    """``inference.descent`` of a config (default off): local descent of every image's merged detections -- greedy deaths
+    and births to a joint fixed point (``MPPModel.descend``).  ``true``, or ``{"max_rounds": .., "min_gain": .., "births": ..,
+    "deaths": ..}`` (any key may be left out: 16 rounds, gain 0, both parts).  Returns the four parameters as a dict, or None
+    when it is off.  The descent contains the completion, so ``inference.birth_complete`` on at the same time is refused;
+    like the completion it runs on ONE context that holds the whole image, so ranks that share one image refuse it."""
+    v = (config.get("inference") or {}).get("descent", False)
+    if isinstance(v, (bool, np.bool_)):
+        params = {} if v else None
+    elif isinstance(v, dict):
+        unknown = sorted(set(v) - {"max_rounds", "min_gain", "births", "deaths"})
+        if unknown:
+            raise ValueError(f"inference.descent: unknown key(s) {unknown}; it takes max_rounds, min_gain, births and deaths")
+        params = dict(v)
+    else:
+        raise ValueError(f"inference.descent must be true, false or a dict of max_rounds / min_gain / births / deaths, got {v!r}")
+    if params is None:
+        return None
+    r, g = params.get("max_rounds", 16), params.get("min_gain", 0.0)
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= 1024:
+        raise ValueError(f"inference.descent.max_rounds must be an integer in 1..1024, got {r!r}")
+    if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not np.isfinite(g) or g < 0:
+        raise ValueError(f"inference.descent.min_gain must be a finite number >= 0, got {g!r}")
+    parts = {}
+    for k in ("births", "deaths"):
+        parts[k] = params.get(k, True)
+        if not isinstance(parts[k], (bool, np.bool_)):
+            raise ValueError(f"inference.descent.{k} must be true or false, got {parts[k]!r}")
+    if not parts["births"] and not parts["deaths"]:
+        raise ValueError("inference.descent: births and deaths are both false (set inference.descent to false)")
+    if check_birth_complete(config) is not None:
+        raise ValueError("inference.descent contains the completion: set inference.birth_complete to false")
+    if world_size > 1:
+        raise ValueError(f"inference.descent needs an image held by one GPU; {world_size} ranks share this one "
+                         f"(set inference.descent to false)")
+    return {"max_rounds": int(r), "min_gain": float(g), "births": bool(parts["births"]), "deaths": bool(parts["deaths"])}
+
+
+def format_descent_summary(summary: Dict) -> str:
+    """the log line of one image's descent"""
+    return (f"descent: +{summary['n_added']} -{summary['n_removed']} object(s) in {summary['rounds']} round(s), "
+            f"energy -{abs(summary['gain']):.2f}, {summary['n_negative']} pixel(s) below 0, {summary['n_positive']} point(s) above 0")
+
+
 def format_birth_summary(summary: Dict) -> str:
     """the log line of one image's birth map"""
     return (f"birth map: min dE {summary['min_dE']:.2f} at ({summary['argmin'][0]}, {summary['argmin'][1]}), "
@@ -451,16 +495,38 @@ class MPPModel:
         check_tempering(self.config, world_size)
         check_recombine(self.config, world_size)
         birth_map, complete = check_birth_map(self.config, world_size), check_birth_complete(self.config, world_size)
-        if not birth_map and complete is None:
+        descent = check_descent(self.config, world_size)
+        if not birth_map and complete is None and descent is None:
             return self._infer_image(image_data, rank, world_size, region_data, seed)
         if region_data is None:
             region_data = self.region_maps(image_data, rank, world_size)
         merged, scores = self._infer_image(image_data, rank, world_size, region_data, seed)
         if complete is not None:
             merged, scores, self.last_complete = self.complete(region_data, merged)
+        if descent is not None:
+            merged, scores, self.last_descent = self.descend(region_data, merged)
         if birth_map:
             self.last_birth = self.birth_map(region_data, merged)
         return merged, scores
+
+    def descend(self, region_data: ImageWMaps, merged):
+        """Local descent of one image's detections (``inference.descent``, ``EPointsSet.descend``): one context with the
+        image as its single tile and ``merged`` as its configuration, as ``complete`` builds it.  Returns (descended, scores,
+        summary): the ``EPointsSet`` of the surviving detections in their order followed by the born ``Rectangle``s, the final
+        Papangelou scores of EVERY point of it (``papangelou_all``), summary = the dict of ``EPointsSet.descend`` without
+        ``n_after``; logs one line."""
+        pts = list(merged)
+        p = check_descent(self.config) or {"max_rounds": 16, "min_gain": 0.0, "births": True, "deaths": True}
+        unit, pair = self.energy_setup.make_energies(region_data)
+        agg = EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
+                         device=self.device, point_capacity=max(1024, 2 * len(pts) + 64))
+        r = agg.descend(energy_combinator=self.energy_model, births=p["births"], deaths=p["deaths"], max_rounds=p["max_rounds"],
+                        min_gain=p["min_gain"])
+        scores = agg.papangelou_all(energy_combinator=self.energy_model) if len(agg) else np.zeros(0)
+        summary = {k: r[k] for k in ("n_added", "n_removed", "rounds", "gain", "gain_births", "gain_deaths", "status", "max_p",
+                                     "slot_max", "n_positive", "min_dE", "argmin", "n_negative", "n_nan")}
+        logging.info(format_descent_summary(summary))
+        return agg, scores, summary
 
     def complete(self, region_data: ImageWMaps, merged):
         """Greedy completion of one image's detections (``inference.birth_complete``, ``EPointsSet.birth_complete``): one
@@ -812,12 +878,13 @@ class MPPModel:
     TILE_SHARD_MIN = 2048
 
     def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None,
-                       complete_summary=None, tempering=None, recombine=None) -> dict:
+                       complete_summary=None, tempering=None, recombine=None, descent=None) -> dict:
         """Write ``NNNN_results.pkl`` of one image (mpp_model.py:333-366) and return what the two DOTA translators need
         of it (plain arrays: the records of all ranks travel to rank 0 in one gather).  ``birth_summary``
         (``inference.birth_map``) and ``complete_summary`` (``inference.birth_complete``, key ``birth_complete``): one more
         key of the pickle each; ``tempering`` (``inference.tempering``): the image's ``tempering_summary``, key ``tempering``;
-        ``recombine`` (``inference.recombine``): the image's ``recombine_summary``, key ``recombine``."""
+        ``recombine`` (``inference.recombine``): the image's ``recombine_summary``, key ``recombine``; ``descent``
+        (``inference.descent``): the summary of ``descend``, key ``descent``."""
         pts = list(merged)
         pred_params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
         pred_centers = np.array([[p.x, p.y] for p in pts]).reshape(-1, 2)
@@ -842,6 +909,8 @@ class MPPModel:
             record["tempering"] = tempering
         if recombine is not None:
             record["recombine"] = recombine
+        if descent is not None:
+            record["descent"] = descent
         with open(out_file, "wb") as f:
             pickle.dump(record, f)
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
@@ -879,6 +948,8 @@ class MPPModel:
         ``NNNN_birth_energy.png``, the key ``birth_summary`` of the pickle and one log line.  ``inference.birth_complete``
         (off): the merged detections are completed from that map first (``complete``): the pickle, the CSV, the figures and the
         birth map are those of the completed list, the pickle has the key ``birth_complete``, and one log line says what was added.
+        ``inference.descent`` (off): the merged detections go through the local descent instead (``descend``: deaths and births
+        to a joint fixed point); the files are those of the descended list, the pickle has the key ``descent``, one log line.
         ``inference.recombine`` (off, needs ``inference.restarts`` >= 2): every tile returns the best restart per interaction
         cluster (``check_recombine``); the pickle has the key ``recombine`` and one log line per image says what was taken.
 
@@ -893,6 +964,7 @@ class MPPModel:
             figures = bool(self.config["inference"].get("figures", False))
         # (an image shared by all ranks refuses the option in ``infer_image``, before its first collective)
         birth_map, complete = check_birth_map(self.config), check_birth_complete(self.config)
+        descent = check_descent(self.config)
         check_tempering(self.config)
         check_recombine(self.config)
         dataset = self.config["dataset"]["dataset"]
@@ -955,15 +1027,18 @@ class MPPModel:
 
         try:
             for k, image_data, region_data, merged, scores, tempered, recombined in inferred():
-                birth = done = None
+                birth = done = descended = None
                 if complete is not None:            # (before the map and the figures: they show the completed list)
                     merged, scores, done = self.complete(region_data, merged)
+                if descent is not None:             # (the same place: the files show the descended list)
+                    merged, scores, descended = self.descend(region_data, merged)
                 if birth_map:                       # (the image's own maps and its merged detections: one context, one tile)
                     dE, birth = self.birth_map(region_data, merged)
                     self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
                     del dE
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth,
-                                                   complete_summary=done, tempering=tempered, recombine=recombined))
+                                                   complete_summary=done, tempering=tempered, recombine=recombined,
+                                                   descent=descended))
                 if figures:
                     self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all

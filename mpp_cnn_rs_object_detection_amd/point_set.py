@@ -275,6 +275,53 @@ class EPointsSet:
                    argmin=(int(rep["x"]), int(rep["y"])), n_negative=int(rep["n_negative"]), n_nan=int(rep["n_nan"]))
         return out
 
+    def descend(self, energy_combinator=None, births: bool = True, deaths: bool = True, max_rounds: int = 16,
+                min_gain: float = 0.0) -> dict:
+        """Local descent (``mpp_descend``): rounds of greedy deaths -- the points whose removal lowers the energy by more than
+        ``min_gain``, no two within twice the interaction range -- and of the births of ``birth_complete``, until a whole
+        round changes nothing or ``max_rounds`` rounds have changed the set.  The set is rebuilt from the call's ``src``:
+        the surviving ``Rectangle`` objects stay, in their relative order, the born ones follow.  A birth round that does not
+        fit the context's point capacity makes the set move to a context of twice the capacity and go on (the gains are then
+        the sums of the parts' gains).  Returns {"status" (0 joint fixed point, 1 round limit), "rounds", "n_added",
+        "n_removed", "n_after", "gain_births", "gain_deaths", "gain" (births minus deaths: the energy change), "max_p",
+        "slot_max", "n_positive", "min_dE", "argmin": (x, y), "n_negative", "n_nan"}, the last seven of the returned set."""
+        from .hip_api import DESCEND_BIRTHS, DESCEND_DEATHS, DESCENT_CAPACITY
+        what = (DESCEND_DEATHS if deaths else 0) | (DESCEND_BIRTHS if births else 0)
+        if not what:
+            raise ValueError("descend: births and deaths are both off")
+        out = {"status": 0, "rounds": 0, "n_added": 0, "n_removed": 0, "n_after": len(self._points), "gain_births": 0.0,
+               "gain_deaths": 0.0}
+        left, first = int(max_rounds), True
+        while True:
+            self._use(energy_combinator)
+            rep, src = self._ctx.descend(what, left, min_gain, src=True)
+            rep, src = rep[0], src[0]
+            if int(rep["n_added"]) or int(rep["n_removed"]):
+                n = int(rep["n_after"])
+                xy, marks = self._ctx.get_points(0)
+                assert len(xy) == n == len(self._points) + int(rep["n_added"]) - int(rep["n_removed"])
+                pts = [self._points[s] if s >= 0 else Rectangle(int(x), int(y), size=float(m[0]), ratio=float(m[1]), angle=float(m[2]))
+                       for s, (x, y), m in zip(src[:n].tolist(), xy, marks)]
+                self._points = pts
+                self._index = {u: k for k, u in enumerate(pts)}
+            for k in ("rounds", "n_added", "n_removed"):
+                out[k] += int(rep[k])
+            for k in ("gain_births", "gain_deaths"):
+                out[k] = float(rep[k]) if first else out[k] + float(rep[k])
+            left, first = left - int(rep["rounds"]), False
+            if int(rep["status"]) != DESCENT_CAPACITY:
+                break
+            if left < 1:                                # (the round that did not fit was the last one allowed)
+                rep = rep.copy()
+                rep["status"] = 1
+                break
+            self._grow_context()
+        out.update(status=int(rep["status"]), n_after=int(rep["n_after"]), gain=out["gain_births"] - out["gain_deaths"],
+                   max_p=float(rep["max_p"]), slot_max=int(rep["slot_max"]), n_positive=int(rep["n_positive"]),
+                   min_dE=float(rep["min_dE"]), argmin=(int(rep["x"]), int(rep["y"])), n_negative=int(rep["n_negative"]),
+                   n_nan=int(rep["n_nan"]))
+        return out
+
     # -- mutation ------------------------------------------------------------------------------------
     def apply_perturbation(self, p: Perturbation, inplace: bool = False) -> "EPointsSet":
         """Reference ``energy_point_set.py:118-154``."""
