@@ -93,7 +93,7 @@ def test_hip_epilogues_match_torch_float32(nets):
         runner.ctx.posnet_epilogue(pos_out, H, W, -10.8, -2.1, d)
         runner.ctx.shapenet_epilogue(logits, H, W, m)
         torch.cuda.synchronize()
-        if H > 1:
+        if H > 1:   # (torch.gradient refuses an axis of length 1: tests/test_gpu_unet_epilogue_float64.py holds H = 1 to float64)
             ref_d = unet.detection_map_torch(pos_out.cpu(), H, W, -10.8, -2.1)
             np.testing.assert_allclose(d.cpu().numpy(), ref_d.numpy(), rtol=1e-5, atol=1e-6)
         ref_m = unet.marks_torch([logits.cpu()], H, W)[0]
