@@ -278,7 +278,8 @@ int mpp_select_minima(mpp_ctx *ctx, int H, int W, int ld, const double *dE_dev, 
                       int32_t *xy, double *values, int64_t *n_candidates, int64_t *n_kept);
 /* Greedy completion: births from the birth-energy map until none lowers the energy by more than min_gain.  Every chain of the
  * ctx on its own, from the state mpp_get_points_all reads.  A round:
- *   the map of mpp_birth_energy_map of the current state (into a workspace of the ctx: 8 B per pixel per chain);
+ *   the map of mpp_birth_energy_map of the current state (into the workspace of mpp_descend, whose births-only round loop
+ *   this is: 8 B per pixel per chain);
  *   mpp_select_minima on it with below = -min_gain and distance = 2 * max_inter, max_inter the model's largest pair range --
  *   two kept candidates then neither interact nor share a neighbour, so in real arithmetic the round lowers the energy by
  *   exactly the sum of its dE;

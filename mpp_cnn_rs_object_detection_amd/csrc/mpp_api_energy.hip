@@ -146,25 +146,21 @@ static int birth_refusals(mpp_ctx *c, const char *who) {
 // The launches of one birth-energy map of every chain (mpp_birth_map.hip): grids as mpp_total_energy_all builds them, the
 // pre-pass that caches every point's record, the map.  After push_state; part / d_sum: the summary's workspace.
 static int birth_map_launches(mpp_ctx *c, const char *who, double *dE, double *marks, BirthPart **part, mpp_birth_summary **d_sum) {
-  const int T = c->n_tiles, ncell = c->hp.nx * c->hp.ny;
+  const int T = c->n_tiles;
   if (T > 65535) return fail(c, -1, "%s: %d chains, at most 65535", who, T);
-  const bool grid = c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points;
   const size_t TC = (size_t)T * c->cap;
-  // doubles: lin, r0, r1, e [T][cap]; the summary's parts and results; ints: gate [T][cap], then the grids
+  // doubles: lin, r0, r1, e [T][cap]; the summary's parts and results; ints: gate [T][cap]
   const size_t part_bytes = (size_t)T * MPP_BIRTH_PARTS * sizeof(BirthPart), sum_bytes = (size_t)T * sizeof(mpp_birth_summary);
-  const size_t n_int = TC + (grid ? (size_t)T * (2 * (size_t)ncell + 1) + TC : 0);
-  if (c->birth_ws.reserve(c->stream, 4 * TC * sizeof(double) + part_bytes + sum_bytes + n_int * sizeof(int32_t)) != hipSuccess)
+  ChainGrids g;
+  if (c->birth_ws.reserve(c->stream, 4 * TC * sizeof(double) + part_bytes + sum_bytes + TC * sizeof(int32_t)) != hipSuccess ||
+      chain_grids_build(c, c->cap, chain_grids_on(c), &g))
     return fail(c, -2, "no device memory for the point cache of %d chains", T);
   double *d0 = (double *)c->birth_ws.p;
   *part = (BirthPart *)(d0 + 4 * TC);
   *d_sum = (mpp_birth_summary *)(*part + (size_t)T * MPP_BIRTH_PARTS);
-  int32_t *gate = (int32_t *)(*d_sum + T);
-  const BirthCache bc{d0, d0 + TC, d0 + 2 * TC, d0 + 3 * TC, gate};
-  int32_t *gs = grid ? gate + TC : nullptr, *gc = grid ? gs + (size_t)T * (ncell + 1) : nullptr;
-  int32_t *gi = grid ? gc + (size_t)T * ncell : nullptr;
-  c->birth_grid = grid ? 1 : 0;
-  if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, gs, gc, gi);
-  mpp_launch_birth_prepass(c->stream, c->dp, c->d_tiles, T, c->cap, bc, gs, gi, ncell + 1, c->grid_min_points);
+  const BirthCache bc{d0, d0 + TC, d0 + 2 * TC, d0 + 3 * TC, (int32_t *)(*d_sum + T)};
+  c->birth_grid = g.ncell > 0 ? 1 : 0;
+  mpp_launch_birth_prepass(c->stream, c->dp, c->d_tiles, T, c->cap, bc, g.start, g.items, g.ncell + 1, c->grid_min_points);
   mpp_launch_birth_map(c->stream, c->dp, c->d_tiles, T, c->cap, c->H, c->W, bc, dE, marks);
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -234,72 +230,15 @@ extern "C" int mpp_select_minima(mpp_ctx *c, int H, int W, int ld, const double 
   return 0;
 }
 
-// Greedy completion.  Per round: the launches of the map, of the selection and of the append, and one
-// copy of the chains' reports; the maps and the point lists stay on the device.
-extern "C" int mpp_birth_complete(mpp_ctx *c, int max_rounds, double min_gain, mpp_complete_report *report) {
-  if (!c) return -1;
-  int rc = birth_refusals(c, "birth_complete");
-  if (rc) return rc;
-  if (!report) return fail(c, -1, "birth_complete: report is NULL");
-  if (max_rounds < 1 || max_rounds > 1024) return fail(c, -1, "birth_complete: max_rounds %d, must be 1..1024", max_rounds);
-  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(c, -1, "birth_complete: min_gain must be finite and >= 0");
-  if ((rc = push_state(c))) return rc;
-  const int T = c->n_tiles, H = c->H, W = c->W;
-  if (T > 65535) return fail(c, -1, "birth_complete: %d chains, at most 65535", T);
-  const size_t hw = (size_t)H * W, TC = (size_t)T * c->cap;
-  if (c->complete_ws.reserve(c->stream, (T * hw + TC) * sizeof(double) + (size_t)T * sizeof(mpp_complete_report)) != hipSuccess)
-    return fail(c, -2, "no device memory for the maps of %d chains", T);
-  double *dE = (double *)c->complete_ws.p, *gain_val = dE + T * hw;
-  mpp_complete_report *rep = (mpp_complete_report *)(gain_val + TC);
-  MinSel s;
-  if ((rc = minsel_setup(c, &s, dE, hw, T, H, W, W, -min_gain, 2.0 * c->hp.max_inter, rep))) return rc;
-  mpp_launch_complete_init(c->stream, T, rep);
-  BirthPart *part = nullptr;
-  mpp_birth_summary *d_sum = nullptr;
-  bool open = true, limit = false;
-  std::vector<int32_t> was(T, -1);
-  // (a chain is open for at most max_rounds appending rounds and the one that closes it)
-  for (int round = 0; round <= max_rounds && open; ++round) {
-    if ((rc = birth_map_launches(c, "birth_complete", dE, nullptr, &part, &d_sum))) return rc;
-    mpp_launch_minsel(c->stream, s);
-    mpp_launch_complete_round(c->stream, s, c->dp, c->d_tiles, c->cap, gain_val, max_rounds, rep);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(report, rep, (size_t)T * sizeof(mpp_complete_report), hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    HIPCHK(c, e); HIPCHK(c, e2);
-    open = limit = false;                                  // limit: a chain appended in this round and stopped at max_rounds
-    for (int t = 0; t < T; ++t) {
-      open = open || report[t].status < 0;
-      limit = limit || (report[t].status == 1 && was[t] < 0);
-      was[t] = report[t].status;
-    }
-  }
-  if (open) return fail(c, -9, "birth_complete: a chain is still open after %d rounds", max_rounds + 1);
-  // the summary of the returned state's map: the last map is that of every chain but those its round stopped at the limit
-  if (limit && (rc = birth_map_launches(c, "birth_complete", dE, nullptr, &part, &d_sum))) return rc;
-  mpp_launch_birth_summary(c->stream, T, H, W, dE, part, d_sum);
-  mpp_launch_complete_summary(c->stream, T, d_sum, rep);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(report, rep, (size_t)T * sizeof(mpp_complete_report), hipMemcpyDeviceToHost, c->stream);
-  hipError_t e2 = hipStreamSynchronize(c->stream);
-  HIPCHK(c, e); HIPCHK(c, e2);
-  return 0;
-}
-
 // ---- the local descent (mpp_descent.hip) -------------------------------------------------------------------
-// Does the Papangelou pass of every chain take its neighbours from candidate grids?  As chain_energy_launches decides it: when
-// a chain could reach scratch_grid_min_points.  k_papangelou_tiles has no threshold per chain, so then every chain uses its
-// grid; the values are the same bits either way.
-static int descent_ncell(const mpp_ctx *c) {
-  const int ncell = c->hp.nx * c->hp.ny;
-  return c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points ? ncell : 0;
-}
-// The launches of mpp_merge_score's scoring for every chain, into d.p; the counts stay on the device (a block per slot of the
-// capacity: the blocks behind a chain's count return at once).
-static int papangelou_launches(mpp_ctx *c, const Descent &d, int ncell) {
-  const int T = c->n_tiles;
-  if (ncell > 0) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, d.gs, d.gc, d.gi);
-  mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, c->cap, c->cap, d.p, d.gs, d.gi, ncell + 1, c->cap);
+// The launches of mpp_merge_score's scoring for every chain, into p [n_chains][cap]; the counts stay on the device (a block per
+// slot of the capacity: the blocks behind a chain's count return at once).  k_papangelou_tiles has no threshold per chain, so
+// with the grids on every chain uses its own; the values are the same bits either way.  `what` names the caller's workspace.
+static int papangelou_launches(mpp_ctx *c, double *p, const char *what) {
+  ChainGrids g;
+  if (chain_grids_build(c, c->cap, chain_grids_on(c), &g))
+    return fail(c, -2, "no device memory for the %s of %d chains", what, c->n_tiles);
+  mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, c->n_tiles, c->cap, c->cap, p, g.start, g.items, g.ncell + 1, c->cap);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -308,15 +247,15 @@ extern "C" int mpp_papangelou_all(mpp_ctx *c, double *dE) {
   if (!c || !dE) return fail(c, -1, "bad papangelou_all arguments");
   int rc = push_state(c);
   if (rc) return rc;
-  const int T = c->n_tiles, ncell = descent_ncell(c);
+  const int T = c->n_tiles;
   if (T > 65535) return fail(c, -1, "papangelou_all: %d chains, at most 65535", T);
-  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, 0, ncell)) != hipSuccess)
+  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, 0)) != hipSuccess)
     return fail(c, -2, "no device memory for the Papangelou values of %d chains", T);
   Descent d;
-  mpp_descent_plan(&d, T, c->cap, 0, ncell, c->descent_ws.p);
+  mpp_descent_plan(&d, T, c->cap, 0, c->descent_ws.p);
   const size_t bytes = (size_t)T * c->cap * sizeof(double);
   HIPCHK(c, hipMemsetAsync(d.p, 0, bytes, c->stream));           // (the kernel writes the slots below a chain's count only)
-  if ((rc = papangelou_launches(c, d, ncell))) return rc;
+  if ((rc = papangelou_launches(c, d.p, "Papangelou values"))) return rc;
   hipError_t e = hipMemcpyAsync(dE, d.p, bytes, hipMemcpyDeviceToHost, c->stream);
   hipError_t e2 = hipStreamSynchronize(c->stream);
   HIPCHK(c, e); HIPCHK(c, e2);
@@ -347,30 +286,30 @@ extern "C" int mpp_select_points(mpp_ctx *c, int n, const int32_t *xy, const dou
   return 0;
 }
 
-// Per round: the launches of the Papangelou pass, of the selection among points and of the removal; those of one round of the
-// completion; the round's book; one copy of the chains' reports.  The point lists and the maps stay on the device.
-extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain, mpp_descent_report *report, int32_t *src) {
-  if (!c) return -1;
-  if (what < 1 || what > 3) return fail(c, -1, "descend: what %d, must be 1 (deaths), 2 (births) or 3 (both)", what);
-  const bool deaths = what & MPP_DESCEND_DEATHS, births = what & MPP_DESCEND_BIRTHS;
-  int rc = 0;
-  if (births) { if ((rc = birth_refusals(c, "descend"))) return rc; }
-  else if (!c->have_maps || !c->have_model) return fail(c, -1, "descend: mpp_set_maps / mpp_set_model have not been called");
-  if (!report) return fail(c, -1, "descend: report is NULL");
-  if (max_rounds < 1 || max_rounds > 1024) return fail(c, -1, "descend: max_rounds %d, must be 1..1024", max_rounds);
-  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(c, -1, "descend: min_gain must be finite and >= 0");
-  for (int p = 0; p < c->hp.model.n_pair; ++p)                   // (a round's gains add up only under an order-free reduction)
-    if (c->hp.model.pair[p].reduce != MPP_REDUCE_MAX && c->hp.model.pair[p].reduce != MPP_REDUCE_MIN)
-      return fail(c, -1, "descend: pair term %d has a reduction that is neither max nor min", p);
-  const int T = c->n_tiles, H = c->H, W = c->W;
-  if (T > 65535) return fail(c, -1, "descend: %d chains, at most 65535", T);
-  if ((rc = push_state(c))) return rc;
-  const size_t hw = births ? (size_t)H * W : 0;
-  const int ncell = descent_ncell(c);
-  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, hw, ncell)) != hipSuccess)
-    return fail(c, -2, "no device memory for the descent of %d chains", T);
+// The rounds of mpp_descend and of mpp_birth_complete (what = births: DESIGN.md sections 13 and 16), from the refusal of too many
+// chains to the round that closes the last chain.  Per round: the launches of the Papangelou pass, of the selection among
+// points and of the removal; those of one round of the completion; the round's book; one copy of the chains' reports to
+// report [n_chains].  The point lists and the maps stay on the device.  `who` names the caller and `noun` its workspace in the
+// messages.  What it leaves for the caller's tail: the workspace, whether the last Papangelou values (the last map) are not
+// those of the returned state, and the map summary's workspace.
+struct DescentRounds {
   Descent d;
-  mpp_descent_plan(&d, T, c->cap, hw, ncell, c->descent_ws.p);
+  bool stale_p, stale_map;
+  BirthPart *part;
+  mpp_birth_summary *d_sum;
+};
+static int descent_rounds(mpp_ctx *c, const char *who, const char *noun, int what, int max_rounds, double min_gain,
+                          mpp_descent_report *report, DescentRounds *out) {
+  const bool deaths = what & MPP_DESCEND_DEATHS, births = what & MPP_DESCEND_BIRTHS;
+  const int T = c->n_tiles, H = c->H, W = c->W;
+  if (T > 65535) return fail(c, -1, "%s: %d chains, at most 65535", who, T);
+  int rc = push_state(c);
+  if (rc) return rc;
+  const size_t hw = births ? (size_t)H * W : 0;
+  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, hw)) != hipSuccess)
+    return fail(c, -2, "no device memory for the %s of %d chains", noun, T);
+  Descent &d = out->d;
+  mpp_descent_plan(&d, T, c->cap, hw, c->descent_ws.p);
   const double reach = 2.0 * c->hp.max_inter;
   MinSel s{};
   if (births && (rc = minsel_setup(c, &s, d.dE, hw, T, H, W, W, -min_gain, reach, d.crep))) return rc;
@@ -379,19 +318,19 @@ extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain
   ps.above = min_gain; ps.d2 = reach * reach; ps.closed = d.crep;
   mpp_launch_complete_init(c->stream, T, d.crep);
   mpp_launch_descent_init(c->stream, c->d_tiles, d);
-  BirthPart *part = nullptr;
-  mpp_birth_summary *d_sum = nullptr;
-  bool open = true, stale_p = !deaths, stale_map = false;
+  out->part = nullptr; out->d_sum = nullptr;
+  out->stale_p = !deaths; out->stale_map = false;
+  bool open = true;
   std::vector<int32_t> was(T, -1);
   // (a chain is open for at most max_rounds rounds that change it and the one that closes it)
   for (int round = 0; round <= max_rounds && open; ++round) {
     if (deaths) {
-      if ((rc = papangelou_launches(c, d, ncell))) return rc;
+      if ((rc = papangelou_launches(c, d.p, noun))) return rc;
       mpp_launch_ptsel(c->stream, ps);
       mpp_launch_descent_remove(c->stream, c->d_tiles, d);
     }
     if (births) {
-      if ((rc = birth_map_launches(c, "descend", d.dE, nullptr, &part, &d_sum))) return rc;
+      if ((rc = birth_map_launches(c, who, d.dE, nullptr, &out->part, &out->d_sum))) return rc;
       mpp_launch_minsel(c->stream, s);
       mpp_launch_complete_round(c->stream, s, c->dp, c->d_tiles, c->cap, d.gain_val, 1 << 30, d.crep);
     }
@@ -405,20 +344,70 @@ extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain
       const int st = report[t].status;
       open = open || st < 0;
       // a chain that changed in the round that closed it: its last Papangelou values (its last map) are not its state's
-      if (was[t] < 0 && st > 0) { stale_p = true; stale_map = stale_map || st == 1; }
+      if (was[t] < 0 && st > 0) { out->stale_p = true; out->stale_map = out->stale_map || st == 1; }
       was[t] = st;
     }
   }
-  if (open) return fail(c, -9, "descend: a chain is still open after %d rounds", max_rounds + 1);
-  if (stale_p && (rc = papangelou_launches(c, d, ncell))) return rc;
-  if (births) {
-    if (stale_map && (rc = birth_map_launches(c, "descend", d.dE, nullptr, &part, &d_sum))) return rc;
-    mpp_launch_birth_summary(c->stream, T, H, W, d.dE, part, d_sum);
-  }
-  mpp_launch_descent_summary(c->stream, c->d_tiles, d, births ? d_sum : nullptr);
+  if (open) return fail(c, -9, "%s: a chain is still open after %d rounds", who, max_rounds + 1);
+  return 0;
+}
+
+// What mpp_birth_complete and mpp_descend refuse alike in their round limit and gain
+static int rounds_refusals(mpp_ctx *c, const char *who, int max_rounds, double min_gain) {
+  if (max_rounds < 1 || max_rounds > 1024) return fail(c, -1, "%s: max_rounds %d, must be 1..1024", who, max_rounds);
+  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(c, -1, "%s: min_gain must be finite and >= 0", who);
+  return 0;
+}
+
+// Greedy completion: the births-only rounds of the descent, whose birth half keeps the completion's
+// book in d.crep -- k_complete_round books the appends with no round limit, k_descent_round applies max_rounds and writes the
+// status back, so status, rounds, n_added, n_after and gain are what a loop over k_complete_round alone would leave.  The tail
+// is the completion's own: the summary of the returned state's map, and no Papangelou pass.
+extern "C" int mpp_birth_complete(mpp_ctx *c, int max_rounds, double min_gain, mpp_complete_report *report) {
+  if (!c) return -1;
+  int rc = birth_refusals(c, "birth_complete");
+  if (rc) return rc;
+  if (!report) return fail(c, -1, "birth_complete: report is NULL");
+  if ((rc = rounds_refusals(c, "birth_complete", max_rounds, min_gain))) return rc;
+  const int T = c->n_tiles;
+  std::vector<mpp_descent_report> book(T > 0 ? T : 1);
+  DescentRounds r;
+  if ((rc = descent_rounds(c, "birth_complete", "maps", MPP_DESCEND_BIRTHS, max_rounds, min_gain, book.data(), &r))) return rc;
+  // the last map is that of every chain but those its round stopped at the limit
+  if (r.stale_map && (rc = birth_map_launches(c, "birth_complete", r.d.dE, nullptr, &r.part, &r.d_sum))) return rc;
+  mpp_launch_birth_summary(c->stream, T, c->H, c->W, r.d.dE, r.part, r.d_sum);
+  mpp_launch_complete_summary(c->stream, T, r.d_sum, r.d.crep);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(report, d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && src) e = hipMemcpyAsync(src, d.src, (size_t)T * c->cap * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(report, r.d.crep, (size_t)T * sizeof(mpp_complete_report), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
+extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain, mpp_descent_report *report, int32_t *src) {
+  if (!c) return -1;
+  if (what < 1 || what > 3) return fail(c, -1, "descend: what %d, must be 1 (deaths), 2 (births) or 3 (both)", what);
+  const bool births = what & MPP_DESCEND_BIRTHS;
+  int rc = 0;
+  if (births) { if ((rc = birth_refusals(c, "descend"))) return rc; }
+  else if (!c->have_maps || !c->have_model) return fail(c, -1, "descend: mpp_set_maps / mpp_set_model have not been called");
+  if (!report) return fail(c, -1, "descend: report is NULL");
+  if ((rc = rounds_refusals(c, "descend", max_rounds, min_gain))) return rc;
+  for (int p = 0; p < c->hp.model.n_pair; ++p)                   // (a round's gains add up only under an order-free reduction)
+    if (c->hp.model.pair[p].reduce != MPP_REDUCE_MAX && c->hp.model.pair[p].reduce != MPP_REDUCE_MIN)
+      return fail(c, -1, "descend: pair term %d has a reduction that is neither max nor min", p);
+  DescentRounds r;
+  if ((rc = descent_rounds(c, "descend", "descent", what, max_rounds, min_gain, report, &r))) return rc;
+  const int T = c->n_tiles;
+  if (r.stale_p && (rc = papangelou_launches(c, r.d.p, "descent"))) return rc;
+  if (births) {
+    if (r.stale_map && (rc = birth_map_launches(c, "descend", r.d.dE, nullptr, &r.part, &r.d_sum))) return rc;
+    mpp_launch_birth_summary(c->stream, T, c->H, c->W, r.d.dE, r.part, r.d_sum);
+  }
+  mpp_launch_descent_summary(c->stream, c->d_tiles, r.d, births ? r.d_sum : nullptr);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(report, r.d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && src) e = hipMemcpyAsync(src, r.d.src, (size_t)T * c->cap * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
   hipError_t e2 = hipStreamSynchronize(c->stream);
   HIPCHK(c, e); HIPCHK(c, e2);
   return 0;
@@ -531,7 +520,7 @@ extern "C" int mpp_merge_score(mpp_ctx *c, double distance, int cap, int32_t *n_
   // (the walk carries a position as two 16-bit halves; mpp_set_maps is the guard: it takes no side above 65535)
   const size_t TC = (size_t)T * c->cap;
   DevBuf<double> d_dE, ts, tr, ta;
-  DevBuf<int32_t> work, slot_of, tx, ty, d_rem, gs, gc, gi;       // (gs, gc, gi: the candidate grids, where they pay)
+  DevBuf<int32_t> work, slot_of, tx, ty, d_rem;
   hipError_t e = hipSuccess;
   auto A = [&](auto &buf, size_t count) { if (e == hipSuccess) e = buf.alloc(count); };
   A(d_dE, TC); A(ts, TC); A(tr, TC); A(ta, TC);
@@ -540,17 +529,14 @@ extern "C" int mpp_merge_score(mpp_ctx *c, double distance, int cap, int32_t *n_
   if (e == hipSuccess && max_n > 0) {
     // (64 bits: 65535^2 + 65535^2 does not fit an int; beyond that every pair of points is within the distance)
     const long long dist2 = (long long)floor(fmin(distance * distance + 1e-9, 1e10));
-    // the from-scratch energies look their neighbours up in per-tile candidate grids, built on the device before each of
-    // the two scorings (the removals in between move points)
-    const int ncell = c->hp.nx * c->hp.ny;
-    if (ncell > 0 && max_n >= 64) { A(gs, (size_t)T * (ncell + 1)); A(gc, (size_t)T * ncell); A(gi, TC); }
-    const bool grid = gs && gc && gi && e == hipSuccess;
-    if (e == hipSuccess) {
-      if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, max_n, ncell, c->cap, gs, gc, gi);
-      mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, max_n, c->cap, d_dE, grid ? gs.p : nullptr, grid ? gi.p : nullptr, ncell + 1, c->cap);
-      mpp_launch_dedupe_tiles(c->stream, c->d_tiles, T, max_n, c->cap, d_dE, dist2, work, slot_of, tx, ty, ts, tr, ta, d_rem);
-      if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, max_n, ncell, c->cap, gs, gc, gi);
-      mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, max_n, c->cap, d_dE, grid ? gs.p : nullptr, grid ? gi.p : nullptr, ncell + 1, c->cap);
+    // the from-scratch energies look their neighbours up in the chains' candidate grids where they pay, built on the device
+    // before each of the two scorings (the removals in between move points)
+    const bool grid = c->hp.nx * c->hp.ny > 0 && max_n >= 64;
+    ChainGrids g;
+    for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
+      if (chain_grids_build(c, max_n, grid, &g)) { e = hipErrorOutOfMemory; break; }
+      mpp_launch_papangelou_tiles(c->stream, c->dp, c->d_tiles, T, max_n, c->cap, d_dE, g.start, g.items, g.ncell + 1, c->cap);
+      if (pass == 0) mpp_launch_dedupe_tiles(c->stream, c->d_tiles, T, max_n, c->cap, d_dE, dist2, work, slot_of, tx, ty, ts, tr, ta, d_rem);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_rem.data(), d_rem, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream);

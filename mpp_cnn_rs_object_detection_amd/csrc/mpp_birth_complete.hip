@@ -50,7 +50,6 @@ __global__ __launch_bounds__(MINSEL_THREADS) void k_minsel_compact(MinSel s) {
   const long long hw = (long long)s.H * s.W;
   const double *d = s.dE + (size_t)chain * s.chain_stride;
   const bool closed = minsel_closed(s, chain);                 // (a finished chain of the completion has no candidates)
-  const unsigned long long lower = (1ull << lane) - 1ull;
   const size_t lbase = (size_t)chain * hw;
   int at = FILL ? s.cblk[(size_t)chain * s.nb_fill + blockIdx.x] : 0;      // (after the scan: where this block's run starts)
   int mine = 0;
@@ -63,19 +62,14 @@ __global__ __launch_bounds__(MINSEL_THREADS) void k_minsel_compact(MinSel s) {
       v = d[(size_t)x * s.ld + y];
       is = v < s.below;                                        // (false for a NaN, true for -inf)
     }
-    const unsigned long long m = __ballot(is);
-    if (!FILL) { mine += lane == 0 ? __popcll(m) : 0; continue; }
-    if (lane == 0) s_w[wave] = __popcll(m);
-    __syncthreads();
-    int pos = at + __popcll(m & lower), total = 0;
-#pragma unroll
-    for (int w = 0; w < MINSEL_WAVES; ++w) {
-      const int c = s_w[w];
-      pos += w < wave ? c : 0;
-      total += c;
+    if (!FILL) {
+      const unsigned long long m = __ballot(is);
+      mine += lane == 0 ? __popcll(m) : 0;
+      continue;
     }
+    int total;
+    const int pos = at + block_scan_place<MINSEL_WAVES>(is, s_w, &total);
     if (is) { s.idx[lbase + pos] = (int32_t)p; s.val[lbase + pos] = v; }    // (pos < the chain's candidates <= hw)
-    __syncthreads();                                           // (the wave counts may be overwritten)
     at += total;
   }
   if (!FILL) {
@@ -178,16 +172,12 @@ __global__ __launch_bounds__(MINSEL_THREADS) void k_minsel_resolve(MinSel s) {
 // The place of this lane's candidate among the chain's kept ones, -1 if it is none or not kept; *id, *v: the candidate.
 // Every lane of the block calls it (it synchronises); s_w: MINSEL_WAVES ints of LDS.
 __device__ __forceinline__ int minsel_kept_place(const MinSel &s, int chain, int *s_w, int *id, double *v) {
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  const int i = blockIdx.x * MINSEL_THREADS + tid;
+  const int i = blockIdx.x * MINSEL_THREADS + threadIdx.x;
   const size_t lbase = (size_t)chain * s.H * s.W;
   const bool kept = i < s.n_cand[chain] && s.keep[lbase + i] != 0;
   if (kept) { *id = s.idx[lbase + i]; *v = s.val[lbase + i]; }
-  const unsigned long long m = __ballot(kept);
-  if (lane == 0) s_w[wave] = __popcll(m);
-  __syncthreads();
-  int pos = s.kblk[(size_t)chain * s.nb_res + blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) pos += s_w[w];
+  int total;                                                   // (not needed: the block's start comes from the scan of kblk)
+  const int pos = s.kblk[(size_t)chain * s.nb_res + blockIdx.x] + block_scan_place<MINSEL_WAVES, false>(kept, s_w, &total);
   return kept ? pos : -1;
 }
 

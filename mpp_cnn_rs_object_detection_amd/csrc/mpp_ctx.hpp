@@ -132,16 +132,17 @@ struct mpp_ctx : TileMem {
   int64_t x_exchanges = 0, x_attempts = 0;
   double x_ms = 0.0;
   DevWs x_log;
-  // uniform grid over one tile's configuration for the from-scratch energies (built per call; see mpp_scratch.hip)
+  // uniform grid over one tile's configuration for the from-scratch energies (built per call; see mpp_scratch.hip).  It stays
+  // apart from grids_ws: its threshold is the tile's actual count, not the capacity
   DevWs g_cells, g_items;            // cell starts [ncell + 1] then cursors [ncell]; the points by cell [cap]
   int grid_min_points = 256;
-  DevWs energy_ws;                   // mpp_total_energy_all: every chain's point energies, their sums, the chains' grids
-  DevWs birth_ws;                    // mpp_birth_energy_map: the per-point cache, the chains' grids, the summary's parts
+  DevWs grids_ws;                    // the candidate grids of every chain (chain_grids_build): rebuilt right before their one consumer
+  DevWs energy_ws;                   // mpp_total_energy_all: every chain's point energies, their sums
+  DevWs birth_ws;                    // mpp_birth_energy_map: the per-point cache, the summary's parts
   int birth_grid = 0;                // ... its last pre-pass built candidate grids
-  DevWs minsel_ws;                   // mpp_select_minima / mpp_birth_complete: the candidate list and its tables
-  DevWs complete_ws;                 // mpp_birth_complete: every chain's map, the appended values, the reports
+  DevWs minsel_ws;                   // mpp_select_minima / mpp_birth_complete / mpp_descend: the candidate list and its tables
   DevWs recombine_ws;                // mpp_recombine: the tiles' labels and cluster choices, the staged composites, the reports
-  DevWs descent_ws;                  // mpp_descend / mpp_papangelou_all: the Papangelou values, the grids, the round's lists, the reports
+  DevWs descent_ws;                  // mpp_descend / mpp_birth_complete / mpp_papangelou_all: the Papangelou values, the maps, the round's lists, the reports
   DevWs ptsel_ws;                    // mpp_select_points: its two counters
   int recombine_lds = MPP_RECOMBINE_LDS_POINTS;   // ... a tile of more points over its replicas labels in the workspace, not in LDS
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
@@ -168,24 +169,46 @@ static int fail(mpp_ctx *c, int code, const char *fmt, ...) {
 int push_state(mpp_ctx *c);             // (mpp_api.hip)
 int check_tile(mpp_ctx *c, int tile);
 
+// The candidate grids of every chain (mpp_launch_grid_build_all): start [T][ncell + 1], cursor [T][ncell], items [T][cap] in
+// grids_ws.  Off: null pointers and ncell 0, and the kernels scan the whole configuration.
+struct ChainGrids {
+  int32_t *start = nullptr, *cursor = nullptr, *items = nullptr;
+  int ncell = 0;
+};
+// The passes over every chain keep the counts on the device, so their grids are on whenever a chain could reach
+// scratch_grid_min_points (mpp_merge_score, which knows the counts, has a rule of its own).
+static bool chain_grids_on(const mpp_ctx *c) {
+  return c->grid_min_points > 0 && c->hp.nx * c->hp.ny > 0 && c->cap >= c->grid_min_points;
+}
+// When `on`, build the grids over the first max_n slots of every chain; nonzero: no device memory.  They serve the launches
+// that follow on the context's stream up to the next build, and *g holds for that long only: reserve may move the block.
+static int chain_grids_build(mpp_ctx *c, int max_n, bool on, ChainGrids *g) {
+  *g = ChainGrids{};
+  if (!on) return 0;
+  const int ncell = c->hp.nx * c->hp.ny;
+  const size_t T = (size_t)c->n_tiles;
+  if (c->grids_ws.reserve(c->stream, T * (2 * (size_t)ncell + 1 + c->cap) * sizeof(int32_t)) != hipSuccess) return -2;
+  g->start = (int32_t *)c->grids_ws.p; g->cursor = g->start + T * (ncell + 1); g->items = g->cursor + T * ncell;
+  g->ncell = ncell;
+  mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, c->n_tiles, max_n, ncell, c->cap, g->start, g->cursor, g->items);
+  return 0;
+}
+
 // The launches of mpp_total_energy_all, after push_state: every chain's energy, from the written-back state, stays on the
 // device in *d_sum [n_chains] (workspace energy_ws).  The point energies of all chains in one launch (the kernel of
-// mpp_total_energy, so the same bits), their sums in slot order.  The counts stay on the device: the grids are built for every
-// chain whenever a chain could reach scratch_grid_min_points, and each chain uses its own only from that many points on.
+// mpp_total_energy, so the same bits), their sums in slot order.  Each chain uses its grid only from scratch_grid_min_points
+// points on.
 static int chain_energy_launches(mpp_ctx *c, double **d_sum) {
-  const int T = c->n_tiles, ncell = c->hp.nx * c->hp.ny;
+  const int T = c->n_tiles;
   if (T > 65535) return fail(c, -1, "total_energy_all: %d chains, at most 65535", T);
-  const bool grid = c->grid_min_points > 0 && ncell > 0 && c->cap >= c->grid_min_points;
   const size_t TC = (size_t)T * c->cap;
-  const size_t n_dbl = TC + (size_t)T, n_int = grid ? (size_t)T * (2 * (size_t)ncell + 1) + TC : 0;
-  if (c->energy_ws.reserve(c->stream, n_dbl * sizeof(double) + n_int * sizeof(int32_t)) != hipSuccess)
+  ChainGrids g;
+  if (c->energy_ws.reserve(c->stream, (TC + (size_t)T) * sizeof(double)) != hipSuccess ||
+      chain_grids_build(c, c->cap, chain_grids_on(c), &g))
     return fail(c, -2, "no device memory for the energies of %d chains", T);
   double *e_pts = (double *)c->energy_ws.p;
   *d_sum = e_pts + TC;
-  int32_t *gs = grid ? (int32_t *)(*d_sum + T) : nullptr, *gc = grid ? gs + (size_t)T * (ncell + 1) : nullptr;
-  int32_t *gi = grid ? gc + (size_t)T * ncell : nullptr;
-  if (grid) mpp_launch_grid_build_all(c->stream, c->dp, c->d_tiles, T, c->cap, ncell, c->cap, gs, gc, gi);
-  mpp_launch_chain_energies(c->stream, c->dp, c->d_tiles, T, c->cap, e_pts, *d_sum, gs, gi, ncell + 1, c->grid_min_points);
+  mpp_launch_chain_energies(c->stream, c->dp, c->d_tiles, T, c->cap, e_pts, *d_sum, g.start, g.items, g.ncell + 1, c->grid_min_points);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -19,14 +19,13 @@
 
 static size_t desc_up8(size_t b) { return (b + 7) & ~(size_t)7; }
 
-extern "C" size_t mpp_descent_bytes(int n_chains, int cap, size_t hw, int ncell) {
+extern "C" size_t mpp_descent_bytes(int n_chains, int cap, size_t hw) {
   const size_t T = (size_t)n_chains, TC = T * cap;
-  const size_t ints = TC + (ncell > 0 ? TC + T * (2 * (size_t)ncell + 1) : 0) + T;
   return (3 * TC + T * hw) * sizeof(double) + T * (sizeof(mpp_descent_report) + sizeof(mpp_complete_report)) +
-         desc_up8(ints * sizeof(int32_t)) + TC;
+         desc_up8((TC + T) * sizeof(int32_t)) + TC;
 }
 // (the doubles first, then the records, the ints, the bytes: every array is aligned for its type)
-extern "C" void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, int ncell, void *ws) {
+extern "C" void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, void *ws) {
   const size_t T = (size_t)n_chains, TC = T * cap;
   d->n_chains = n_chains; d->cap = cap;
   d->p = (double *)ws; d->rem_val = d->p + TC; d->gain_val = d->rem_val + TC;
@@ -35,12 +34,7 @@ extern "C" void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, i
   d->crep = (mpp_complete_report *)(d->rep + T);
   d->src = (int32_t *)(d->crep + T);
   d->n_rem = d->src + TC;
-  int32_t *g = d->n_rem + T;
-  d->gi = ncell > 0 ? g : nullptr;
-  d->gs = ncell > 0 ? g + TC : nullptr;
-  d->gc = ncell > 0 ? d->gs + T * ((size_t)ncell + 1) : nullptr;
-  const size_t ints = TC + (ncell > 0 ? TC + T * (2 * (size_t)ncell + 1) : 0) + T;
-  d->keep = (uint8_t *)d->src + desc_up8(ints * sizeof(int32_t));
+  d->keep = (uint8_t *)d->src + desc_up8((TC + T) * sizeof(int32_t));
 }
 
 __device__ __forceinline__ int desc_count(const TileRef &t, int cap) {
@@ -122,6 +116,7 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descent_init(const TileRef *ti
 // The points the selection kept leave an open chain; the survivors keep their order.  rem_val[chain][place]: the removed
 // values in slot order; n_rem[chain]: their number.  The count and the error code are written only when a point left.
 __global__ __launch_bounds__(DESC_THREADS) void k_descent_remove(const TileRef *tiles, Descent d) {
+  // (two predicates scanned behind one pair of barriers: block_scan_place, mpp_device.hpp, twice would take two pairs)
   __shared__ int s_s[DESC_WAVES], s_r[DESC_WAVES];
   const int chain = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
   if (d.crep[chain].status >= 0) return;                         // (closed: not touched again)

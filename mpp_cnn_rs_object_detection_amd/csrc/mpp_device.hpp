@@ -393,8 +393,24 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
   return v;
 }
+// The workgroup's compaction scan: the exclusive position of this lane's kept element among those of the WAVES waves, and
+// their number in *total.  Every lane of the block calls it (it synchronises); wave_tot: WAVES ints of LDS.  AGAIN: the block
+// calls it again on the same wave_tot, so it waits until every lane has read the counts.
+template <int WAVES, bool AGAIN = true>
+__device__ __forceinline__ int block_scan_place(bool keep, int *wave_tot, int *total) {
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wave_tot[wv] = __popcll(m);
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int q = 0; q < WAVES; ++q) { const int v = wave_tot[q]; before += q < wv ? v : 0; all += v; }
+  if (AGAIN) __syncthreads();
+  *total = all;
+  return before + __popcll(m & ((1ull << lane) - 1ull));
+}
 
-// ---- Philox4x32-10 --------------------------------------------------------------------------
+// ---- Philox4x32-10--------------------------------------------------------------------------
 __host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                               uint32_t k1, uint32_t out[4]) {
   for (int r = 0; r < 10; ++r) {

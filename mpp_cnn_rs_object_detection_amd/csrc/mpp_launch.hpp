@@ -177,21 +177,20 @@ struct PtSel {
   const mpp_complete_report *closed;
   int32_t *count;
 };
-// The workspace of one mpp_descend, placed by mpp_descent_plan in mpp_descent_bytes bytes (hw: the pixels of a map, 0 without
-// births; ncell: the cells of a candidate grid, 0 without grids).
+// The workspace of one mpp_descend / mpp_birth_complete, placed by mpp_descent_plan in mpp_descent_bytes bytes (hw: the pixels
+// of a map, 0 without births).
 struct Descent {
   int n_chains, cap;
   double *p, *rem_val, *gain_val;                  // [n_chains][cap]: Papangelou values; the removed p and the appended dE of a round by place
   double *dE;                                      // [n_chains][hw] the maps
   mpp_descent_report *rep;                         // [n_chains]
   mpp_complete_report *crep;                       // [n_chains] the birth half's book (the completion's); status >= 0: the chain is closed
-  int32_t *src, *gi;                               // [n_chains][cap]: where a slot's point started; the grids' items
-  int32_t *gs, *gc;                                // [n_chains][ncell + 1], [n_chains][ncell]
-  int32_t *n_rem;                                  // [n_chains] points the round's death half removed
+  int32_t *src;                                    // [n_chains][cap]: where a slot's point started
+  int32_t *n_rem;                                 // [n_chains] points the round's death half removed
   uint8_t *keep;                                   // [n_chains][cap] the selection's answer: 1 = remove
 };
-size_t mpp_descent_bytes(int n_chains, int cap, size_t hw, int ncell);
-void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, int ncell, void *ws);
+size_t mpp_descent_bytes(int n_chains, int cap, size_t hw);
+void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, void *ws);
 void mpp_launch_ptsel(hipStream_t st, const PtSel &s);
 void mpp_launch_descent_init(hipStream_t st, const TileRef *tiles, const Descent &d);
 void mpp_launch_descent_remove(hipStream_t st, const TileRef *tiles, const Descent &d);

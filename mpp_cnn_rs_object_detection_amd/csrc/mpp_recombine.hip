@@ -24,20 +24,6 @@
 #define RC_THREADS 1024
 #define RC_WAVES (RC_THREADS / WAVE)
 
-// exclusive position of this lane's kept point among the workgroup's, and their number (every lane of the block calls it)
-__device__ __forceinline__ int rc_block_scan(bool keep, int *wave_tot, int *total) {
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wave_tot[wv] = __popcll(m);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int q = 0; q < RC_WAVES; ++q) { const int v = wave_tot[q]; before += q < wv ? v : 0; all += v; }
-  __syncthreads();
-  *total = all;
-  return before + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 // The stages of one tile after the winner and the offsets are known.  Inlined twice, with the four arrays in LDS and in the
 // workspace: each copy addresses them in their own address space (one body behind pointers chosen at run time would read the
 // LDS through flat loads).  sh: {changed, taken} and the scan's wave totals, in LDS.
@@ -113,7 +99,7 @@ __device__ __forceinline__ void rc_tile(const DevParams *P, const TileRef *tiles
     const int k = k0 + tid;
     const bool root = k < N && lab[k] == k;
     int total;
-    const int pos = ncl + rc_block_scan(root, s_wave, &total);
+    const int pos = ncl + block_scan_place<RC_WAVES>(root, s_wave, &total);
     if (root) xy[pos] = (uint32_t)k;
     ncl += total;
   }
@@ -146,7 +132,7 @@ __device__ __forceinline__ void rc_tile(const DevParams *P, const TileRef *tiles
         const int s = s0 + tid;
         const bool keep = s < nr && choice[lab[o + s]] == r;
         int total;
-        const int pos = m + rc_block_scan(keep, s_wave, &total);
+        const int pos = m + block_scan_place<RC_WAVES>(keep, s_wave, &total);
         if (keep && pos < cap) {
           rc.spx[row + pos] = t.px[s]; rc.spy[row + pos] = t.py[s];
           rc.sps[row + pos] = t.ps[s]; rc.spr[row + pos] = t.pr[s]; rc.spa[row + pos] = t.pa[s];
