@@ -159,6 +159,10 @@ extern "C" int mpp_set_option(mpp_ctx *c, const char *name, int64_t v) {
     // an untraced deep round skips the evaluation of a step that re-writes its target with the values it holds (0: it evaluates it)
     if (v < 0 || v > 1) return fail(c, -1, "deep_skip_same must be 0 or 1");
     c->deep_skip_same = (int)v;
+  } else if (!strcmp(name, "deep_carry")) {
+    // an untraced queue round keeps the reports behind its end that stay trustworthy; the next round does not evaluate them (0: it does)
+    if (v < 0 || v > 1) return fail(c, -1, "deep_carry must be 0 or 1");
+    c->deep_carry = (int)v;
   } else return fail(c, -1, "unknown option %s", name);
   return 0;
 }
@@ -198,6 +202,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "hot_past_births")) return c->hp.hot_past;
   if (!strcmp(name, "window_rows")) return c->window_rows;
   if (!strcmp(name, "deep_skip_same")) return c->deep_skip_same;
+  if (!strcmp(name, "deep_carry")) return c->deep_carry;
   // parallel tempering since the last mpp_set_ladder: exchange steps, attempted and accepted pairs, time of their launches
   if (!strcmp(name, "tempering_exchanges")) return c->x_exchanges;
   if (!strcmp(name, "tempering_attempts")) return c->x_attempts;

@@ -276,7 +276,7 @@ int ChainRun::launch_lds() {
     }
     if (pt.word) c->prepass_used = 1;
     if (pt.qoff) c->prepass_queues_used = 1;
-    const int flags = c->deep_skip_same ? MPP_DEEP_SKIP_SAME : 0;
+    const int flags = (c->deep_skip_same ? MPP_DEEP_SKIP_SAME : 0) | (c->deep_carry ? MPP_DEEP_CARRY : 0);
     HIPCHK(c, mpp_launch_deep(a, sh.waves, occ, nmax, fixed, c->deep_gain, flags, (unsigned long long *)c->deep_stats.p, sh.ext, &pt));
   } else {
     // the hot start reads its steps' draws from a table (mpp_hot.hip) where the pre-pass builds one with queues whose words can

@@ -24,6 +24,7 @@
 #define DI_NBOV (1 << 24)    // ... of more than two neighbours (their positions are not all reported)
 #define DI_NB2 (1 << 26)     // ... of at least two neighbours
 #define DI_RESC (1 << 25)    // the evaluation re-reduced a neighbour: it looked two interaction ranges away
+#define DI_KEPT (1 << 27)    // (queue rounds, option deep_carry) the report outlived the round it was made in: see carry_keeps
 
 // a changing report that ends the round when the commit reaches it
 __host__ __device__ __forceinline__ bool commit_terminal(unsigned f) {
@@ -81,4 +82,20 @@ __host__ __device__ __forceinline__ bool commit_conflict(const uint4 &q, const u
       }
     }
   return bad;
+}
+
+// Kept reports (option deep_carry).  A round ends at the first report a committed change makes untrustworthy; the reports
+// behind it are evaluated against the very state the next round starts from, unless a change that committed wrote something
+// they read.  Report o of the window, at offset idx, stays trustworthy for the next round iff
+//   it is valid and does not change the state (a changing step is evaluated again: deep_mutate wants its record);
+//   it lies at or behind the committed count, and is not the report S at which the round ended;
+//   the round committed no birth or death (n and order[] are what o was evaluated against);
+//   commit_conflict(q, qn, o, ...) is false for EVERY changing report q that committed in this round.
+// The last condition arrives as first_q: the lowest offset of a changing report below min(T, first invalid report) that
+// conflicts with o (CARRY_NO_Q: none).  Those are the reports the commit decision tests anyway; every changing report that
+// commits without ending the round is among them, and one of them committed iff its offset is below the committed count.
+// No order is needed here either: first_q is a minimum over pair tests that do not depend on each other.
+#define CARRY_NO_Q 0xffffffffu
+__host__ __device__ __forceinline__ bool carry_keeps(unsigned of, int idx, int committed, int s_end, bool pop_changed, unsigned first_q) {
+  return (of & DI_VALID) && !(of & DI_CHG) && idx >= committed && idx != s_end && !pop_changed && first_q >= (unsigned)committed;
 }

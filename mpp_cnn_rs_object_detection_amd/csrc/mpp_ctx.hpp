@@ -90,6 +90,10 @@ struct mpp_ctx : TileMem {
   // as a flag of mpp_launch_deep, not in DevParams: the block is an argument of every chain kernel, and a field more
   // would move the arguments behind it in kernels this option has nothing to do with
   int deep_skip_same = 1;
+  // deep_carry 1: a queue round keeps the non-changing reports behind its end that no change it committed conflicts with
+  // (carry_keeps, mpp_commit.hpp), and the next round does not evaluate their steps again; 0: every step of a window is
+  // evaluated.  A flag of mpp_launch_deep like deep_skip_same, for the same reason
+  int deep_carry = 1;
   DevWs deep_stats;
   // the birth pre-pass of a deep launch (mpp_prepass.hip): prepass 1 on, 0 off (the chains draw their births themselves);
   // a launch whose table would exceed prepass_mb MB runs without one; prepass_used: a deep launch of the last call used one

@@ -472,10 +472,13 @@ __device__ __forceinline__ bool deep_same_values(const Lds &L, const Rec &r) {
   const int sl = r.tslot;
   return r.ax == r.rx && r.ay == r.ry && r.as == L.s[sl] && r.ar == L.r[sl] && r.aa == L.a[sl];
 }
+// (QUE) the place of the report of the step at offset `off` of the round that starts at step `done`: by the step, so that a
+// kept report is found by whichever lane gets its step in the next round (nmax: a power of two)
+__device__ __forceinline__ int deep_slot(long long done, int off, int nmax) { return ((int)done + off) & (nmax - 1); }
 __device__ __forceinline__ unsigned long long low_mask(int k) { return k <= 0 ? 0ull : (k >= 64 ? ~0ull : ((1ull << k) - 1ull)); }
 
 // (QUE) The fields of a step that the neighbour pass does not read wait in LDS while it runs, in space of the step's own
-// offset that nothing else uses at that time: u_acc and qf in its report D.info[off], qb in D.nb[off] (both are written only
+// own that nothing else uses at that time: u_acc and qf in its report D.info[slot], qb in D.nb[slot] (both are written only
 // after deep_post, and every wave has finished reading the previous round's reports before barrier (1)); lin_a and gate_a
 // in D.pw[off] (the queue rounds sort nothing: no Philox words), where they stay until deep_mutate writes the slot.
 __device__ __forceinline__ uint4 pack_dd(double a, double b) {
@@ -483,15 +486,17 @@ __device__ __forceinline__ uint4 pack_dd(double a, double b) {
   return make_uint4((unsigned)x, (unsigned)(x >> 32), (unsigned)y, (unsigned)(y >> 32));
 }
 __device__ __forceinline__ double unpack_d(unsigned lo, unsigned hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); }
-__device__ __forceinline__ void deep_park(const DeepLds &D, int off, const Rec &r) {
-  D.info[off] = pack_dd(r.u_acc, r.qf);
-  D.nb[off] = pack_dd(r.qb, 0.0);
+// D.info and D.nb are indexed by the step (`slot`, see deep_slot), D.pw by the offset; the last word of D.pw[off] is the
+// round's first_q of the report at that offset (carry_keeps, mpp_commit.hpp): none yet.
+__device__ __forceinline__ void deep_park(const DeepLds &D, int slot, int off, const Rec &r) {
+  D.info[slot] = pack_dd(r.u_acc, r.qf);
+  D.nb[slot] = pack_dd(r.qb, 0.0);
   const uint4 l = pack_dd(r.lin_a, 0.0);
-  D.pw[off] = make_uint4(l.x, l.y, (unsigned)r.gate_a, 0u);
+  D.pw[off] = make_uint4(l.x, l.y, (unsigned)r.gate_a, CARRY_NO_Q);
 }
-__device__ __forceinline__ void deep_unpark_green(const DeepLds &D, int off, Rec &r) {
-  const uint4 a = D.info[off];
-  const uint2 b = *(const uint2 *)(D.nb + off);
+__device__ __forceinline__ void deep_unpark_green(const DeepLds &D, int slot, Rec &r) {
+  const uint4 a = D.info[slot];
+  const uint2 b = *(const uint2 *)(D.nb + slot);
   r.u_acc = unpack_d(a.x, a.y); r.qf = unpack_d(a.z, a.w); r.qb = unpack_d(b.x, b.y);
 }
 __device__ __forceinline__ void deep_unpark_unit(const DeepLds &D, int off, Rec &r) {
@@ -529,6 +534,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   static_assert(!QUE || (TAB && WAVES == 8), "the queues are dealt to eight waves");
   const bool by_type = (gain8 & 0x100) == 0;      // (bit 8 of the gain word: deal the sorted steps in blocks instead -- A/B tests)
   const bool skip_opt = (flags & MPP_DEEP_SKIP_SAME) != 0;        // (option deep_skip_same)
+  const bool carry_opt = QUE && (flags & MPP_DEEP_CARRY) != 0;    // (option deep_carry; the queue rounds only)
   gain8 &= 0xff;
   const DevParams *P = stage_params<(WAVES >= MPP_LDS_PARAMS_MIN_WAVES)>(Pv, WAVE * WAVES);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -552,6 +558,13 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   // or not, and in an untraced chain nothing reads its dE, its densities or its accept bit: such a step is not evaluated.
   // A traced chain records them for every step: it never skips.
   const bool skip_same = skip_opt && !tracing;
+  // (QUE) A report behind the end of a round that no change the round committed conflicts with is the report the next round
+  // would write again (carry_keeps, mpp_commit.hpp): phase C marks it DI_KEPT, and the lane that gets its step in the next
+  // round leaves it as it is.  For a step to find its report whichever lane gets it, the queue rounds index D.info and D.nb
+  // by the step (deep_slot: nmax is a power of two and a window has at most nmax steps), not by the offset in the round.
+  // The bit is set by phase C alone, which re-writes it for all nmax entries every round: clear at launch, it is set on
+  // entry to a round exactly for the kept reports of the round before.  A traced chain never keeps, as it never skips.
+  const bool carry = carry_opt && !tracing;
 
   // ---------------------------------------------------------------- load the configuration (as mpp_chain_kernel does)
   int n0 = __builtin_amdgcn_readfirstlane(*c.t.n);
@@ -565,6 +578,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   for (int i = tid; i < rowbase_n; i += nthr) L.rowbase[i] = c.t.rowbase[i];
   for (int i = tid; i < cap; i += nthr) L.order[i] = (unsigned short)i;
   for (int i = tid; i < ncell; i += nthr) L.cell_cnt[i] = 0;
+  if constexpr (QUE) for (int i = tid; i < nmax; i += nthr) D.info[i].x = 0u;       // no report is kept
   __syncthreads();
   for (int i = tid; i < n0; i += nthr) {
     Rect q{c.t.px[i], c.t.py[i], c.t.ps[i], c.t.pr[i], c.t.pa[i]};
@@ -630,7 +644,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
   int depth = WAVES, ema16 = WAVES * 16;        // steps of the next round; committed steps per round, x16, smoothed
   unsigned long long st_rounds = 0, st_eval = 0, st_apply = 0;
 #ifdef MPP_DEEP_PROF
-  unsigned long long dph_[DPH_N] = {0}, dph_t_ = 0;
+  unsigned long long dph_[DPH_N] = {0}, dph_t_ = 0, dph_fresh = 0;      // (dph_fresh: steps this wave evaluated afresh)
 #endif
 
   // The loop alternates between two stages that share the call of eval_delta_lane: stage 1 draws and evaluates a round's
@@ -734,7 +748,10 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       r.ax = r.ay = r.rx = r.ry = 0; r.pid = -1; r.ncls = -1; r.acls = 0; r.n_stash = 0; r._pad2 = 0; r.gate_a = 1;
       r.as = r.ar = r.aa = r.aux0 = r.aux1 = r.u_acc = r.qf = r.qb = r.dE = 0.0;
       r.hl = r.hw = r.ca = r.sa = r.rad = r.lin_a = r.ra0 = r.ra1 = 0.0;
-      if (mine) {
+      const int myslot = deep_slot(done, myoff, nmax);
+      // (a kept report: the lane behaves as one whose step re-writes its target unchanged, and leaves the report untouched)
+      if (mine && carry && (D.info[myslot].x & DI_KEPT)) same = true;
+      else if (mine) {
         r.valid = 1;
         int keep = 0;
         const bool pre_b = kq == MPP_K_UBIRTH || kq == MPP_K_DBIRTH;      // a birth: the table has it all
@@ -748,8 +765,12 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
           deep_add_geo(c, r, keep);
           deep_pre<false>(c, r, keep, tracing, pmv, nullptr);
         }
-        if (!same) deep_park(D, myoff, r);
+        if (!same) deep_park(D, myslot, myoff, r);
       }
+      if (carry && same) D.pw[myoff].w = CARRY_NO_Q;      // (an evaluated lane parked it)
+#ifdef MPP_DEEP_PROF
+      if (stats) { const int nf = __popcll(__ballot(mine && !(same && r.valid == 0))); if (c.lane == 0) dph_fresh += (unsigned long long)nf; }
+#endif
       do_eval = mine && r.valid && (r.has_rem || r.has_add) && !same;
       DPH(4);
     } else {
@@ -938,7 +959,9 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
     }
     DPH(stage == 1 ? 5 : 9);
     if (stage == 1) {
-    if (mine) {
+    const int myslot = QUE ? deep_slot(done, myoff, nmax) : myoff;       // where my report goes
+    // (a lane that did not evaluate re-reads the bit: no flag of its own lives through the neighbour pass)
+    if (mine && !(carry && same && (D.info[myslot].x & DI_KEPT))) {
       // the step's temperature: its ring entry stays as it is while the step is in the window (the ring is filled two rounds ahead)
       const double Tm = D.tring[(int)((done + myoff) & (long long)rmask)];
       // (a skipped step: nothing was parked for it, and no test is made.  Its report below is the one an evaluated re-write
@@ -946,7 +969,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       // removed one's bits and takes every extremum over; the reach radius from the target's cache, r.rad being 0 -- except
       // for DI_ACC, which the commit decision does not read: the bit stays clear, r.accepted is 0 from the round's reset.)
       if (!same) {
-        if constexpr (QUE) deep_unpark_green(D, myoff, r);
+        if constexpr (QUE) deep_unpark_green(D, myslot, r);
         if (r.valid) deep_post(c, r, n, Tm, tracing);
       }
       // does the step change the configuration?  An accepted move that writes the values the slot already holds does not
@@ -965,13 +988,13 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       const int f = (r.tslot & 0xffff) | (r.valid ? DI_VALID : DI_BAD) | (chg ? DI_CHG : 0) | (r.has_rem ? DI_HR : 0) |
                     (r.has_add ? DI_HA : 0) | (r.accepted ? DI_ACC : 0) | (full ? DI_FULL : 0) | (chg && r.n_stash > 0 ? DI_NB : 0) |
                     (chg && r.n_stash > 1 ? DI_NB2 : 0) | (chg && r.n_stash > 2 ? DI_NBOV : 0) | (r.valid && r._pad2 > 0 ? DI_RESC : 0);
-      D.info[myoff] = make_uint4((unsigned)f, (unsigned)((r.rx & 0xffff) | (r.ry << 16)), (unsigned)((r.ax & 0xffff) | (r.ay << 16)),
+      D.info[myslot] = make_uint4((unsigned)f, (unsigned)((r.rx & 0xffff) | (r.ry << 16)), (unsigned)((r.ax & 0xffff) | (r.ay << 16)),
                                  (unsigned)(ci_r | (cj_r << 8) | (ci_a << 16) | (cj_a << 24)));
       // circumradius (rounded up, at most 255) of the largest rectangle the step removes or adds: how far its overlap term reaches
       double rr = r.has_add ? r.rad : 0.0;
       if (r.has_rem) { const double r0_ = L.rad[r.tslot]; rr = r0_ > rr ? r0_ : rr; }
       const int own_r = rr < 254.0 ? (int)ceil(rr) : 255;
-      D.nb[myoff] = make_uint4((unsigned)nb0, (unsigned)nb1, (unsigned)nbr, (unsigned)own_r);
+      D.nb[myslot] = make_uint4((unsigned)nb0, (unsigned)nb1, (unsigned)nbr, (unsigned)own_r);
     }
     // temperatures of the steps that entered the window with the PREVIOUS round's commit (the ring is two rounds ahead; wave 0
     // runs the cheapest kernels and would wait at the barrier anyway): one multiply per step, in step order, as the chain does
@@ -1005,7 +1028,8 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       if (ch < nch) {
         const int idx = ch * 64 + c.lane;
         const bool in = idx < lim;
-        if (in) { o_[ch] = D.info[idx]; or_[ch] = (int)D.nb[idx].w; }
+        const int sl = QUE ? deep_slot(done, idx, nmax) : idx;
+        if (in) { o_[ch] = D.info[sl]; or_[ch] = (int)D.nb[sl].w; }
         const unsigned f = o_[ch].x;
         am_[ch] = __ballot(in && (f & DI_CHG));
         const unsigned long long bm = __ballot(in && !(f & DI_VALID)), tm = __ballot(in && commit_terminal(f));
@@ -1051,16 +1075,19 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
           if ((wq >> 6) == ch)
             q = make_uint4((unsigned)__builtin_amdgcn_readlane((int)o_[ch].x, wq & 63), (unsigned)__builtin_amdgcn_readlane((int)o_[ch].y, wq & 63),
                            (unsigned)__builtin_amdgcn_readlane((int)o_[ch].z, wq & 63), (unsigned)__builtin_amdgcn_readlane((int)o_[ch].w, wq & 63));
-        const uint4 qn = D.nb[wq];
+        const uint4 qn = D.nb[QUE ? deep_slot(done, wq, nmax) : wq];
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
-          // (the chunks behind q, and not beyond what is known to end the round)
-          if (ch < nch && ch * 64 + 63 > wq && ch * 64 < s_end && ch * 64 <= bound) {
+          // (the chunks behind q; for the end of the round not beyond what is known to end it; for the kept reports all of
+          // them: every report q conflicts with notes the lowest such q in its first_q word)
+          const bool for_end = ch * 64 < s_end && ch * 64 <= bound;
+          if (ch < nch && ch * 64 + 63 > wq && (for_end || carry)) {
             const int idx = ch * 64 + c.lane;
             bool bad = false;
             if (idx > wq && (o_[ch].x & DI_VALID)) bad = commit_conflict(q, qn, o_[ch], or_[ch], range2, far2, c.pr1.maxd2);
+            if constexpr (QUE) { if (carry && bad) atomicMin(&D.pw[idx].w, (unsigned)wq); }
             const unsigned long long b = __ballot(bad);
-            if (b) { const int o = ch * 64 + __ffsll((long long)b) - 1; s_end = o < s_end ? o : s_end; }
+            if (for_end && b) { const int o = ch * 64 + __ffsll((long long)b) - 1; s_end = o < s_end ? o : s_end; }
           }
         }
       }
@@ -1095,6 +1122,31 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
       committed = s_end;
       if (s_end < lim && (flags_at(s_end) & DI_BAD)) err = ERR_BAD_TARGET;
       // otherwise: invalidated by an earlier commit of this round -> evaluated again next round
+    }
+    if constexpr (QUE) {
+      // the kept reports of the next round: wave ch re-writes the bit of chunk ch, in and behind the window (a window may be
+      // shorter than the one before).  A round without a relevant changing step has no barrier (5) -- it commits its whole
+      // window, or ends at a birth / death, or stops the chain, and has nothing to keep that a later round would use: a wave
+      // that still loads its chunks sees the bit either way, and nothing in this phase reads it.  (first_q: the words are
+      // complete after barrier (5), and without one nothing was noted.)
+      if (carry) {
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch)
+          if (c.wave == ch && ch * 64 < nmax) {
+            const int idx = ch * 64 + c.lane;
+            unsigned *w = &D.info[deep_slot(done, idx, nmax)].x;
+            if (idx < lim) {
+              const unsigned of = o_[ch].x;
+              bool keep = false;
+              if (idx >= committed) keep = carry_keeps(of, idx, committed, s_end, cur_n != n, D.pw[idx].w);
+              const unsigned nf = keep ? (of | DI_KEPT) : (of & ~(unsigned)DI_KEPT);
+              if (nf != of) *w = nf;
+            } else if (idx < nmax) {
+              const unsigned of = *w;
+              if (of & DI_KEPT) *w = of & ~(unsigned)DI_KEPT;
+            }
+          }
+      }
     }
     bool any_commit = false, any_apply = false;     // a step commits with a change; ... and changes reductions of neighbours
 #pragma unroll
@@ -1186,6 +1238,7 @@ __global__ __launch_bounds__(WAVE *WAVES, OCC) void mpp_deep_kernel(const DevPar
 #ifdef MPP_DEEP_PROF
   if (c.lane == 0) for (int i = 0; i < 3; ++i) dph_[20 + i] = atomicExch(&g_win_clk[c.wave * 3 + i], 0ull);   // (one chain per launch: the probe's)
   if (stats && c.lane == 0) for (int i = 0; i < DPH_N; ++i) atomicAdd(stats + 16 + DPH_N * c.wave + i, dph_[i]);
+  if (stats && c.lane == 0) atomicAdd(stats + 4, dph_fresh);
 #endif
   if (tid == 0) {
     long long start = 0;                        // (QUE) where in the table this launch started
@@ -1204,7 +1257,7 @@ extern "C" size_t mpp_deep_lds_bytes(int cap, int ncell, int cell_cap, int rowba
 template <int WAVES, bool DIAG, int OCC, bool EXT, bool TAB, bool QUE = false, int NCH = DEEP_NMAX_LIMIT / 64>
 static hipError_t launch_deep_d(const ChainLaunch &a, int nmax, int fixed_depth, int gain8, int flags,
                                 unsigned long long *stats, const PreTab &pt) {
-  if (nmax > 64 * NCH) return hipErrorInvalidValue;
+  if (nmax > 64 * NCH || (nmax & (nmax - 1))) return hipErrorInvalidValue;     // (a power of two: the ring's mask, deep_slot)
   hipError_t e = hipFuncSetAttribute((const void *)mpp_deep_kernel<WAVES, DIAG, OCC, EXT, TAB, QUE, NCH>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds);
   if (e != hipSuccess) return e;
@@ -1218,7 +1271,8 @@ static hipError_t launch_deep_d(const ChainLaunch &a, int nmax, int fixed_depth,
 // pt: the launch's birth table (mpp_prepass.hip), or pt->word == nullptr: the chains draw their births themselves; with
 // pt->qoff, eight waves and the cost deal (gain8 without bit 8), the rounds take their steps from the table's queues
 // flags: MPP_DEEP_SKIP_SAME: an untraced chain does not evaluate the steps that re-write their target unchanged (option
-// deep_skip_same)
+// deep_skip_same); MPP_DEEP_CARRY: an untraced chain in queue rounds keeps the reports behind a round's end that stay
+// trustworthy, and does not evaluate their steps again (option deep_carry)
 // (a.tape is not read: deep rounds draw their proposals from Philox)
 extern "C" hipError_t mpp_launch_deep(const ChainLaunch &a, int waves, int occ, int nmax, int fixed_depth, int gain8, int flags,
                                       unsigned long long *stats, int ext, const PreTab *pt) {

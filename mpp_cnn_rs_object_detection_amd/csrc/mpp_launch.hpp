@@ -69,6 +69,7 @@ struct MinSel {
 
 // flags of mpp_launch_deep
 #define MPP_DEEP_SKIP_SAME 1                       // option deep_skip_same: steps that re-write their target unchanged are not evaluated
+#define MPP_DEEP_CARRY 2                           // option deep_carry: the queue rounds keep the reports no commit of the round touched
 
 extern "C" {
 size_t mpp_chain_lds_bytes(int cap, int ncell, int cell_cap, int spec, int rowbase_n, int waves);

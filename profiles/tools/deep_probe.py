@@ -40,6 +40,7 @@ def run(tile, objects, iters, spec, deep, fixed, reps, ntiles=1, cap=1024, repli
         # (C of a round whose changing steps are dealt: "C:set-up+pairs" up to the exchange, "C:bar5" the wait at its barrier,
         # the rest -- the rule, tracing, the queues' cursors -- under "C:decide+trace+ring"; a round without: all of it there)
         R = max(1, st["rounds"])
+        st["fresh"] = ctx.get_option("deep_stat4")       # steps evaluated afresh: the windows' steps without the kept reports (queue rounds)
         st["phase_cycles_per_round"] = {}
         for w in range(spec):
             ph = [ctx.get_option(f"deep_stat{16 + 24 * w + i}") for i in range(len(names))]
