@@ -189,7 +189,7 @@ extern "C" int mpp_birth_energy_map(mpp_ctx *c, double *dE, double *marks, mpp_b
 
 // The first block of a selection and its workspace (mpp_birth_complete.hip)
 static int minsel_setup(mpp_ctx *c, MinSel *s, const double *dE, size_t chain_stride, int T, int H, int W, int ld, double below,
-                        double distance, const mpp_complete_report *rep) {
+                        double distance, const mpp_descent_report *rep) {
   *s = MinSel{};
   s->dE = dE; s->chain_stride = chain_stride; s->H = H; s->W = W; s->ld = ld; s->n_chains = T;
   s->below = below; s->d2 = distance * distance;
@@ -288,18 +288,13 @@ extern "C" int mpp_select_points(mpp_ctx *c, int n, const int32_t *xy, const dou
 
 // The rounds of mpp_descend and of mpp_birth_complete (what = births: DESIGN.md sections 13 and 16), from the refusal of too many
 // chains to the round that closes the last chain.  Per round: the launches of the Papangelou pass, of the selection among
-// points and of the removal; those of one round of the completion; the round's book; one copy of the chains' reports to
-// report [n_chains].  The point lists and the maps stay on the device.  `who` names the caller and `noun` its workspace in the
-// messages.  What it leaves for the caller's tail: the workspace, whether the last Papangelou values (the last map) are not
-// those of the returned state, and the map summary's workspace.
-struct DescentRounds {
-  Descent d;
-  bool stale_p, stale_map;
-  BirthPart *part;
-  mpp_birth_summary *d_sum;
-};
-static int descent_rounds(mpp_ctx *c, const char *who, const char *noun, int what, int max_rounds, double min_gain,
-                          mpp_descent_report *report, DescentRounds *out) {
+// points and of the removal; those of the map, of the selection of its minima and of their append; the round's book (the one
+// record a chain has, its descent report); one copy of the chains' reports to report [n_chains].  The point lists and the maps
+// stay on the device.  `who` names the caller and `noun` its workspace in the messages.  Then the tail: the Papangelou values
+// and the map of the returned state, each recomputed only when the last one is not that state's, and their summaries.  The
+// completion (values = false) takes neither a Papangelou pass nor a value of d.p, which nothing has filled for it.
+static int descent_rounds(mpp_ctx *c, const char *who, const char *noun, int what, bool values, int max_rounds, double min_gain,
+                          mpp_descent_report *report, int32_t *src) {
   const bool deaths = what & MPP_DESCEND_DEATHS, births = what & MPP_DESCEND_BIRTHS;
   const int T = c->n_tiles, H = c->H, W = c->W;
   if (T > 65535) return fail(c, -1, "%s: %d chains, at most 65535", who, T);
@@ -308,19 +303,18 @@ static int descent_rounds(mpp_ctx *c, const char *who, const char *noun, int wha
   const size_t hw = births ? (size_t)H * W : 0;
   if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, hw)) != hipSuccess)
     return fail(c, -2, "no device memory for the %s of %d chains", noun, T);
-  Descent &d = out->d;
+  Descent d;
   mpp_descent_plan(&d, T, c->cap, hw, c->descent_ws.p);
   const double reach = 2.0 * c->hp.max_inter;
   MinSel s{};
-  if (births && (rc = minsel_setup(c, &s, d.dE, hw, T, H, W, W, -min_gain, reach, d.crep))) return rc;
+  if (births && (rc = minsel_setup(c, &s, d.dE, hw, T, H, W, W, -min_gain, reach, d.rep))) return rc;
   PtSel ps{};
   ps.tiles = c->d_tiles; ps.n_chains = T; ps.cap = c->cap; ps.val = d.p; ps.keep = d.keep; ps.pitch = (size_t)c->cap;
-  ps.above = min_gain; ps.d2 = reach * reach; ps.closed = d.crep;
-  mpp_launch_complete_init(c->stream, T, d.crep);
+  ps.above = min_gain; ps.d2 = reach * reach; ps.closed = d.rep;
   mpp_launch_descent_init(c->stream, c->d_tiles, d);
-  out->part = nullptr; out->d_sum = nullptr;
-  out->stale_p = !deaths; out->stale_map = false;
-  bool open = true;
+  BirthPart *part = nullptr;
+  mpp_birth_summary *d_sum = nullptr;
+  bool stale_p = !deaths, stale_map = false, open = true;
   std::vector<int32_t> was(T, -1);
   // (a chain is open for at most max_rounds rounds that change it and the one that closes it)
   for (int round = 0; round <= max_rounds && open; ++round) {
@@ -330,11 +324,11 @@ static int descent_rounds(mpp_ctx *c, const char *who, const char *noun, int wha
       mpp_launch_descent_remove(c->stream, c->d_tiles, d);
     }
     if (births) {
-      if ((rc = birth_map_launches(c, who, d.dE, nullptr, &out->part, &out->d_sum))) return rc;
+      if ((rc = birth_map_launches(c, who, d.dE, nullptr, &part, &d_sum))) return rc;
       mpp_launch_minsel(c->stream, s);
-      mpp_launch_complete_round(c->stream, s, c->dp, c->d_tiles, c->cap, d.gain_val, 1 << 30, d.crep);
+      mpp_launch_complete_append(c->stream, s, c->dp, c->d_tiles, c->cap, d.gain_val);
     }
-    mpp_launch_descent_round(c->stream, c->d_tiles, d, what, max_rounds);
+    mpp_launch_descent_round(c->stream, c->d_tiles, d, what, max_rounds, s.n_kept);   // (s.n_kept: nullptr without births)
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(report, d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
@@ -344,11 +338,23 @@ static int descent_rounds(mpp_ctx *c, const char *who, const char *noun, int wha
       const int st = report[t].status;
       open = open || st < 0;
       // a chain that changed in the round that closed it: its last Papangelou values (its last map) are not its state's
-      if (was[t] < 0 && st > 0) { out->stale_p = true; out->stale_map = out->stale_map || st == 1; }
+      if (was[t] < 0 && st > 0) { stale_p = true; stale_map = stale_map || st == 1; }
       was[t] = st;
     }
   }
   if (open) return fail(c, -9, "%s: a chain is still open after %d rounds", who, max_rounds + 1);
+  if (!values) d.p = nullptr;                                    // (k_descent_summary then skips its reduction)
+  else if (stale_p && (rc = papangelou_launches(c, d.p, noun))) return rc;
+  if (births) {
+    if (stale_map && (rc = birth_map_launches(c, who, d.dE, nullptr, &part, &d_sum))) return rc;
+    mpp_launch_birth_summary(c->stream, T, H, W, d.dE, part, d_sum);
+  }
+  mpp_launch_descent_summary(c->stream, c->d_tiles, d, d_sum);   // (d_sum: nullptr without births)
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(report, d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && src) e = hipMemcpyAsync(src, d.src, (size_t)T * c->cap * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
   return 0;
 }
 
@@ -359,10 +365,8 @@ static int rounds_refusals(mpp_ctx *c, const char *who, int max_rounds, double m
   return 0;
 }
 
-// Greedy completion: the births-only rounds of the descent, whose birth half keeps the completion's
-// book in d.crep -- k_complete_round books the appends with no round limit, k_descent_round applies max_rounds and writes the
-// status back, so status, rounds, n_added, n_after and gain are what a loop over k_complete_round alone would leave.  The tail
-// is the completion's own: the summary of the returned state's map, and no Papangelou pass.
+// Greedy completion: the births-only form of the descent, without its Papangelou values; the caller's
+// records are filled from the chains' descent reports.
 extern "C" int mpp_birth_complete(mpp_ctx *c, int max_rounds, double min_gain, mpp_complete_report *report) {
   if (!c) return -1;
   int rc = birth_refusals(c, "birth_complete");
@@ -371,16 +375,12 @@ extern "C" int mpp_birth_complete(mpp_ctx *c, int max_rounds, double min_gain, m
   if ((rc = rounds_refusals(c, "birth_complete", max_rounds, min_gain))) return rc;
   const int T = c->n_tiles;
   std::vector<mpp_descent_report> book(T > 0 ? T : 1);
-  DescentRounds r;
-  if ((rc = descent_rounds(c, "birth_complete", "maps", MPP_DESCEND_BIRTHS, max_rounds, min_gain, book.data(), &r))) return rc;
-  // the last map is that of every chain but those its round stopped at the limit
-  if (r.stale_map && (rc = birth_map_launches(c, "birth_complete", r.d.dE, nullptr, &r.part, &r.d_sum))) return rc;
-  mpp_launch_birth_summary(c->stream, T, c->H, c->W, r.d.dE, r.part, r.d_sum);
-  mpp_launch_complete_summary(c->stream, T, r.d_sum, r.d.crep);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(report, r.d.crep, (size_t)T * sizeof(mpp_complete_report), hipMemcpyDeviceToHost, c->stream);
-  hipError_t e2 = hipStreamSynchronize(c->stream);
-  HIPCHK(c, e); HIPCHK(c, e2);
+  if ((rc = descent_rounds(c, "birth_complete", "maps", MPP_DESCEND_BIRTHS, false, max_rounds, min_gain, book.data(), nullptr)))
+    return rc;
+  for (int t = 0; t < T; ++t) {
+    const mpp_descent_report &b = book[t];
+    report[t] = mpp_complete_report{b.status, b.rounds, b.n_added, b.n_after, b.gain_births, b.min_dE, b.x, b.y, b.n_negative, b.n_nan};
+  }
   return 0;
 }
 
@@ -396,21 +396,7 @@ extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain
   for (int p = 0; p < c->hp.model.n_pair; ++p)                   // (a round's gains add up only under an order-free reduction)
     if (c->hp.model.pair[p].reduce != MPP_REDUCE_MAX && c->hp.model.pair[p].reduce != MPP_REDUCE_MIN)
       return fail(c, -1, "descend: pair term %d has a reduction that is neither max nor min", p);
-  DescentRounds r;
-  if ((rc = descent_rounds(c, "descend", "descent", what, max_rounds, min_gain, report, &r))) return rc;
-  const int T = c->n_tiles;
-  if (r.stale_p && (rc = papangelou_launches(c, r.d.p, "descent"))) return rc;
-  if (births) {
-    if (r.stale_map && (rc = birth_map_launches(c, "descend", r.d.dE, nullptr, &r.part, &r.d_sum))) return rc;
-    mpp_launch_birth_summary(c->stream, T, c->H, c->W, r.d.dE, r.part, r.d_sum);
-  }
-  mpp_launch_descent_summary(c->stream, c->d_tiles, r.d, births ? r.d_sum : nullptr);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(report, r.d.rep, (size_t)T * sizeof(mpp_descent_report), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && src) e = hipMemcpyAsync(src, r.d.src, (size_t)T * c->cap * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
-  hipError_t e2 = hipStreamSynchronize(c->stream);
-  HIPCHK(c, e); HIPCHK(c, e2);
-  return 0;
+  return descent_rounds(c, "descend", "descent", what, true, max_rounds, min_gain, report, src);
 }
 
 // shared body of mpp_delta_batch (dE != NULL) and mpp_delta_vectors (before/after/mask != NULL)

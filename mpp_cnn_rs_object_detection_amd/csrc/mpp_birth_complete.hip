@@ -1,5 +1,5 @@
-// mpp_birth_complete.hip -- the selection of a map's local minima (mpp_select_minima) and the greedy completion that acts on
-// the birth-energy map with it (mpp_birth_complete): DESIGN.md section 13.
+// mpp_birth_complete.hip -- the selection of a map's local minima (mpp_select_minima) and the append of the kept ones, the birth
+// half of a round of mpp_birth_complete and mpp_descend (the round's book is k_descent_round's): DESIGN.md section 13.
 //
 //   candidates  the pixels with dE < below, compacted by ballot into a list in row-major order: a count per block of
 //               MINSEL_SPAN pixels, an exclusive scan of the counts, the same ballots again to fill;
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(MINSEL_THREADS) void k_minsel_compact(MinSel s) {
   const int chain = blockIdx.y, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
   const long long hw = (long long)s.H * s.W;
   const double *d = s.dE + (size_t)chain * s.chain_stride;
-  const bool closed = minsel_closed(s, chain);                 // (a finished chain of the completion has no candidates)
+  const bool closed = minsel_closed(s, chain);                 // (a closed chain of the descent has no candidates)
   const size_t lbase = (size_t)chain * hw;
   int at = FILL ? s.cblk[(size_t)chain * s.nb_fill + blockIdx.x] : 0;      // (after the scan: where this block's run starts)
   int mine = 0;
@@ -194,17 +194,8 @@ __global__ __launch_bounds__(MINSEL_THREADS) void k_minsel_emit(MinSel s, int ou
 }
 
 // ---- the completion ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVE) void k_complete_init(int n_chains, mpp_complete_report *rep) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_chains) return;
-  mpp_complete_report r;
-  r.status = -1; r.rounds = 0; r.n_added = 0; r.n_after = 0; r.gain = 0.0; r.min_dE = 0.0; r.x = -1; r.y = -1;
-  r.n_negative = 0; r.n_nan = 0;
-  rep[c] = r;
-}
-
 // The kept candidates of an open chain go behind its configuration, slot n + place, when all of them fit; their values go to
-// gain_val [n_chains][cap] by place, for the sum k_complete_round forms.  The count itself is k_complete_round's to change.
+// gain_val [n_chains][cap] by place, for the sum k_descent_round forms.  The count itself is k_descent_round's to change.
 __global__ __launch_bounds__(MINSEL_THREADS) void k_complete_append(MinSel s, const DevParams *P, const TileRef *tiles, int cap,
                                                                     double *gain_val) {
   __shared__ int s_w[MINSEL_WAVES];
@@ -223,38 +214,6 @@ __global__ __launch_bounds__(MINSEL_THREADS) void k_complete_append(MinSel s, co
   gain_val[(size_t)chain * cap + pos] = v;
 }
 
-// one lane per chain: the round's outcome.  The appended values are added in slot order, one after another.
-__global__ __launch_bounds__(WAVE) void k_complete_round(int n_chains, const TileRef *tiles, int cap, const int32_t *n_kept, const double *gain_val,
-                                 int max_rounds, mpp_complete_report *rep) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_chains) return;
-  mpp_complete_report r = rep[c];
-  if (r.status >= 0) return;
-  TileRef t = tiles[c];
-  int n = *t.n;
-  const int k = n_kept[c];
-  if (k == 0) r.status = 0;
-  else if (n < 0 || k > cap - n) r.status = 2;
-  else {
-    double g = r.gain;
-    for (int i = 0; i < k; ++i) g += gain_val[(size_t)c * cap + i];
-    r.gain = g;
-    n += k;
-    *t.n = n; *t.err = 0;                                      // (what mpp_set_points of the longer list leaves)
-    r.rounds += 1; r.n_added += k;
-    if (r.rounds >= max_rounds) r.status = 1;
-  }
-  r.n_after = n;
-  rep[c] = r;
-}
-
-__global__ __launch_bounds__(WAVE) void k_complete_summary(int n_chains, const mpp_birth_summary *sum, mpp_complete_report *rep) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_chains) return;
-  const mpp_birth_summary s = sum[c];
-  rep[c].min_dE = s.min_dE; rep[c].x = s.x; rep[c].y = s.y; rep[c].n_negative = s.n_negative; rep[c].n_nan = s.n_nan;
-}
-
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 extern "C" void mpp_launch_minsel(hipStream_t st, const MinSel &s) {
   if (s.n_chains <= 0) return;
@@ -270,18 +229,7 @@ extern "C" void mpp_launch_minsel_emit(hipStream_t st, const MinSel &s, int out_
   if (s.n_chains <= 0 || out_cap <= 0) return;
   hipLaunchKernelGGL(k_minsel_emit, dim3(s.nb_res, s.n_chains), dim3(MINSEL_THREADS), 0, st, s, out_cap, xy, values);
 }
-extern "C" void mpp_launch_complete_init(hipStream_t st, int n_chains, mpp_complete_report *rep) {
-  if (n_chains <= 0) return;
-  hipLaunchKernelGGL(k_complete_init, dim3((n_chains + WAVE - 1) / WAVE), dim3(WAVE), 0, st, n_chains, rep);
-}
-extern "C" void mpp_launch_complete_round(hipStream_t st, const MinSel &s, const DevParams *P, const TileRef *tiles, int cap,
-                                          double *gain_val, int max_rounds, mpp_complete_report *rep) {
+extern "C" void mpp_launch_complete_append(hipStream_t st, const MinSel &s, const DevParams *P, const TileRef *tiles, int cap, double *gain_val) {
   if (s.n_chains <= 0) return;
   hipLaunchKernelGGL(k_complete_append, dim3(s.nb_res, s.n_chains), dim3(MINSEL_THREADS), 0, st, s, P, tiles, cap, gain_val);
-  hipLaunchKernelGGL(k_complete_round, dim3((s.n_chains + WAVE - 1) / WAVE), dim3(WAVE), 0, st, s.n_chains, tiles, cap,
-                     (const int32_t *)s.n_kept, (const double *)gain_val, max_rounds, rep);
-}
-extern "C" void mpp_launch_complete_summary(hipStream_t st, int n_chains, const mpp_birth_summary *sum, mpp_complete_report *rep) {
-  if (n_chains <= 0) return;
-  hipLaunchKernelGGL(k_complete_summary, dim3((n_chains + WAVE - 1) / WAVE), dim3(WAVE), 0, st, n_chains, sum, rep);
 }

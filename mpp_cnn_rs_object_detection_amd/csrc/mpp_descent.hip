@@ -6,23 +6,21 @@
 //   remove    one workgroup per chain: the kept points leave by stable compaction in place, in ascending chunks of
 //             DESC_THREADS slots.  A chunk is read whole before any of it is written and a destination never passes its
 //             source, so no second copy of the state is needed.  The removed values go to a list in slot order;
-//   round     one lane per chain books the round: the removed values and the births' gain are added one after another;
+//   round     one lane per chain books the round in the chain's one record, its descent report (descent_book, mpp_round.hpp);
 //   summary   the largest Papangelou value of the returned state, its first slot and the count of positive ones.
-// The birth half is the completion's (mpp_birth_complete.hip), the Papangelou values are k_papangelou_tiles' (mpp_scratch.hip).
+// The birth half's selection and append are mpp_birth_complete.hip's, the Papangelou values k_papangelou_tiles' (mpp_scratch.hip).
 #include <cmath>
 
 #include "mpp_device.hpp"
 #include "mpp_launch.hpp"
+#include "mpp_round.hpp"
 
 #define DESC_THREADS 256
 #define DESC_WAVES (DESC_THREADS / WAVE)
 
-static size_t desc_up8(size_t b) { return (b + 7) & ~(size_t)7; }
-
 extern "C" size_t mpp_descent_bytes(int n_chains, int cap, size_t hw) {
   const size_t T = (size_t)n_chains, TC = T * cap;
-  return (3 * TC + T * hw) * sizeof(double) + T * (sizeof(mpp_descent_report) + sizeof(mpp_complete_report)) +
-         desc_up8((TC + T) * sizeof(int32_t)) + TC;
+  return (3 * TC + T * hw) * sizeof(double) + T * sizeof(mpp_descent_report) + (TC + T) * sizeof(int32_t) + TC;
 }
 // (the doubles first, then the records, the ints, the bytes: every array is aligned for its type)
 extern "C" void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, void *ws) {
@@ -31,10 +29,9 @@ extern "C" void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, v
   d->p = (double *)ws; d->rem_val = d->p + TC; d->gain_val = d->rem_val + TC;
   d->dE = hw ? d->gain_val + TC : nullptr;
   d->rep = (mpp_descent_report *)(d->gain_val + TC + T * hw);
-  d->crep = (mpp_complete_report *)(d->rep + T);
-  d->src = (int32_t *)(d->crep + T);
+  d->src = (int32_t *)(d->rep + T);
   d->n_rem = d->src + TC;
-  d->keep = (uint8_t *)d->src + desc_up8((TC + T) * sizeof(int32_t));
+  d->keep = (uint8_t *)(d->n_rem + T);
 }
 
 __device__ __forceinline__ int desc_count(const TileRef &t, int cap) {
@@ -105,10 +102,8 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descent_init(const TileRef *ti
   int32_t *src = d.src + (size_t)chain * d.cap;
   for (int i = tid; i < d.cap; i += DESC_THREADS) src[i] = i < n ? i : -1;
   if (tid != 0) return;
-  mpp_descent_report r;
-  r.status = -1; r.rounds = 0; r.n_added = 0; r.n_removed = 0; r.n_after = n; r.slot_max = -1;
-  r.gain_births = 0.0; r.gain_deaths = 0.0; r.max_p = -HUGE_VAL; r.min_dE = 0.0; r.x = -1; r.y = -1;
-  r.n_positive = 0; r.n_negative = 0; r.n_nan = 0;
+  mpp_descent_report r{};                                        // (the counts and the gains start at 0)
+  r.status = -1; r.n_after = n; r.slot_max = -1; r.max_p = -HUGE_VAL; r.x = -1; r.y = -1;
   d.rep[chain] = r;
   d.n_rem[chain] = 0;
 }
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descent_remove(const TileRef *
   // (two predicates scanned behind one pair of barriers: block_scan_place, mpp_device.hpp, twice would take two pairs)
   __shared__ int s_s[DESC_WAVES], s_r[DESC_WAVES];
   const int chain = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  if (d.crep[chain].status >= 0) return;                         // (closed: not touched again)
+  if (d.rep[chain].status >= 0) return;                          // (closed: not touched again)
   TileRef t = tiles[chain];
   const int n = desc_count(t, d.cap);
   const size_t o = (size_t)chain * d.cap;
@@ -159,44 +154,22 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descent_remove(const TileRef *
   }
 }
 
-// one lane per chain: the round's outcome.  The birth half's book is the completion's (k_complete_round has run on crep with
-// no round limit): status 0 there says that this round's map kept nothing, 2 that its births do not fit.
-__global__ __launch_bounds__(WAVE) void k_descent_round(const TileRef *tiles, Descent d, int what, int max_rounds) {
+// one lane per chain: the round's book.  n_kept: nullptr, or the candidates the birth half kept per chain (MinSel::n_kept)
+__global__ __launch_bounds__(WAVE) void k_descent_round(const TileRef *tiles, Descent d, int what, int max_rounds, const int32_t *n_kept) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= d.n_chains) return;
+  if (c >= d.n_chains || d.rep[c].status >= 0) return;
   mpp_descent_report r = d.rep[c];
-  if (r.status >= 0) return;
-  bool changed = false, full = false;
-  if (what & MPP_DESCEND_DEATHS) {
-    const int k = d.n_rem[c];
-    if (k > 0) {
-      double g = r.gain_deaths;
-      for (int i = 0; i < k; ++i) g += d.rem_val[(size_t)c * d.cap + i];
-      r.gain_deaths = g;
-      r.n_removed += k;
-      changed = true;
-    }
-  }
-  if (what & MPP_DESCEND_BIRTHS) {
-    const mpp_complete_report b = d.crep[c];
-    full = b.status == 2;
-    if (b.n_added > r.n_added) { r.n_added = b.n_added; r.gain_births = b.gain; changed = true; }
-  }
-  if (changed) r.rounds += 1;
-  if (full) r.status = 2;
-  else if (!changed) r.status = 0;
-  else if (r.rounds >= max_rounds) r.status = 1;
-  r.n_after = desc_count(tiles[c], d.cap);
+  const size_t o = (size_t)c * d.cap;
+  descent_book(r, what, max_rounds, d.cap, tiles[c].n, tiles[c].err, d.n_rem[c], d.rem_val + o, n_kept ? n_kept[c] : 0, d.gain_val + o);
   d.rep[c] = r;
-  d.crep[c].status = r.status;                                   // (open again for the next round, or closed for good)
 }
 
-// max_p, slot_max, n_positive of every chain's state from d.p; the map's summary is copied in when there is one
+// max_p, slot_max, n_positive of every chain's state from d.p (nullptr: skipped); the map's summary is copied in when there is one
 __global__ __launch_bounds__(DESC_THREADS) void k_descent_summary(const TileRef *tiles, Descent d, const mpp_birth_summary *sum) {
   __shared__ double s_v[DESC_THREADS];
   __shared__ int s_i[DESC_THREADS], s_c[DESC_THREADS];
   const int chain = blockIdx.x, tid = threadIdx.x;
-  const int n = desc_count(tiles[chain], d.cap);
+  const int n = d.p ? desc_count(tiles[chain], d.cap) : 0;
   const double *p = d.p + (size_t)chain * d.cap;
   double best = -HUGE_VAL;
   int slot = -1, pos = 0;
@@ -207,7 +180,7 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descent_summary(const TileRef 
   }
   s_v[tid] = best; s_i[tid] = slot; s_c[tid] = pos;
   __syncthreads();
-  for (int h = DESC_THREADS / 2; h > 0; h >>= 1) {
+  for (int h = DESC_THREADS / 2; d.p && h > 0; h >>= 1) {
     if (tid < h) {
       const double v2 = s_v[tid + h];
       const int i2 = s_i[tid + h];
@@ -218,7 +191,7 @@ __global__ __launch_bounds__(DESC_THREADS) void k_descent_summary(const TileRef 
   }
   if (tid != 0) return;
   mpp_descent_report *r = d.rep + chain;
-  r->max_p = s_v[0]; r->slot_max = s_i[0]; r->n_positive = s_c[0];
+  r->max_p = s_v[0]; r->slot_max = s_i[0]; r->n_positive = s_c[0];  // ((-inf, -1, 0) without d.p, as k_descent_init wrote them)
   if (sum) {
     const mpp_birth_summary b = sum[chain];
     r->min_dE = b.min_dE; r->x = b.x; r->y = b.y; r->n_negative = b.n_negative; r->n_nan = b.n_nan;
@@ -239,9 +212,9 @@ extern "C" void mpp_launch_descent_remove(hipStream_t st, const TileRef *tiles, 
   if (d.n_chains <= 0) return;
   hipLaunchKernelGGL(k_descent_remove, dim3(d.n_chains), dim3(DESC_THREADS), 0, st, tiles, d);
 }
-extern "C" void mpp_launch_descent_round(hipStream_t st, const TileRef *tiles, const Descent &d, int what, int max_rounds) {
+extern "C" void mpp_launch_descent_round(hipStream_t st, const TileRef *tiles, const Descent &d, int what, int max_rounds, const int32_t *n_kept) {
   if (d.n_chains <= 0) return;
-  hipLaunchKernelGGL(k_descent_round, dim3((d.n_chains + WAVE - 1) / WAVE), dim3(WAVE), 0, st, tiles, d, what, max_rounds);
+  hipLaunchKernelGGL(k_descent_round, dim3((d.n_chains + WAVE - 1) / WAVE), dim3(WAVE), 0, st, tiles, d, what, max_rounds, n_kept);
 }
 extern "C" void mpp_launch_descent_summary(hipStream_t st, const TileRef *tiles, const Descent &d, const mpp_birth_summary *sum) {
   if (d.n_chains <= 0) return;

@@ -58,7 +58,7 @@ struct MinSel {
   int H, W, ld, n_chains;
   double below, d2;                                // candidates: dE < below; within reach: (double)(dx*dx + dy*dy) <= d2
   int reach;                                       // no pixel further than this in a row or a column is within reach
-  const mpp_complete_report *rep;                  // nullptr, or [n_chains]: a chain whose status is >= 0 has no candidates
+  const mpp_descent_report *rep;                   // nullptr, or [n_chains]: a chain whose status is >= 0 has no candidates
   int nb_fill, nb_res;                             // blocks per chain of the compaction and of the resolve
   double *val; int32_t *idx;                       // the candidates in row-major order, [n_chains][H*W]
   int32_t *rows;                                   // [n_chains][H+1]: where a row's candidates start in the list
@@ -131,18 +131,15 @@ void mpp_launch_birth_map(hipStream_t st, const DevParams *P, const TileRef *til
                           BirthCache bc, double *dE, double *marks);
 void mpp_launch_birth_summary(hipStream_t st, int n_chains, int H, int W, const double *dE, BirthPart *part,
                               mpp_birth_summary *out);
-// the selection of local minima and the greedy completion (mpp_birth_complete.hip).  mpp_launch_minsel: from the maps to
+// the selection of local minima and the birth half of a round (mpp_birth_complete.hip).  mpp_launch_minsel: from the maps to
 // n_cand, n_kept, keep and kblk; _emit: the kept pixels and values of chain t to xy / values + t * out_cap, out_cap >= every
-// n_kept.  The completion: rep [n_chains] device; _round appends an open chain's kept candidates behind its configuration
-// when they fit cap (their values to gain_val [n_chains][cap]) and books the round; _summary copies the summaries in.
+// n_kept; _complete_append: an open chain's kept candidates go behind its configuration when they fit cap, their values to
+// gain_val [n_chains][cap].  The count and the book are mpp_launch_descent_round's.
 size_t mpp_minsel_bytes(int n_chains, int H, int W);
 void mpp_minsel_plan(MinSel *s, void *ws);
 void mpp_launch_minsel(hipStream_t st, const MinSel &s);
 void mpp_launch_minsel_emit(hipStream_t st, const MinSel &s, int out_cap, int32_t *xy, double *values);
-void mpp_launch_complete_init(hipStream_t st, int n_chains, mpp_complete_report *rep);
-void mpp_launch_complete_round(hipStream_t st, const MinSel &s, const DevParams *P, const TileRef *tiles, int cap,
-                               double *gain_val, int max_rounds, mpp_complete_report *rep);
-void mpp_launch_complete_summary(hipStream_t st, int n_chains, const mpp_birth_summary *sum, mpp_complete_report *rep);
+void mpp_launch_complete_append(hipStream_t st, const MinSel &s, const DevParams *P, const TileRef *tiles, int cap, double *gain_val);
 // the exchange of parallel tempering at absolute step s, exchange number e (mpp_tempering.hip), all device: tiles the ctx's
 // table (entry i: replica 0 of tile i, whose key the draw takes), sched [n_chains][3], rung [n_chains], energy [n_chains];
 // accepted [n_maps][R - 1] counts per (tile, pair); log nullptr or log_cap records, this exchange's from log_base on
@@ -175,17 +172,16 @@ struct PtSel {
   const int32_t *x, *y; int stride, n;
   const double *val; uint8_t *keep; size_t pitch;
   double above, d2;
-  const mpp_complete_report *closed;
+  const mpp_descent_report *closed;
   int32_t *count;
 };
 // The workspace of one mpp_descend / mpp_birth_complete, placed by mpp_descent_plan in mpp_descent_bytes bytes (hw: the pixels
-// of a map, 0 without births).
+// of a map, 0 without births).  _round (after the halves' launches) books the round; n_kept: MinSel::n_kept, nullptr without births.
 struct Descent {
   int n_chains, cap;
   double *p, *rem_val, *gain_val;                  // [n_chains][cap]: Papangelou values; the removed p and the appended dE of a round by place
   double *dE;                                      // [n_chains][hw] the maps
-  mpp_descent_report *rep;                         // [n_chains]
-  mpp_complete_report *crep;                       // [n_chains] the birth half's book (the completion's); status >= 0: the chain is closed
+  mpp_descent_report *rep;                         // [n_chains] the chain's one book; status >= 0: the chain is closed
   int32_t *src;                                    // [n_chains][cap]: where a slot's point started
   int32_t *n_rem;                                 // [n_chains] points the round's death half removed
   uint8_t *keep;                                   // [n_chains][cap] the selection's answer: 1 = remove
@@ -195,7 +191,7 @@ void mpp_descent_plan(Descent *d, int n_chains, int cap, size_t hw, void *ws);
 void mpp_launch_ptsel(hipStream_t st, const PtSel &s);
 void mpp_launch_descent_init(hipStream_t st, const TileRef *tiles, const Descent &d);
 void mpp_launch_descent_remove(hipStream_t st, const TileRef *tiles, const Descent &d);
-void mpp_launch_descent_round(hipStream_t st, const TileRef *tiles, const Descent &d, int what, int max_rounds);
+void mpp_launch_descent_round(hipStream_t st, const TileRef *tiles, const Descent &d, int what, int max_rounds, const int32_t *n_kept);
 void mpp_launch_descent_summary(hipStream_t st, const TileRef *tiles, const Descent &d, const mpp_birth_summary *sum_or_null);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);

@@ -298,20 +298,10 @@ class MppContext:
         self.shape = (0, 0)
         self.n_terms = 0
         self.names: List[str] = []
-        if point_capacity is not None:
-            self.set_option("point_capacity", point_capacity)
-        if cell_capacity is not None:
-            self.set_option("cell_capacity", cell_capacity)
-        if spec_waves is not None:
-            self.set_option("spec_waves", spec_waves)
-        if spec_lanes is not None:
-            self.set_option("spec_lanes", spec_lanes)
-        if replicas is not None:
-            self.set_option("replicas", replicas)
-        if deep is not None:
-            self.set_option("deep", deep)
-        if chain_state is not None:
-            self.set_option("chain_state", chain_state)
+        for name, value in (("point_capacity", point_capacity), ("cell_capacity", cell_capacity), ("spec_waves", spec_waves),
+                            ("spec_lanes", spec_lanes), ("replicas", replicas), ("deep", deep), ("chain_state", chain_state)):
+            if value is not None:
+                self.set_option(name, value)
         if os.environ.get("MPP_HANDOVER_TILES"):           # (experiments: the largest launch that starts hot)
             self.set_option("handover_tiles", int(os.environ["MPP_HANDOVER_TILES"]))
         if os.environ.get("MPP_HANDOVER_AT"):

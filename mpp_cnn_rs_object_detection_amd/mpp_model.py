@@ -225,10 +225,39 @@ def check_birth_map(config: Dict, world_size: int = 1) -> bool:
     on = (config.get("inference") or {}).get("birth_map", False)
     if not isinstance(on, (bool, np.bool_)):
         raise ValueError(f"inference.birth_map must be true or false, got {on!r}")
-    if on and world_size > 1:
-        raise ValueError(f"inference.birth_map needs an image held by one GPU; {world_size} ranks share this one "
-                         f"(set inference.birth_map to false)")
+    if on:
+        _needs_one_gpu("birth_map", world_size)
     return bool(on)
+
+
+def _needs_one_gpu(key: str, world_size: int):
+    if world_size > 1:
+        raise ValueError(f"inference.{key} needs an image held by one GPU; {world_size} ranks share this one "
+                         f"(set inference.{key} to false)")
+
+
+def _rounds_option(config: Dict, key: str, extra=()) -> Optional[Dict]:
+    """An option of ``inference`` that is off (``false``, the default), ``true``, or a mapping of known keys -- ``max_rounds``
+    (16), ``min_gain`` (0) and those of ``extra`` (each ``true``): None when it is off, else the checked round limit and gain
+    and the values of the ``extra`` keys as given."""
+    v = (config.get("inference") or {}).get(key, False)
+    known = ("max_rounds", "min_gain") + tuple(extra)
+    if isinstance(v, dict):
+        unknown = sorted(set(v) - set(known))
+        if unknown:
+            raise ValueError(f"inference.{key}: unknown key(s) {unknown}; it takes {', '.join(known[:-1])} and {known[-1]}")
+    elif not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"inference.{key} must be true, false or a dict of {' / '.join(known)}, got {v!r}")
+    elif not v:
+        return None
+    else:
+        v = {}
+    r, g = v.get("max_rounds", 16), v.get("min_gain", 0.0)
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= 1024:
+        raise ValueError(f"inference.{key}.max_rounds must be an integer in 1..1024, got {r!r}")
+    if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not np.isfinite(g) or g < 0:
+        raise ValueError(f"inference.{key}.min_gain must be a finite number >= 0, got {g!r}")
+    return {"max_rounds": int(r), "min_gain": float(g), **{k: v.get(k, True) for k in extra}}
 
 
 def check_birth_complete(config: Dict, world_size: int = 1) -> Optional[Dict]:
@@ -237,27 +266,10 @@ def check_birth_complete(config: Dict, world_size: int = 1) -> Optional[Dict]:
     left out: 16 rounds, gain 0).  Returns the two parameters as a dict, or None when it is off.  Like the birth map it
     runs on ONE context that holds the whole image, so ranks that share one image refuse it -- before any collective, every
     rank alike."""
-    v = (config.get("inference") or {}).get("birth_complete", False)
-    if isinstance(v, (bool, np.bool_)):
-        params = {} if v else None
-    elif isinstance(v, dict):
-        unknown = sorted(set(v) - {"max_rounds", "min_gain"})
-        if unknown:
-            raise ValueError(f"inference.birth_complete: unknown key(s) {unknown}; it takes max_rounds and min_gain")
-        params = dict(v)
-    else:
-        raise ValueError(f"inference.birth_complete must be true, false or a dict of max_rounds / min_gain, got {v!r}")
-    if params is None:
-        return None
-    r, g = params.get("max_rounds", 16), params.get("min_gain", 0.0)
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= 1024:
-        raise ValueError(f"inference.birth_complete.max_rounds must be an integer in 1..1024, got {r!r}")
-    if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not np.isfinite(g) or g < 0:
-        raise ValueError(f"inference.birth_complete.min_gain must be a finite number >= 0, got {g!r}")
-    if world_size > 1:
-        raise ValueError(f"inference.birth_complete needs an image held by one GPU; {world_size} ranks share this one "
-                         f"(set inference.birth_complete to false)")
-    return {"max_rounds": int(r), "min_gain": float(g)}
+    params = _rounds_option(config, "birth_complete")
+    if params is not None:
+        _needs_one_gpu("birth_complete", world_size)
+    return params
 
 
 def format_complete_summary(summary: Dict) -> str:
@@ -272,36 +284,19 @@ def check_descent(config: Dict, world_size: int = 1) -> Optional[Dict]:
     "deaths": ..}`` (any key may be left out: 16 rounds, gain 0, both parts).  Returns the four parameters as a dict, or None
     when it is off.  The descent contains the completion, so ``inference.birth_complete`` on at the same time is refused;
     like the completion it runs on ONE context that holds the whole image, so ranks that share one image refuse it."""
-    v = (config.get("inference") or {}).get("descent", False)
-    if isinstance(v, (bool, np.bool_)):
-        params = {} if v else None
-    elif isinstance(v, dict):
-        unknown = sorted(set(v) - {"max_rounds", "min_gain", "births", "deaths"})
-        if unknown:
-            raise ValueError(f"inference.descent: unknown key(s) {unknown}; it takes max_rounds, min_gain, births and deaths")
-        params = dict(v)
-    else:
-        raise ValueError(f"inference.descent must be true, false or a dict of max_rounds / min_gain / births / deaths, got {v!r}")
+    params = _rounds_option(config, "descent", ("births", "deaths"))
     if params is None:
         return None
-    r, g = params.get("max_rounds", 16), params.get("min_gain", 0.0)
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= 1024:
-        raise ValueError(f"inference.descent.max_rounds must be an integer in 1..1024, got {r!r}")
-    if isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating)) or not np.isfinite(g) or g < 0:
-        raise ValueError(f"inference.descent.min_gain must be a finite number >= 0, got {g!r}")
-    parts = {}
     for k in ("births", "deaths"):
-        parts[k] = params.get(k, True)
-        if not isinstance(parts[k], (bool, np.bool_)):
-            raise ValueError(f"inference.descent.{k} must be true or false, got {parts[k]!r}")
-    if not parts["births"] and not parts["deaths"]:
+        if not isinstance(params[k], (bool, np.bool_)):
+            raise ValueError(f"inference.descent.{k} must be true or false, got {params[k]!r}")
+        params[k] = bool(params[k])
+    if not params["births"] and not params["deaths"]:
         raise ValueError("inference.descent: births and deaths are both false (set inference.descent to false)")
     if check_birth_complete(config) is not None:
         raise ValueError("inference.descent contains the completion: set inference.birth_complete to false")
-    if world_size > 1:
-        raise ValueError(f"inference.descent needs an image held by one GPU; {world_size} ranks share this one "
-                         f"(set inference.descent to false)")
-    return {"max_rounds": int(r), "min_gain": float(g), "births": bool(parts["births"]), "deaths": bool(parts["deaths"])}
+    _needs_one_gpu("descent", world_size)
+    return params
 
 
 def format_descent_summary(summary: Dict) -> str:
@@ -501,13 +496,34 @@ class MPPModel:
         if region_data is None:
             region_data = self.region_maps(image_data, rank, world_size)
         merged, scores = self._infer_image(image_data, rank, world_size, region_data, seed)
+        merged, scores, done, descended, birth, dE = self._after_merge(region_data, merged, scores, complete, descent, birth_map)
         if complete is not None:
-            merged, scores, self.last_complete = self.complete(region_data, merged)
+            self.last_complete = done
         if descent is not None:
-            merged, scores, self.last_descent = self.descend(region_data, merged)
+            self.last_descent = descended
         if birth_map:
-            self.last_birth = self.birth_map(region_data, merged)
+            self.last_birth = (dE, birth)
         return merged, scores
+
+    def _after_merge(self, region_data: ImageWMaps, merged, scores, complete, descent, birth_map):
+        """What the options do to an image's merged detections, in this order: the completion, the descent (the map, the files
+        and the figures show the list they leave), the birth map of what is left (the image's own maps and its detections: one
+        context, one tile).  Returns (merged, scores, the three summaries, dE), None for what is off."""
+        done = descended = birth = dE = None
+        if complete is not None:
+            merged, scores, done = self.complete(region_data, merged)
+        if descent is not None:
+            merged, scores, descended = self.descend(region_data, merged)
+        if birth_map:
+            dE, birth = self.birth_map(region_data, merged)
+        return merged, scores, done, descended, birth, dE
+
+    def _image_set(self, region_data: ImageWMaps, merged, room: int) -> EPointsSet:
+        """one context with the image as its single tile and ``merged`` as its configuration, with room for ``room`` more points"""
+        pts = list(merged)
+        unit, pair = self.energy_setup.make_energies(region_data)
+        return EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
+                          device=self.device, point_capacity=max(1024, len(pts) + room))
 
     def descend(self, region_data: ImageWMaps, merged):
         """Local descent of one image's detections (``inference.descent``, ``EPointsSet.descend``): one context with the
@@ -515,11 +531,8 @@ class MPPModel:
         summary): the ``EPointsSet`` of the surviving detections in their order followed by the born ``Rectangle``s, the final
         Papangelou scores of EVERY point of it (``papangelou_all``), summary = the dict of ``EPointsSet.descend`` without
         ``n_after``; logs one line."""
-        pts = list(merged)
         p = check_descent(self.config) or {"max_rounds": 16, "min_gain": 0.0, "births": True, "deaths": True}
-        unit, pair = self.energy_setup.make_energies(region_data)
-        agg = EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
-                         device=self.device, point_capacity=max(1024, 2 * len(pts) + 64))
+        agg = self._image_set(region_data, merged, len(merged) + 64)
         r = agg.descend(energy_combinator=self.energy_model, births=p["births"], deaths=p["deaths"], max_rounds=p["max_rounds"],
                         min_gain=p["min_gain"])
         scores = agg.papangelou_all(energy_combinator=self.energy_model) if len(agg) else np.zeros(0)
@@ -535,11 +548,8 @@ class MPPModel:
         added ``Rectangle``s in slot order, the final Papangelou scores of EVERY point of it (``papangelou_all``, the
         scoring of ``merge_patches``' second pass: a detection next to a new one is rescored), summary = {"n_added",
         "rounds", "gain", "status", "min_dE", "argmin", "n_negative", "n_nan"}; logs one line."""
-        pts = list(merged)
         p = check_birth_complete(self.config) or {"max_rounds": 16, "min_gain": 0.0}
-        unit, pair = self.energy_setup.make_energies(region_data)
-        agg = EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
-                         device=self.device, point_capacity=max(1024, 2 * len(pts) + 64))
+        agg = self._image_set(region_data, merged, len(merged) + 64)
         r = agg.birth_complete(energy_combinator=self.energy_model, max_rounds=p["max_rounds"], min_gain=p["min_gain"])
         scores = agg.papangelou_all(energy_combinator=self.energy_model) if len(agg) else np.zeros(0)
         summary = {k: r[k] for k in ("n_added", "rounds", "gain", "status", "min_dE", "argmin", "n_negative", "n_nan")}
@@ -550,11 +560,7 @@ class MPPModel:
         """The birth-energy map of one image (``EPointsSet.birth_energy_map``): one context with the image as its single
         tile and ``merged`` as its configuration, as ``merge_patches`` builds its ``EPointsSet``.  Returns (dE, summary):
         dE [H,W] float64 on the device, summary = {"min_dE", "argmin": (x, y), "n_negative", "n_nan"}; logs one line."""
-        pts = list(merged)
-        unit, pair = self.energy_setup.make_energies(region_data)
-        agg = EPointsSet(pts, tuple(int(v) for v in region_data.shape[:2]), unit, pair, image_data=region_data,
-                         device=self.device, point_capacity=max(1024, len(pts) + 64))
-        dE, s = agg.birth_energy_map(energy_combinator=self.energy_model)
+        dE, s = self._image_set(region_data, merged, 64).birth_energy_map(energy_combinator=self.energy_model)
         summary = {"min_dE": float(s["min_dE"]), "argmin": (int(s["x"]), int(s["y"])), "n_negative": int(s["n_negative"]),
                    "n_nan": int(s["n_nan"])}
         logging.info(format_birth_summary(summary))
@@ -672,10 +678,7 @@ class MPPModel:
                     idx = np.nonzero(inside)[0]
                     local = [Rectangle(int(xy[k, 0] - ox), int(xy[k, 1] - oy), size=points[k].size, ratio=points[k].ratio,
                                        angle=points[k].angle) for k in idx]
-                    unit, pair = self.energy_setup.make_energies(region_data)
-                    pts = EPointsSet(local, (h, w), unit, pair, image_data=region_data, device=self.device,
-                                     point_capacity=max(1024, len(local) + 64))
-                    sc = pts.papangelou_all(energy_combinator=self.energy_model)
+                    sc = self._image_set(region_data, local, 64).papangelou_all(energy_combinator=self.energy_model)
                     sel = owned[idx]
                     out[idx[sel]] = sc[sel]
             except Exception:                       # noqa: BLE001
@@ -1027,13 +1030,9 @@ class MPPModel:
 
         try:
             for k, image_data, region_data, merged, scores, tempered, recombined in inferred():
-                birth = done = descended = None
-                if complete is not None:            # (before the map and the figures: they show the completed list)
-                    merged, scores, done = self.complete(region_data, merged)
-                if descent is not None:             # (the same place: the files show the descended list)
-                    merged, scores, descended = self.descend(region_data, merged)
-                if birth_map:                       # (the image's own maps and its merged detections: one context, one tile)
-                    dE, birth = self.birth_map(region_data, merged)
+                merged, scores, done, descended, birth, dE = self._after_merge(region_data, merged, scores, complete, descent,
+                                                                                 birth_map)
+                if birth_map:
                     self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
                     del dE
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth,

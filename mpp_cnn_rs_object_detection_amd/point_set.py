@@ -243,34 +243,51 @@ class EPointsSet:
             old.close()
         self._ctx, self._owns_ctx, self._dirty = new, True, True
 
-    def birth_complete(self, energy_combinator=None, max_rounds: int = 16, min_gain: float = 0.0) -> dict:
-        """Greedy completion (``mpp_birth_complete``): the set takes the births of its birth-energy map -- per round the
-        local minima below ``-min_gain``, no two within twice the interaction range -- until none is left or ``max_rounds``
-        rounds have added points.  The new ``Rectangle``s are appended to the set in slot order.  A round that does not fit
-        the context's point capacity makes the set move to a context of twice the capacity and go on (the gain is then the
-        sum of the parts' gains).  Returns {"status" (0 converged, 1 round limit), "rounds", "n_added", "n_after", "gain",
-        "min_dE", "argmin": (x, y), "n_negative", "n_nan"}, the last four of the completed set's map."""
-        from .hip_api import COMPLETE_CAPACITY
-        out = {"status": 0, "rounds": 0, "n_added": 0, "n_after": len(self._points), "gain": 0.0}
+    def _descent_parts(self, energy_combinator, max_rounds: int, part, counts, gains, out: dict):
+        """The loop ``birth_complete`` and ``descend`` share.  ``part(left)`` runs the context for at most ``left`` rounds and
+        returns (the tile's report, for every slot of the returned list the slot its point had before, -1 for a born one);
+        a part that changed the set makes the set that list: the surviving ``Rectangle`` objects stay, the born ones are new.
+        ``out`` takes the sums of the parts' ``counts`` and ``gains`` (the first part sets a gain, later parts add).  A part
+        that ends at the context's point capacity makes the set move to a context of twice the capacity and go on, unless no
+        round is left.  Returns the last part's report."""
+        from .hip_api import DESCENT_CAPACITY
         left, first = int(max_rounds), True
         while True:
             self._use(energy_combinator)
-            rep = self._ctx.birth_complete(left, min_gain)[0]
-            k = int(rep["n_added"])
-            if k:
+            rep, src = part(left)
+            if int(rep["rounds"]):
                 xy, marks = self._ctx.get_points(0)
-                assert len(xy) == len(self._points) + k
-                for (x, y), m in zip(xy[-k:], marks[-k:]):
-                    u = Rectangle(int(x), int(y), size=float(m[0]), ratio=float(m[1]), angle=float(m[2]))
-                    self._index[u] = len(self._points)
-                    self._points.append(u)
-            out["rounds"] += int(rep["rounds"])
-            out["n_added"] += k
-            out["gain"] = float(rep["gain"]) if first else out["gain"] + float(rep["gain"])
+                assert len(xy) == len(src) == int(rep["n_after"])
+                self._points = [self._points[s] if s >= 0 else Rectangle(int(x), int(y), size=float(m[0]), ratio=float(m[1]), angle=float(m[2]))
+                                for s, (x, y), m in zip(src, xy, marks)]
+                self._index = {u: k for k, u in enumerate(self._points)}
+            for k in counts:
+                out[k] += int(rep[k])
+            for k in gains:
+                out[k] = float(rep[k]) if first else out[k] + float(rep[k])
             left, first = left - int(rep["rounds"]), False
-            if int(rep["status"]) != COMPLETE_CAPACITY:
-                break
+            if int(rep["status"]) != DESCENT_CAPACITY:
+                return rep
+            if left < 1:                                # (the round that did not fit was the last one allowed)
+                rep = rep.copy()
+                rep["status"] = 1
+                return rep
             self._grow_context()
+
+    def birth_complete(self, energy_combinator=None, max_rounds: int = 16, min_gain: float = 0.0) -> dict:
+        """Greedy completion (``mpp_birth_complete``), the births-only form of ``descend`` without its Papangelou values: the
+        set takes the births of its birth-energy map -- per round the local minima below ``-min_gain``, no two within twice
+        the interaction range -- until none is left or ``max_rounds`` rounds have added points.  The new ``Rectangle``s are
+        appended to the set in slot order.  A round that does not fit the context's point capacity makes the set move to a
+        context of twice the capacity and go on (the gain is then the sum of the parts' gains).  Returns {"status" (0
+        converged, 1 round limit), "rounds", "n_added", "n_after", "gain", "min_dE", "argmin": (x, y), "n_negative",
+        "n_nan"}, the last four of the completed set's map."""
+        out = {"status": 0, "rounds": 0, "n_added": 0, "n_after": len(self._points), "gain": 0.0}
+
+        def part(left):
+            rep = self._ctx.birth_complete(left, min_gain)[0]
+            return rep, list(range(len(self._points))) + [-1] * int(rep["n_added"])
+        rep = self._descent_parts(energy_combinator, max_rounds, part, ("rounds", "n_added"), ("gain",), out)
         out.update(status=int(rep["status"]), n_after=int(rep["n_after"]), min_dE=float(rep["min_dE"]),
                    argmin=(int(rep["x"]), int(rep["y"])), n_negative=int(rep["n_negative"]), n_nan=int(rep["n_nan"]))
         return out
@@ -285,37 +302,18 @@ class EPointsSet:
         the sums of the parts' gains).  Returns {"status" (0 joint fixed point, 1 round limit), "rounds", "n_added",
         "n_removed", "n_after", "gain_births", "gain_deaths", "gain" (births minus deaths: the energy change), "max_p",
         "slot_max", "n_positive", "min_dE", "argmin": (x, y), "n_negative", "n_nan"}, the last seven of the returned set."""
-        from .hip_api import DESCEND_BIRTHS, DESCEND_DEATHS, DESCENT_CAPACITY
+        from .hip_api import DESCEND_BIRTHS, DESCEND_DEATHS
         what = (DESCEND_DEATHS if deaths else 0) | (DESCEND_BIRTHS if births else 0)
         if not what:
             raise ValueError("descend: births and deaths are both off")
         out = {"status": 0, "rounds": 0, "n_added": 0, "n_removed": 0, "n_after": len(self._points), "gain_births": 0.0,
                "gain_deaths": 0.0}
-        left, first = int(max_rounds), True
-        while True:
-            self._use(energy_combinator)
+
+        def part(left):
             rep, src = self._ctx.descend(what, left, min_gain, src=True)
-            rep, src = rep[0], src[0]
-            if int(rep["n_added"]) or int(rep["n_removed"]):
-                n = int(rep["n_after"])
-                xy, marks = self._ctx.get_points(0)
-                assert len(xy) == n == len(self._points) + int(rep["n_added"]) - int(rep["n_removed"])
-                pts = [self._points[s] if s >= 0 else Rectangle(int(x), int(y), size=float(m[0]), ratio=float(m[1]), angle=float(m[2]))
-                       for s, (x, y), m in zip(src[:n].tolist(), xy, marks)]
-                self._points = pts
-                self._index = {u: k for k, u in enumerate(pts)}
-            for k in ("rounds", "n_added", "n_removed"):
-                out[k] += int(rep[k])
-            for k in ("gain_births", "gain_deaths"):
-                out[k] = float(rep[k]) if first else out[k] + float(rep[k])
-            left, first = left - int(rep["rounds"]), False
-            if int(rep["status"]) != DESCENT_CAPACITY:
-                break
-            if left < 1:                                # (the round that did not fit was the last one allowed)
-                rep = rep.copy()
-                rep["status"] = 1
-                break
-            self._grow_context()
+            return rep[0], src[0][:int(rep[0]["n_after"])].tolist()
+        rep = self._descent_parts(energy_combinator, max_rounds, part, ("rounds", "n_added", "n_removed"),
+                                  ("gain_births", "gain_deaths"), out)
         out.update(status=int(rep["status"]), n_after=int(rep["n_after"]), gain=out["gain_births"] - out["gain_deaths"],
                    max_p=float(rep["max_p"]), slot_max=int(rep["slot_max"]), n_positive=int(rep["n_positive"]),
                    min_dE=float(rep["min_dE"]), argmin=(int(rep["x"]), int(rep["y"])), n_negative=int(rep["n_negative"]),

@@ -490,6 +490,44 @@ def test_chains_do_not_depend_on_each_other():
     ctx.close()
 
 
+def test_chains_of_one_context_close_in_different_rounds():
+    """the closed test of every kernel of a round reads the one book: an empty chain, the 12 points, and the state a completion
+    of the 12 points returned (which the completion closes in its first round) equal three one-chain contexts, completed and
+    descended.  The one-chain completions take 5, 2 and 0 rounds: pairwise different.  The one-chain descents take 5, 9 and 9:
+    the last two states hold the same nine points to remove, one per round (the tile is smaller than the selection's
+    distance), and that many rounds cover the two births the 12 points lack; there the empty chain closes before the others."""
+    _, _, desc = model_desc("mpp_hrcM")
+    det, marks = tile_maps()
+    first = make_ctx(desc, det, marks, point_capacity=64)
+    first.set_points(0, POINTS, POINT_MARKS)
+    assert int(first.birth_complete(max_rounds=16)[0]["status"]) == 0
+    configs = [NO_POINTS, (POINTS, POINT_MARKS), first.get_points(0)]
+    first.close()
+    calls = {"birth_complete": lambda c: (c.birth_complete(max_rounds=16), None),
+             "descend": lambda c: c.descend(what=3, max_rounds=16, src=True)}
+    for what, call in calls.items():
+        ctx = make_ctx(desc, det, marks, replicas=3, point_capacity=64)
+        for c in range(3):
+            ctx.set_points(c, *configs[c])
+        rep, src = call(ctx)
+        final = ctx.get_points_all()
+        ctx.close()
+        rounds = []
+        for c in range(3):
+            one = make_ctx(desc, det, marks, point_capacity=64)
+            one.set_points(0, *configs[c])
+            r1, s1 = call(one)
+            got = one.get_points(0)
+            one.close()
+            rounds.append(int(r1[0]["rounds"]))
+            assert r1[0].tobytes() == rep[c].tobytes(), (what, c, r1[0], rep[c])     # every field, bit for bit
+            assert src is None or np.array_equal(s1[0], src[c]), (what, c)
+            np.testing.assert_array_equal(final[c][0], got[0], err_msg=f"{what}, chain {c}")
+            np.testing.assert_array_equal(final[c][1], got[1], err_msg=f"{what}, chain {c}")
+        print(f"{what}: rounds {rounds}, status {[int(r['status']) for r in rep]}")
+        assert len(set(rounds)) >= (3 if what == "birth_complete" else 2), (what, rounds)
+
+
 @pytest.mark.parametrize("name", MODELS)
 def test_with_and_without_the_candidate_grid(name):
     out = []
