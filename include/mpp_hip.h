@@ -391,6 +391,51 @@ int mpp_papangelou_all(mpp_ctx *ctx, double *dE);
 int mpp_select_points(mpp_ctx *ctx, int n, const int32_t *xy_dev, const double *values_dev, double above, double distance,
                       uint8_t *keep_dev, int64_t *n_candidates, int64_t *n_kept);
 int mpp_descend(mpp_ctx *ctx, int what, int max_rounds, double min_gain, mpp_descent_report *report, int32_t *src_or_null);
+/* Relocation (csrc/mpp_relocate.hip): move a point to a better map candidate nearby, in one step.
+ *
+ * mpp_move_gains: for every point v (slot i) of every chain and every pixel c of the (2 radius + 1)^2 window around v, clipped
+ * to the tile, with u_c the candidate of mpp_birth_energy_map at c (position c, marks edges[k][argmax class]):
+ *   value   g(v, c) = E(X) - E(X - v + u_c), X' = X - v + u_c;
+ *   order   S = e(u_c | X') - e(v | X), one difference; then e(w | X') - e(w | X) of the slots w != i within max_inter of v or
+ *           of c is added to S one after another in ASCENDING SLOT ORDER; g = -S.  Every e(. | .) is the point energy of
+ *           mpp_total_energy.  A pixel's g does not depend on the other chains, on n_chains, on "scratch_grid_min_points" or on
+ *           the radius (beyond which pixels are in the window), bit for bit;
+ *   output  gain[i] = the largest non-NaN g over the window, to[i] = (x, y) of its pixel, ties to the smaller row, then the
+ *           smaller column; gain = NaN and to = (-1, -1) when every g is NaN.  c = v's own pixel is a candidate: it replaces
+ *           the marks only.  Behind a chain's count: 0.0 and (-1, -1).
+ * The pair reductions are max / min from the seed 0.0, exact selections: a pre-pass caches per point and pair term the best
+ * value, the second-best and the slot of the best, so red_w(X - v) is the second-best when v is the slot of w's best and the
+ * best otherwise (equal values: second = best; the seed is a contributor no removal takes away), and red_w(X') =
+ * reduce(red_w(X - v), pair(w, u_c)).  One workgroup per point, one lane per window pixel; the points within reach are staged
+ * in LDS in slot order, MPP_MOVE_CHUNK at a time, and walked twice: first for u_c's own reductions, then for the sum.
+ * gain HOST [n_chains][point_capacity] float64, to HOST [n_chains][point_capacity][2] int32.  -1 with a message: radius
+ * outside 1..MPP_MOVE_RADIUS_MAX; no maps or no model; a classic image energy (the candidate's unit terms come from the
+ * maps); a pair reduction that is neither max nor min; more than 65535 chains.  Read-only option "move_gains_grid": the last
+ * call's pre-pass built candidate grids.
+ *
+ * mpp_relocate: every chain of the ctx on its own, from the state mpp_get_points_all reads.  A round of an open chain:
+ *   the gains above; the selection of mpp_select_points on them with above = min_gain and
+ *   distance = 2 * (max_inter + radius * sqrt(2.0)) in float64; every kept point is REWRITTEN IN PLACE: position to[i], marks
+ *   the candidate's there; slot, count and slot order stay, the error code is cleared when something moved -- the state
+ *   mpp_set_points of the edited list leaves.
+ * A move changes only points within max_inter of v or of c, and |v - c| <= radius * sqrt(2): two kept points, further apart
+ * than the distance, neither interact before or after nor share an affected neighbour, so in real arithmetic a round lowers
+ * the energy by exactly the sum of its gains.
+ * status 0: a round moved nothing; 1: max_rounds (1..1024) rounds have moved something (the count never changes: there is no
+ * status 2).  A closed chain is not touched again.  report [n_chains] HOST: rounds = the rounds that moved something; n_moved
+ * the moves; n_after the chain's count; gain = the kept gains added one after another to a float64 from 0.0, round by round and
+ * in slot order within a round.  Of the RETURNED state: max_gain the largest non-NaN gain and slot_max the first slot that has
+ * it ((-inf, -1) for an empty chain or when every gain is NaN), n_positive the count of gains > 0; after status 1 one more gain
+ * pass is computed for them.  moved_or_null HOST [n_chains][point_capacity] int32: how often a slot was rewritten, 0 behind
+ * the count.  Per round a fixed number of launches and one copy of n_chains reports; no point list crosses to the host.
+ * -1 with a message: the refusals of the gains; max_rounds outside 1..1024; min_gain negative or not finite; report NULL.
+ * With min_gain = 0 a point within rounding of 0 could move back and forth between two pixels; max_rounds ends that with
+ * status 1, a min_gain above the rounding bound excludes it. */
+#define MPP_MOVE_CHUNK 256         /* points staged per pass of a workgroup */
+#define MPP_MOVE_RADIUS_MAX 7      /* 15 x 15 = 225 window pixels in 256 lanes */
+typedef struct { int32_t status, rounds, n_moved, n_after, slot_max, n_positive; double gain, max_gain; } mpp_relocate_report;
+int mpp_move_gains(mpp_ctx *ctx, int radius, double *gain, int32_t *to);
+int mpp_relocate(mpp_ctx *ctx, int radius, int max_rounds, double min_gain, mpp_relocate_report *report, int32_t *moved_or_null);
 /* naive_detection (sample_rjmcmc.py:23-35): threshold + greedy distance-NMS, sets every tile's points.  Candidates are
  * det >= (float)threshold (float32, as NumPy compares); rank and NMS rule as mpp_detect_centers below.  A tile that keeps more
  * than point_capacity points: -12 ("naive init, tile t"), its first point_capacity picks stay stored; every call replaces

@@ -46,6 +46,13 @@ def _ratio(text):
     return v
 
 
+def _radius(text):
+    v = int(text)
+    if not 1 <= v <= 7:
+        raise argparse.ArgumentTypeError(f"{text}: a radius of 1..7 pixels")
+    return v
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-m", "--model", help="model to use")
@@ -93,6 +100,12 @@ def build_parser():
                              "deaths (objects whose removal lowers the energy) and of the births of --birth-complete, until a whole "
                              "round changes nothing; the results are those of the descended list, the pickle gains the key descent "
                              "and one line is logged; same as inference.descent in the config (whose parameters it keeps)")
+    parser.add_argument("--relocate", type=_radius, nargs="?", const=True, default=None, metavar="RADIUS",
+                        help="(-m mpp, infer / infereval / detect) relocation of every image's detections: every object moves to "
+                             "the candidate of the score maps within RADIUS pixels (1..7, default: the config's, else 2) that "
+                             "lowers the energy most, round after round, until none does; with --descent the two repeat while "
+                             "something moves; the pickle gains the key relocate and one line is logged; same as "
+                             "inference.relocate in the config (whose other parameters it keeps)")
     parser.add_argument("--images", nargs="+", default=None, metavar="PATH",
                         help="(-p detect) image files, or directories whose image files are taken in sorted order")
     parser.add_argument("--out", default=None, metavar="DIR", help="(-p detect) where the results go")
@@ -119,6 +132,18 @@ def apply_descent(args, config):
         inference = config.setdefault("inference", {})
         if not isinstance(inference.get("descent"), dict):
             inference["descent"] = True
+    return config
+
+
+def apply_relocate(args, config):
+    """--relocate turns inference.relocate on; --relocate RADIUS sets its radius; other parameters the config gives stay"""
+    if args.relocate is not None and args.procedure in ("infer", "infereval", "detect"):
+        inference = config.setdefault("inference", {})
+        if args.relocate is not True:
+            kept = inference["relocate"] if isinstance(inference.get("relocate"), dict) else {}
+            inference["relocate"] = dict(kept, radius=args.relocate)
+        elif not isinstance(inference.get("relocate"), dict):
+            inference["relocate"] = True
     return config
 
 
@@ -176,6 +201,7 @@ def main():
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
         apply_descent(args, config)
+        apply_relocate(args, config)
         apply_tempering(args, config)
         apply_recombine(args, config)
         model = MPPModel(config, phase="val", load=True, device=local_rank,
@@ -195,6 +221,7 @@ def main():
             config.setdefault("inference", {})["birth_map"] = True
         apply_birth_complete(args, config)
         apply_descent(args, config)
+        apply_relocate(args, config)
         apply_tempering(args, config)
         apply_recombine(args, config)
         nets = None

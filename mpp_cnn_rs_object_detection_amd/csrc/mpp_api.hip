@@ -222,6 +222,7 @@ extern "C" int64_t mpp_get_option(mpp_ctx *c, const char *name) {
   if (!strcmp(name, "scratch_grid_min_points")) return c->grid_min_points;
   if (!strcmp(name, "recombine_lds_points")) return c->recombine_lds;
   if (!strcmp(name, "birth_map_grid")) return c->birth_grid;                    // the last birth map's pre-pass built grids
+  if (!strcmp(name, "move_gains_grid")) return c->move_grid;                    // the last move-gain pre-pass built grids
   if (!strcmp(name, "force_accept")) return c->hp.force_accept;
   if (!strcmp(name, "grid_nx")) return c->hp.nx;       // spatial hash dimensions (point_set.py:58-61)
   if (!strcmp(name, "grid_ny")) return c->hp.ny;

@@ -399,6 +399,113 @@ extern "C" int mpp_descend(mpp_ctx *c, int what, int max_rounds, double min_gain
   return descent_rounds(c, "descend", "descent", what, true, max_rounds, min_gain, report, src);
 }
 
+// ---- relocation (mpp_relocate.hip) --------------------------------------------------------------------------
+// What mpp_move_gains and mpp_relocate refuse alike; `who` names the caller in the message.
+static int move_refusals(mpp_ctx *c, const char *who, int radius) {
+  if (radius < 1 || radius > MPP_MOVE_RADIUS_MAX)
+    return fail(c, -1, "%s: radius %d, must be 1..%d", who, radius, MPP_MOVE_RADIUS_MAX);
+  int rc = birth_refusals(c, who);
+  if (rc) return rc;
+  for (int p = 0; p < c->hp.model.n_pair; ++p)                   // (a reduction without its best contributor needs a selection)
+    if (c->hp.model.pair[p].reduce != MPP_REDUCE_MAX && c->hp.model.pair[p].reduce != MPP_REDUCE_MIN)
+      return fail(c, -1, "%s: pair term %d has a reduction that is neither max nor min", who, p);
+  if (c->n_tiles > 65535) return fail(c, -1, "%s: %d chains, at most 65535", who, c->n_tiles);
+  return 0;
+}
+// The two workspaces of a call, after push_state: the Descent's (the gains in d->p, the selection's answer, the round's list,
+// the closed flags) and the Move's.
+static int move_setup(mpp_ctx *c, const char *who, Descent *d, Move *m) {
+  const int T = c->n_tiles;
+  if (c->descent_ws.reserve(c->stream, mpp_descent_bytes(T, c->cap, 0)) != hipSuccess ||
+      c->relocate_ws.reserve(c->stream, mpp_move_bytes(T, c->cap)) != hipSuccess)
+    return fail(c, -2, "%s: no device memory for the move gains of %d chains", who, T);
+  mpp_descent_plan(d, T, c->cap, 0, c->descent_ws.p);
+  mpp_move_plan(m, T, c->cap, c->relocate_ws.p);
+  return 0;
+}
+// The launches of one gain pass over every chain (or every open one): grids as mpp_total_energy_all builds them, the pre-pass, the gains
+static int move_gain_launches(mpp_ctx *c, const char *who, int radius, const Move &m, const Descent &d, bool skip_closed) {
+  ChainGrids g;
+  if (chain_grids_build(c, c->cap, chain_grids_on(c), &g))
+    return fail(c, -2, "%s: no device memory for the candidate grids of %d chains", who, c->n_tiles);
+  c->move_grid = g.ncell > 0 ? 1 : 0;
+  mpp_launch_move_gains(c->stream, c->dp, c->d_tiles, m, d, radius, g.start, g.items, g.ncell + 1, c->grid_min_points, skip_closed ? 1 : 0);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+extern "C" int mpp_move_gains(mpp_ctx *c, int radius, double *gain, int32_t *to) {
+  if (!c) return -1;
+  int rc = move_refusals(c, "move_gains", radius);
+  if (rc) return rc;
+  if (!gain || !to) return fail(c, -1, "move_gains: gain or to is NULL");
+  if ((rc = push_state(c))) return rc;
+  Descent d;
+  Move m;
+  if ((rc = move_setup(c, "move_gains", &d, &m))) return rc;
+  const size_t TC = (size_t)c->n_tiles * c->cap;
+  HIPCHK(c, hipMemsetAsync(d.p, 0, TC * sizeof(double), c->stream));         // (the kernel writes the slots below a chain's count only)
+  HIPCHK(c, hipMemsetAsync(m.to, 0xff, 2 * TC * sizeof(int32_t), c->stream));
+  if ((rc = move_gain_launches(c, "move_gains", radius, m, d, false))) return rc;
+  hipError_t e = hipMemcpyAsync(gain, d.p, TC * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(to, m.to, 2 * TC * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
+// The rounds of mpp_relocate.  Per round: the launches of the gain pass, of the selection among points, of the rewrite and of
+// the round's book; one copy of the chains' books to report [n_chains].  Then the tail: the gains of the returned state,
+// recomputed when a chain moved in the round that closed it, and their summary.
+extern "C" int mpp_relocate(mpp_ctx *c, int radius, int max_rounds, double min_gain, mpp_relocate_report *report, int32_t *moved) {
+  if (!c) return -1;
+  int rc = move_refusals(c, "relocate", radius);
+  if (rc) return rc;
+  if (!report) return fail(c, -1, "relocate: report is NULL");
+  if ((rc = rounds_refusals(c, "relocate", max_rounds, min_gain))) return rc;
+  if ((rc = push_state(c))) return rc;
+  Descent d;
+  Move m;
+  if ((rc = move_setup(c, "relocate", &d, &m))) return rc;
+  const int T = c->n_tiles;
+  const size_t TC = (size_t)T * c->cap;
+  const double distance = 2.0 * (c->hp.max_inter + (double)radius * sqrt(2.0));
+  PtSel ps{};
+  ps.tiles = c->d_tiles; ps.n_chains = T; ps.cap = c->cap; ps.val = d.p; ps.keep = d.keep; ps.pitch = (size_t)c->cap;
+  ps.above = min_gain; ps.d2 = distance * distance; ps.closed = d.rep;
+  HIPCHK(c, hipMemsetAsync(m.moved, 0, TC * sizeof(int32_t), c->stream));
+  HIPCHK(c, hipMemsetAsync(m.to, 0xff, 2 * TC * sizeof(int32_t), c->stream));
+  mpp_launch_descent_init(c->stream, c->d_tiles, d);
+  mpp_launch_move_init(c->stream, c->d_tiles, m);
+  bool stale = false, open = T > 0;
+  // (a chain is open for at most max_rounds rounds that move something and the one that closes it)
+  for (int round = 0; round <= max_rounds && open; ++round) {
+    if ((rc = move_gain_launches(c, "relocate", radius, m, d, true))) return rc;
+    mpp_launch_ptsel(c->stream, ps);
+    mpp_launch_move_apply(c->stream, c->dp, c->d_tiles, m, d);
+    mpp_launch_move_round(c->stream, c->d_tiles, m, d, max_rounds);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(report, m.rep, (size_t)T * sizeof(mpp_relocate_report), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    HIPCHK(c, e); HIPCHK(c, e2);
+    open = false;
+    for (int t = 0; t < T; ++t) {
+      open = open || report[t].status < 0;
+      stale = stale || report[t].status == 1;                    // (moved in the round that closed it: its gains are not its state's)
+    }
+  }
+  if (open) return fail(c, -9, "relocate: a chain is still open after %d rounds", max_rounds + 1);
+  if (stale && (rc = move_gain_launches(c, "relocate", radius, m, d, false))) return rc;
+  mpp_launch_descent_summary(c->stream, c->d_tiles, d, nullptr);
+  mpp_launch_move_finish(c->stream, m, d);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(report, m.rep, (size_t)T * sizeof(mpp_relocate_report), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && moved) e = hipMemcpyAsync(moved, m.moved, TC * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  HIPCHK(c, e); HIPCHK(c, e2);
+  return 0;
+}
+
 // shared body of mpp_delta_batch (dE != NULL) and mpp_delta_vectors (before/after/mask != NULL)
 static int delta_cases(mpp_ctx *c, int tile, int n_cases, const int32_t *rem_off, const int32_t *rem,
                        const int32_t *add_off, const int32_t *add_xy, const double *add_marks, double *dE, int stride,

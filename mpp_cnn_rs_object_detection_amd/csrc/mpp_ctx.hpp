@@ -148,6 +148,8 @@ struct mpp_ctx : TileMem {
   DevWs recombine_ws;                // mpp_recombine: the tiles' labels and cluster choices, the staged composites, the reports
   DevWs descent_ws;                  // mpp_descend / mpp_birth_complete / mpp_papangelou_all: the Papangelou values, the maps, the round's lists, the reports
   DevWs ptsel_ws;                    // mpp_select_points: its two counters
+  DevWs relocate_ws;                 // mpp_move_gains / mpp_relocate: the per-point cache, the target pixels, the books
+  int move_grid = 0;                 // ... its last pre-pass built candidate grids
   int recombine_lds = MPP_RECOMBINE_LDS_POINTS;   // ... a tile of more points over its replicas labels in the workspace, not in LDS
   DetectWs detect;                   // workspace of mpp_detect_centers (mpp_detect.hip)
   TrainWs train;                     // workspace of the loss kernels (mpp_train.hip)

@@ -409,6 +409,19 @@ __device__ __forceinline__ int block_scan_place(bool keep, int *wave_tot, int *t
   *total = all;
   return before + __popcll(m & ((1ull << lane) - 1ull));
 }
+// The same scan for a workgroup whose number of waves is known only at run time (blockDim.x / WAVE = n_waves entries of wave_tot)
+template <bool AGAIN = true>
+__device__ __forceinline__ int block_scan_place_n(bool keep, int n_waves, int *wave_tot, int *total) {
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wave_tot[wv] = __popcll(m);
+  __syncthreads();
+  int before = 0, all = 0;
+  for (int q = 0; q < n_waves; ++q) { const int v = wave_tot[q]; before += q < wv ? v : 0; all += v; }
+  if (AGAIN) __syncthreads();
+  *total = all;
+  return before + __popcll(m & ((1ull << lane) - 1ull));
+}
 
 // ---- Philox4x32-10--------------------------------------------------------------------------
 __host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,

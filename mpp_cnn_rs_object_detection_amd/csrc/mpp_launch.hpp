@@ -193,6 +193,28 @@ void mpp_launch_descent_init(hipStream_t st, const TileRef *tiles, const Descent
 void mpp_launch_descent_remove(hipStream_t st, const TileRef *tiles, const Descent &d);
 void mpp_launch_descent_round(hipStream_t st, const TileRef *tiles, const Descent &d, int what, int max_rounds, const int32_t *n_kept);
 void mpp_launch_descent_summary(hipStream_t st, const TileRef *tiles, const Descent &d, const mpp_birth_summary *sum_or_null);
+// the relocation (mpp_relocate.hip), all device.  Move: the workspace of one mpp_move_gains / mpp_relocate, placed by
+// mpp_move_plan in mpp_move_bytes bytes; the gains, the selection's answer, the round's list and the chains' closed flags are
+// the Descent's (p, keep, rem_val / n_rem, rep[].status).  _move_gains: the pre-pass from the chains' grids (nullptr: every
+// chain scans) and the gain kernel, into d.p and m.to; a chain whose d.rep status is >= 0 is skipped when `skip_closed`.
+// _move_init after mpp_launch_descent_init; _move_apply after mpp_launch_ptsel rewrites the kept points and lists their gains;
+// _move_round books the round; _move_finish after mpp_launch_descent_summary copies the summary into the books.
+struct Move {
+  int n_chains, cap;
+  double *lin, *e, *best[MPP_MAX_PAIR], *second[MPP_MAX_PAIR];   // [n_chains][cap] the pre-pass's record of a point
+  int32_t *gate, *slot[MPP_MAX_PAIR];              // ... its gate and, per pair term, the slot of the best value (-1: the seed)
+  mpp_relocate_report *rep;                        // [n_chains] the chain's book
+  int32_t *to;                                     // [n_chains][cap][2] the pixel of a point's best gain
+  int32_t *moved;                                  // [n_chains][cap] how often a slot was rewritten
+};
+size_t mpp_move_bytes(int n_chains, int cap);
+void mpp_move_plan(Move *m, int n_chains, int cap, void *ws);
+void mpp_launch_move_gains(hipStream_t st, const DevParams *P, const TileRef *tiles, const Move &m, const Descent &d, int radius,
+                           const int32_t *grid_start, const int32_t *grid_items, int sstride, int grid_min, int skip_closed);
+void mpp_launch_move_init(hipStream_t st, const TileRef *tiles, const Move &m);
+void mpp_launch_move_apply(hipStream_t st, const DevParams *P, const TileRef *tiles, const Move &m, const Descent &d);
+void mpp_launch_move_round(hipStream_t st, const TileRef *tiles, const Move &m, const Descent &d, int max_rounds);
+void mpp_launch_move_finish(hipStream_t st, const Move &m, const Descent &d);
 void mpp_launch_cdf(hipStream_t st, int n_tiles, const float *det, int H, int W, double *rowpart, double *rowbase,
                     double *scratch_rowtot);
 void mpp_launch_boxsum(hipStream_t st, int n_tiles, const double *rowpart, int H, int W, int md, double *boxsum);

@@ -23,3 +23,16 @@ __host__ __device__ __forceinline__ void descent_book(mpp_descent_report &r, int
   else if (r.rounds >= max_rounds) r.status = 1;
   r.n_after = n < 0 ? 0 : (n > cap ? cap : n);
 }
+// One round of an open chain of the relocation (k_move_round, mpp_relocate.hip; the rule is spelled out at mpp_relocate in
+// mpp_hip.h): the n_kept gains of the points the round rewrote in place are added one after another, in slot order.  The count
+// never changes.  Moves leave what mpp_set_points of the edited list leaves: *err = 0.  Status: 0 nothing moved, 1 the round
+// limit, else still open.
+__host__ __device__ __forceinline__ void relocate_book(mpp_relocate_report &r, int max_rounds, int32_t *err, int n_kept,
+                                                       const double *gain_val) {
+  for (int i = 0; i < n_kept; ++i) r.gain += gain_val[i];
+  r.n_moved += n_kept;
+  if (n_kept > 0) *err = 0;
+  r.rounds += n_kept > 0 ? 1 : 0;
+  if (n_kept <= 0) r.status = 0;
+  else if (r.rounds >= max_rounds) r.status = 1;
+}

@@ -77,6 +77,7 @@ class DetectResult:
     birth: Any = None                 # ``inference.birth_map``: (dE [h,w] float64 device tensor, summary dict) of ``MPPModel.birth_map``
     complete: Any = None              # ``inference.birth_complete``: the summary dict of ``MPPModel.complete`` (``detections`` are completed)
     descent: Any = None               # ``inference.descent``: the summary dict of ``MPPModel.descend`` (``detections`` are descended)
+    relocate: Any = None              # ``inference.relocate``: the summary dict of ``MPPModel.relocate`` (``detections`` are relocated)
     tempering: Any = None             # ``inference.tempering``: ``last_run["tempering"]`` (exchange rates, the winners' rungs)
     recombine: Any = None             # ``inference.recombine``: ``last_run["recombine"]`` (per tile: status, clusters, energies)
 
@@ -119,11 +120,11 @@ def detect_image(model, rgb_uint8: np.ndarray, gsd: Optional[float] = None, mode
     data = ImageWMaps(name=name, shape=tuple(image.shape[:2]), image=image, detection_map=None, param_dist_maps=None,
                       mappings=default_mappings(),
                       param_names=Rectangle.PARAMETERS, labels=None, gt_config=[])
-    model.last_birth = model.last_complete = model.last_descent = None
+    model.last_birth = model.last_complete = model.last_descent = model.last_relocate = None
     detections, scores = model.infer_image(data, seed=seed)
     return DetectResult(detections=detections, scores=np.asarray(scores, dtype=np.float64), image=image, scale=scale,
                         source_shape=(H, W), birth=getattr(model, "last_birth", None), complete=getattr(model, "last_complete", None),
-                        descent=getattr(model, "last_descent", None),
+                        descent=getattr(model, "last_descent", None), relocate=getattr(model, "last_relocate", None),
                         tempering=(getattr(model, "last_run", None) or {}).get("tempering"),
                         recombine=(getattr(model, "last_run", None) or {}).get("recombine"))
 
@@ -149,6 +150,8 @@ def write_results(result: DetectResult, out_dir: str, stem: str, min_score: Opti
         record["birth_complete"] = result.complete
     if result.descent is not None:
         record["descent"] = result.descent
+    if result.relocate is not None:
+        record["relocate"] = result.relocate
     if result.tempering is not None:
         record["tempering"] = result.tempering
     if result.recombine is not None:

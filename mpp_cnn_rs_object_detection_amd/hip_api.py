@@ -105,6 +105,25 @@ DESCENT_REPORT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_added
                                  ("n_nan", "<i8")], align=True)
 DESCEND_DEATHS, DESCEND_BIRTHS = 1, 2
 DESCENT_FIXED_POINT, DESCENT_ROUND_LIMIT, DESCENT_CAPACITY = 0, 1, 2
+#: mpp_relocate_report, one per chain (``MppContext.relocate``); status: 0 a round moved nothing, 1 round limit.  MOVE_CHUNK:
+#: the points a workgroup of the move-gain kernel stages per pass; MOVE_RADIUS_MAX: the largest window radius
+RELOCATE_REPORT_DTYPE = np.dtype([("status", "<i4"), ("rounds", "<i4"), ("n_moved", "<i4"), ("n_after", "<i4"), ("slot_max", "<i4"),
+                                  ("n_positive", "<i4"), ("gain", "<f8"), ("max_gain", "<f8")], align=True)
+RELOCATE_FIXED_POINT, RELOCATE_ROUND_LIMIT = 0, 1
+MOVE_CHUNK = 256
+MOVE_RADIUS_MAX = 7
+
+
+class RelocateReportC(C.Structure):
+    """mpp_relocate_report"""
+    _fields_ = [("status", C.c_int32), ("rounds", C.c_int32), ("n_moved", C.c_int32), ("n_after", C.c_int32), ("slot_max", C.c_int32),
+                ("n_positive", C.c_int32), ("gain", C.c_double), ("max_gain", C.c_double)]
+
+
+def relocate_distance(max_inter: float, radius: int) -> float:
+    """The selection distance of a relocation round, ``2 * (max_inter + radius * sqrt(2))`` in float64: two points further
+    apart neither interact before or after their moves nor share an affected neighbour"""
+    return 2.0 * (float(max_inter) + float(int(radius)) * float(np.sqrt(np.float64(2.0))))
 #: mpp_exchange_record, one per attempted exchange of ``MppContext.run_tempered``: the values as read before the swap
 EXCHANGE_RECORD_DTYPE = np.dtype([("step", "<i8"), ("tile", "<i4"), ("k", "<i4"), ("chain_a", "<i4"), ("chain_b", "<i4"),
                                   ("accepted", "<i4"), ("_pad", "<i4"), ("Ea", "<f8"), ("Eb", "<f8"), ("Ta", "<f8"),
@@ -146,6 +165,8 @@ PROTOTYPES = {
     "mpp_papangelou_all": (_i32, [_vp, _vp]),
     "mpp_select_points": (_i32, [_vp, _i32, _vp, _vp, _dbl, _dbl, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mpp_descend": (_i32, [_vp, _i32, _i32, _dbl, _vp, _vp]),
+    "mpp_move_gains": (_i32, [_vp, _i32, _vp, _vp]),
+    "mpp_relocate": (_i32, [_vp, _i32, _i32, _dbl, _vp, _vp]),
     "mpp_conv3x3_c32": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpp_conv3x3_stem": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mpp_merge_score": (_i32, [_vp, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -637,6 +658,30 @@ class MppContext:
         where = np.full((max(T, 1), self.get_option("point_capacity")), -1, np.int32) if src else None
         self._check(self._L.mpp_descend(self._h, int(what), int(max_rounds), float(min_gain), _ptr(rep), _ptr(where)))
         return (rep[:T], where[:T]) if src else rep[:T]
+
+    def move_gains(self, radius: int = 2):
+        """``mpp_move_gains``: for every point of every chain the largest energy gain of replacing it by the map's candidate
+        at a pixel of the ``(2 radius + 1)^2`` window around it, and that pixel.  Returns ``(gain, to)``: float64
+        ``[n_chains, point_capacity]`` (NaN: every pixel's value is NaN; 0.0 behind a chain's count) and int32 ``[n_chains,
+        point_capacity, 2]`` (``(-1, -1)`` where there is none)."""
+        T, cap = self.get_option("n_chains"), self.get_option("point_capacity")
+        gain = np.zeros((max(T, 1), cap), np.float64)
+        to = np.full((max(T, 1), cap, 2), -1, np.int32)
+        self._check(self._L.mpp_move_gains(self._h, int(radius), _ptr(gain), _ptr(to)))
+        return gain[:T], to[:T]
+
+    def relocate(self, radius: int = 2, max_rounds: int = 16, min_gain: float = 0.0, moved: bool = False):
+        """``mpp_relocate``: every chain of the context moves, round after round, the points whose best replacement by a map
+        candidate within ``radius`` pixels lowers the energy by more than ``min_gain`` -- no two within
+        ``relocate_distance(max_inter, radius)`` in one round -- until a round moves nothing or ``max_rounds`` rounds have
+        moved something.  The points are rewritten in place on the device: slots, counts and order stay.  Returns one record
+        of ``RELOCATE_REPORT_DTYPE`` per chain; with ``moved`` also int32 ``[n_chains, point_capacity]``: how often each slot
+        was rewritten."""
+        T = self.get_option("n_chains")
+        rep = np.zeros(max(T, 1), RELOCATE_REPORT_DTYPE)
+        count = np.zeros((max(T, 1), self.get_option("point_capacity")), np.int32) if moved else None
+        self._check(self._L.mpp_relocate(self._h, int(radius), int(max_rounds), float(min_gain), _ptr(rep), _ptr(count)))
+        return (rep[:T], count[:T]) if moved else rep[:T]
 
     # -- the chain -----------------------------------------------------------------------------
     def merge_score(self, distance: float):

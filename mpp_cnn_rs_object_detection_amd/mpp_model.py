@@ -305,6 +305,33 @@ def format_descent_summary(summary: Dict) -> str:
             f"energy -{abs(summary['gain']):.2f}, {summary['n_negative']} pixel(s) below 0, {summary['n_positive']} point(s) above 0")
 
 
+def check_relocate(config: Dict, world_size: int = 1) -> Optional[Dict]:
+    """``inference.relocate`` of a config (default off): relocation of every image's merged detections -- each point moves
+    to the map candidate within ``radius`` pixels that lowers the energy most (``MPPModel.relocate``).  ``true``, or
+    ``{"radius": 1..7 (2), "max_rounds": .., "min_gain": .., "cycles": 1..16 (4)}`` (any key may be left out); ``cycles`` bounds
+    the repetitions of (descent, relocation) when ``inference.descent`` is on too.  Returns the four parameters as a dict, or
+    None when it is off.  Like the descent it runs on ONE context that holds the whole image, so ranks that share one image
+    refuse it."""
+    params = _rounds_option(config, "relocate", ("radius", "cycles"))
+    if params is None:
+        return None
+    v = (config.get("inference") or {}).get("relocate")
+    given = v if isinstance(v, dict) else {}
+    for k, default, top in (("radius", 2, 7), ("cycles", 4, 16)):
+        x = given.get(k, default)
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 1 <= x <= top:
+            raise ValueError(f"inference.relocate.{k} must be an integer in 1..{top}, got {x!r}")
+        params[k] = int(x)
+    _needs_one_gpu("relocate", world_size)
+    return params
+
+
+def format_relocate_summary(summary: Dict) -> str:
+    """the log line of one image's relocation"""
+    return (f"relocation: ~{summary['n_moved']} object(s) in {summary['rounds']} round(s), energy -{abs(summary['gain']):.2f}, "
+            f"{summary['n_positive']} point(s) above 0")
+
+
 def format_birth_summary(summary: Dict) -> str:
     """the log line of one image's birth map"""
     return (f"birth map: min dE {summary['min_dE']:.2f} at ({summary['argmin'][0]}, {summary['argmin'][1]}), "
@@ -491,32 +518,64 @@ class MPPModel:
         check_recombine(self.config, world_size)
         birth_map, complete = check_birth_map(self.config, world_size), check_birth_complete(self.config, world_size)
         descent = check_descent(self.config, world_size)
-        if not birth_map and complete is None and descent is None:
+        relocate = check_relocate(self.config, world_size)
+        if not birth_map and complete is None and descent is None and relocate is None:
             return self._infer_image(image_data, rank, world_size, region_data, seed)
         if region_data is None:
             region_data = self.region_maps(image_data, rank, world_size)
         merged, scores = self._infer_image(image_data, rank, world_size, region_data, seed)
-        merged, scores, done, descended, birth, dE = self._after_merge(region_data, merged, scores, complete, descent, birth_map)
+        merged, scores, done, descended, moved, birth, dE = self._after_merge(region_data, merged, scores, complete, descent,
+                                                                                relocate, birth_map)
         if complete is not None:
             self.last_complete = done
         if descent is not None:
             self.last_descent = descended
+        if relocate is not None:
+            self.last_relocate = moved
         if birth_map:
             self.last_birth = (dE, birth)
         return merged, scores
 
-    def _after_merge(self, region_data: ImageWMaps, merged, scores, complete, descent, birth_map):
-        """What the options do to an image's merged detections, in this order: the completion, the descent (the map, the files
-        and the figures show the list they leave), the birth map of what is left (the image's own maps and its detections: one
-        context, one tile).  Returns (merged, scores, the three summaries, dE), None for what is off."""
-        done = descended = birth = dE = None
+    def _after_merge(self, region_data: ImageWMaps, merged, scores, complete, descent, relocate, birth_map):
+        """What the options do to an image's merged detections, in this order: the completion, the descent, the relocation (the
+        map, the files and the figures show the list they leave), the birth map of what is left (the image's own maps and its
+        detections: one context, one tile).  With the descent and the relocation both on, the pair (descent, relocation)
+        repeats while the relocation moved something, at most ``cycles`` times: a move can open room for a birth or turn a
+        neighbour's p positive.  Returns (merged, scores, the four summaries -- completion, descent, relocation, birth map --,
+        dE), None for what is off."""
+        done = descended = moved = birth = dE = None
         if complete is not None:
             merged, scores, done = self.complete(region_data, merged)
-        if descent is not None:
+        if descent is not None and relocate is None:
             merged, scores, descended = self.descend(region_data, merged)
+        elif relocate is not None and descent is None:
+            merged, scores, moved = self.relocate(region_data, merged)
+        elif relocate is not None:
+            merged, scores, descended, moved = self._descend_relocate(region_data, merged, relocate["cycles"])
         if birth_map:
             dE, birth = self.birth_map(region_data, merged)
-        return merged, scores, done, descended, birth, dE
+        return merged, scores, done, descended, moved, birth, dE
+
+    def _descend_relocate(self, region_data: ImageWMaps, merged, cycles: int):
+        """(descent, relocation) until a relocation moves nothing, at most ``cycles`` times.  The counts and gains of both
+        summaries are summed over the cycles, one after another in cycle order; their state fields are those of the last
+        descent and of the last relocation.  Ending before the limit leaves a state in which no death, no map birth and no
+        window move lowers the energy by more than ``min_gain``."""
+        descended = moved = None
+        for cycle in range(int(cycles)):
+            merged, scores, d = self.descend(region_data, merged)
+            merged, scores, r = self.relocate(region_data, merged)
+            still = r["n_moved"] == 0
+            if descended is not None:
+                for k in ("n_added", "n_removed", "rounds", "gain", "gain_births", "gain_deaths"):
+                    d[k] = descended[k] + d[k]
+                for k in ("n_moved", "rounds", "gain"):
+                    r[k] = moved[k] + r[k]
+            descended, moved = d, r
+            moved["cycles"] = cycle + 1
+            if still:
+                break
+        return merged, scores, descended, moved
 
     def _image_set(self, region_data: ImageWMaps, merged, room: int) -> EPointsSet:
         """one context with the image as its single tile and ``merged`` as its configuration, with room for ``room`` more points"""
@@ -539,6 +598,22 @@ class MPPModel:
         summary = {k: r[k] for k in ("n_added", "n_removed", "rounds", "gain", "gain_births", "gain_deaths", "status", "max_p",
                                      "slot_max", "n_positive", "min_dE", "argmin", "n_negative", "n_nan")}
         logging.info(format_descent_summary(summary))
+        return agg, scores, summary
+
+    def relocate(self, region_data: ImageWMaps, merged):
+        """Relocation of one image's detections (``inference.relocate``, ``EPointsSet.relocate``): one context with the image
+        as its single tile and ``merged`` as its configuration, as ``descend`` builds it.  Returns (relocated, scores,
+        summary): the ``EPointsSet`` in its order with a new ``Rectangle`` in every slot that moved, the final Papangelou scores
+        of EVERY point of it (``papangelou_all``), summary = {"n_moved", "rounds", "gain", "status", "cycles", "max_gain",
+        "slot_max", "n_positive"}; logs one line."""
+        p = check_relocate(self.config) or {"radius": 2, "max_rounds": 16, "min_gain": 0.0, "cycles": 4}
+        agg = self._image_set(region_data, merged, 64)
+        r = agg.relocate(energy_combinator=self.energy_model, radius=p["radius"], max_rounds=p["max_rounds"], min_gain=p["min_gain"])
+        scores = agg.papangelou_all(energy_combinator=self.energy_model) if len(agg) else np.zeros(0)
+        summary = {k: r[k] for k in ("n_moved", "rounds", "gain", "status")}
+        summary["cycles"] = 1
+        summary.update({k: r[k] for k in ("max_gain", "slot_max", "n_positive")})
+        logging.info(format_relocate_summary(summary))
         return agg, scores, summary
 
     def complete(self, region_data: ImageWMaps, merged):
@@ -881,13 +956,14 @@ class MPPModel:
     TILE_SHARD_MIN = 2048
 
     def _result_record(self, patch_id: int, out_file: str, image_data: ImageWMaps, merged, scores, birth_summary=None,
-                       complete_summary=None, tempering=None, recombine=None, descent=None) -> dict:
+                       complete_summary=None, tempering=None, recombine=None, descent=None, relocate=None) -> dict:
         """Write ``NNNN_results.pkl`` of one image (mpp_model.py:333-366) and return what the two DOTA translators need
         of it (plain arrays: the records of all ranks travel to rank 0 in one gather).  ``birth_summary``
         (``inference.birth_map``) and ``complete_summary`` (``inference.birth_complete``, key ``birth_complete``): one more
         key of the pickle each; ``tempering`` (``inference.tempering``): the image's ``tempering_summary``, key ``tempering``;
         ``recombine`` (``inference.recombine``): the image's ``recombine_summary``, key ``recombine``; ``descent``
-        (``inference.descent``): the summary of ``descend``, key ``descent``."""
+        (``inference.descent``): the summary of ``descend``, key ``descent``; ``relocate`` (``inference.relocate``): the
+        summary of ``relocate``, key ``relocate``."""
         pts = list(merged)
         pred_params = [sra_to_wla(p.size, p.ratio, p.angle) for p in pts]
         pred_centers = np.array([[p.x, p.y] for p in pts]).reshape(-1, 2)
@@ -914,6 +990,8 @@ class MPPModel:
             record["recombine"] = recombine
         if descent is not None:
             record["descent"] = descent
+        if relocate is not None:
+            record["relocate"] = relocate
         with open(out_file, "wb") as f:
             pickle.dump(record, f)
         return {"patch_id": patch_id, "gt_poly": gt_poly, "difficult": difficult, "cats": cats, "score01": score01,
@@ -968,6 +1046,7 @@ class MPPModel:
         # (an image shared by all ranks refuses the option in ``infer_image``, before its first collective)
         birth_map, complete = check_birth_map(self.config), check_birth_complete(self.config)
         descent = check_descent(self.config)
+        relocate = check_relocate(self.config)
         check_tempering(self.config)
         check_recombine(self.config)
         dataset = self.config["dataset"]["dataset"]
@@ -1030,14 +1109,14 @@ class MPPModel:
 
         try:
             for k, image_data, region_data, merged, scores, tempered, recombined in inferred():
-                merged, scores, done, descended, birth, dE = self._after_merge(region_data, merged, scores, complete, descent,
-                                                                                 birth_map)
+                merged, scores, done, descended, moved, birth, dE = self._after_merge(region_data, merged, scores, complete,
+                                                                                        descent, relocate, birth_map)
                 if birth_map:
                     self._write_birth_figure(os.path.join(results_dir, f"{todo[k][0]:04}_birth_energy.png"), dE, merged)
                     del dE
                 records.append(self._result_record(todo[k][0], todo[k][1], image_data, merged, scores, birth_summary=birth,
                                                    complete_summary=done, tempering=tempered, recombine=recombined,
-                                                   descent=descended))
+                                                   descent=descended, relocate=moved))
                 if figures:
                     self._write_figures(todo[k][0], results_dir, image_data, region_data, merged, scores)
         except Exception as e:                      # noqa: BLE001 -- several ranks: reported through the gather, raised by all

@@ -320,6 +320,27 @@ class EPointsSet:
                    n_nan=int(rep["n_nan"]))
         return out
 
+    def relocate(self, energy_combinator=None, radius: int = 2, max_rounds: int = 16, min_gain: float = 0.0) -> dict:
+        """Relocation (``mpp_relocate``): rounds in which the points whose best replacement by a map candidate within
+        ``radius`` pixels lowers the energy by more than ``min_gain`` -- no two within ``hip_api.relocate_distance`` -- are
+        rewritten in place, until a round moves nothing or ``max_rounds`` rounds have moved something.  The set keeps its
+        order and its length; every slot that moved gets a new ``Rectangle`` read back from the context.  Returns {"status"
+        (0 nothing left to move, 1 round limit), "rounds", "n_moved", "n_after", "gain", "max_gain", "slot_max",
+        "n_positive"}, the last three of the returned set's move gains."""
+        self._use(energy_combinator)
+        rep, moved = self._ctx.relocate(radius, max_rounds, min_gain, moved=True)
+        rep, moved = rep[0], moved[0]
+        if int(rep["n_moved"]):
+            xy, marks = self._ctx.get_points(0)
+            assert len(xy) == len(self._points) == int(rep["n_after"])
+            for s in np.flatnonzero(moved[:len(xy)] > 0):
+                (x, y), m = xy[s], marks[s]
+                self._points[s] = Rectangle(int(x), int(y), size=float(m[0]), ratio=float(m[1]), angle=float(m[2]))
+            self._index = {u: k for k, u in enumerate(self._points)}
+        return {"status": int(rep["status"]), "rounds": int(rep["rounds"]), "n_moved": int(rep["n_moved"]),
+                "n_after": int(rep["n_after"]), "gain": float(rep["gain"]), "max_gain": float(rep["max_gain"]),
+                "slot_max": int(rep["slot_max"]), "n_positive": int(rep["n_positive"])}
+
     # -- mutation ------------------------------------------------------------------------------------
     def apply_perturbation(self, p: Perturbation, inplace: bool = False) -> "EPointsSet":
         """Reference ``energy_point_set.py:118-154``."""
